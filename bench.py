@@ -15,6 +15,12 @@ With N > 1 the SAME graph is sharded by node range (strong scaling): each rank o
 iteration ends with one grouped RCCL all-gather of the owned state rows + convergence flag.  No torch in the process: ranks
 read RANK / LOCAL_RANK / WORLD_SIZE from the environment (set by either launcher) and exchange the RCCL id through a file.
 
+A plain run sets up, warms up, times --steps Loops and prints the line (headline, iterations per step, and the live
+roofline of the timed Loops' own kernel events).  --full adds, after the timed region, everything else: the bit-exact
+path timed beside the default one, the cold-aggregates and PCIe-inclusive Loops, the other BASELINE configs, the CPU
+baseline with the full-size parity check against the C oracle (`parity_ok`), and with N > 1 the sharded-vs-unsharded
+check.  --dump-outputs DIR writes what the last timed Loop returned (see dump_outputs) before any of that runs.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -370,6 +376,22 @@ def profile_figures():
     return None
 
 
+DUMP_STATE_ROWS = 200_000        # state rows in a dump: 200 k x 64 fp32 = 51 MB, with the same rows of the output and their ids < 64 MB
+
+
+def dump_outputs(out_dir, k, state, output, seed=20261003):
+    """What a caller of the timed path receives from its last Loop (k, state [N, Ds], output [N, T]; with N > 1: rank 0's rows),
+    as DIR/<name>.npy: a fixed, seeded sample of the state and output rows (all of them up to DUMP_STATE_ROWS), the sampled row ids
+    and k.  The same arguments give the same inputs and the same sample, so two builds can be compared file by file."""
+    n = state.shape[0]
+    rows = np.arange(n) if n <= DUMP_STATE_ROWS else np.sort(np.random.default_rng(seed).choice(n, DUMP_STATE_ROWS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'iterations.npy'), np.array([k], np.float64))
+    np.save(os.path.join(out_dir, 'state_rows.npy'), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, 'state.npy'), np.ascontiguousarray(state[rows], dtype=np.float32))
+    np.save(os.path.join(out_dir, 'output.npy'), np.ascontiguousarray(output[rows], dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -393,7 +415,12 @@ def main():
     ap.add_argument('--no-other-configs', action='store_true', help='skip the untimed configs[1] / configs[4] figures under config.other_configs')
     ap.add_argument('--cpu-iters', type=int, default=30, help='bodies of the CPU-baseline sample = depth of the full-size parity check (default: the workload\'s max_iter)')
     ap.add_argument('--rank-timeout', type=float, default=900.0, help='N > 1: seconds a rank may spend in the timed / validation region before it gives up (exit 124)')
+    ap.add_argument('--full', action='store_true', help='after the timed region: the exact path, cold-aggregates and PCIe-inclusive Loops, other configs, '
+                                                       'CPU baseline and parity check, N > 1 sharded check (off: only the headline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the state / output sample and k of the last timed Loop as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:      # bare multi-GPU invocation: become the launcher (no GPU call in this process)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -457,20 +484,24 @@ def main():
         t0 = time.perf_counter()
         k_total, iter_ms, gap_ms = 0.0, [], []
         for _ in range(args.steps):
-            k_total += loop.run()
+            k_last = loop.run()
+            k_total += k_last
             tm = loop.timing()
             iter_ms.append(tm['avg_iter_ms'])
             gap_ms.append(tm['avg_between_bodies_ms'])
         elapsed = barrier(time.perf_counter() - t0)          # device sync, then max over ranks
         loop.set_profiling(False)
 
-    # N > 1: the line must validate itself - nobody stands beside a driver's 8-GPU run.  Every rank runs 3 bodies of the SHARDED job and
+    if args.dump_outputs and rank == 0:                      # before anything below runs the loop again
+        dump_outputs(args.dump_outputs, k_last, loop.state(), loop.output())
+
+    # --full, N > 1: the line must validate itself - nobody stands beside a driver's 8-GPU run.  Every rank runs 3 bodies of the SHARDED job and
     # the same 3 bodies UNSHARDED on its own device (the whole graph fits one GPU) and compares its own rows: after three bodies a row
     # depends on rows of every other rank (the synthetic graph has no locality), so a wrong peer, count or offset in any exchange shows
     # in every rank's rows.  The largest difference over all ranks (allreduce max) and the agreement of k go into the line; the exact
     # path (impl 1) must agree bit for bit, and so does the default path (a node's arithmetic does not depend on its tile).
     sharded_check = None
-    if world > 1:
+    if args.full and world > 1:
         with Watchdog(args.rank_timeout, 'sharded-vs-unsharded validation', rank):
             whole = engine.Graph(n, s['indptr'], s['adj_src'], s['adj_w'], s['arc_w'], s['arc_labels_csr'], s['nodes'], np.ones(n, np.uint8), device=local_rank)
             per_impl, diff_all, k_bad_all = {}, 0.0, 0.0
@@ -502,10 +533,10 @@ def main():
                                      'must agree bit for bit); max over ranks'}
             del st_s, out_s, st_u, out_u
 
-    # the bit-exact fused path (impl 1) on the same inputs, one untimed + one timed Loop: reported beside the headline, and
+    # --full: the bit-exact fused path (impl 1) on the same inputs, one untimed + one timed Loop: reported beside the headline, and
     # the two final states are compared (the default path must stay within fp32 rounding noise of the exact one)
     exact = None
-    if world == 1 and impl_used == 2:
+    if args.full and world == 1 and impl_used == 2:
         final_default = loop.state()
         loop.set_impl(1)
         loop.run()
@@ -531,10 +562,10 @@ def main():
         one.close()
         del final_exact, final_default, s2
 
-    # the reference builds the label aggregates (GNN.py:259, :263) in every Loop(); the engine keeps them between Loops until
+    # --full: the reference builds the label aggregates (GNN.py:259, :263) in every Loop(); the engine keeps them between Loops until
     # the labels change.  Cold figure: the same Loop with the kept aggregates dropped before each call.
     cold_ms = None
-    if world == 1:
+    if args.full and world == 1:
         barrier()
         t3 = time.perf_counter()
         for _ in range(2):
@@ -543,12 +574,14 @@ def main():
         barrier()
         cold_ms = 1e3 * (time.perf_counter() - t3) / 2
 
-    # boundary-inclusive rate (never `value`): host state0 in, host state + output back, one Loop (DESIGN.md "Measurement")
-    t1 = time.perf_counter()
-    loop.set_state0(state0[rb:rb + nr])
-    k_e2e = loop.run()
-    loop.state(), loop.output()
-    e2e_s = time.perf_counter() - t1
+    # --full: boundary-inclusive rate (never `value`): host state0 in, host state + output back, one Loop (DESIGN.md "Measurement")
+    e2e_rate = None
+    if args.full:
+        t1 = time.perf_counter()
+        loop.set_state0(state0[rb:rb + nr])
+        k_e2e = loop.run()
+        loop.state(), loop.output()
+        e2e_rate = nr * k_e2e / (time.perf_counter() - t1)
 
     exit_code = 0
     if rank == 0:
@@ -559,7 +592,7 @@ def main():
         # HBM bytes per launch of the dominant kernel come from a separate rocprofv3 --pmc run of this same command
         # (tools/profile.sh; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950), committed under profiles/
         traffic, traffic_src = None, None
-        pf = profile_figures() if (world == 1 and impl_used == 2 and args.nodes == 1_000_000) else None
+        pf = profile_figures() if (args.full and world == 1 and impl_used == 2 and args.nodes == 1_000_000) else None
         if pf:
             traffic = pf.get('hbm_bytes_per_launch')
             traffic_src = pf['source'] + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; FETCH_SIZE doubled as the guide prescribes for gfx950)'
@@ -581,7 +614,7 @@ def main():
                        'tile_form': {1: 'one wave per 32-node tile (k_fused)', 2: 'wave pair per 32-node tile (k_fused_pair)'}.get(tile_form, 'n/a') if impl_used == 2 else 'n/a',
                        'exact_f32_mfma_path': exact,
                        'cold_aggregates_ms_per_step': cold_ms,
-                       'pcie_inclusive_updates_per_s': nr * k_e2e / e2e_s},
+                       'pcie_inclusive_updates_per_s': e2e_rate},
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
                          'traffic': traffic, 'traffic_source': traffic_src,
                          'kernel': 'gnn_fused_iteration' if impl_used else 'spmm + dense x3 + check (sum of the per-iteration kernels)',
@@ -610,19 +643,19 @@ def main():
                                          'between the end of one body\'s kernel and the start of the next (all-gather of rows + flags, or the sliced '
                                          'layout\'s pack / all-to-all / aggregation / all-to-all / unpack)',
                                  'sharded_check': sharded_check}
-        if world == 1 and not args.no_other_configs and args.nodes == 1_000_000:
+        if args.full and world == 1 and not args.no_other_configs and args.nodes == 1_000_000:
             try:             # untimed extras: whatever happens there must not cost the headline line
                 line['config']['other_configs'] = other_configs(engine, s, local_rank)
             except Exception as ex:      # noqa: BLE001
                 line['config']['other_configs'] = {'error': repr(ex)}
         parity_ok = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(s, st, ou, state0, d, args.cpu_iters, engine, local_rank, full=(graph, mst, mou))
             parity_ok = line['cpu_baseline'].pop('parity_ok', None)
             line['default_path_values'] = line['cpu_baseline'].pop('default_path_values', None)      # what parity_ok says about the TIMED path's values
-        if world > 1:
+        if sharded_check is not None:
             parity_ok = sharded_check['ok']
-        line['parity_ok'] = parity_ok       # null: not checked in this invocation (--no-cpu-baseline)
+        line['parity_ok'] = parity_ok       # null: not checked in this invocation (no --full, or --no-cpu-baseline)
         print(json.dumps(line), flush=True)
         if parity_ok is False:
             print('bench.py: PARITY FAILED - ' + ('the sharded run differs from the unsharded one' if world > 1 else

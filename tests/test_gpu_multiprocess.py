@@ -159,7 +159,7 @@ def test_bench_launcher_runs_all_ranks_end_to_end(gpus, exchange):
     env = dict(os.environ, GNN_RCCL_LIBRARY=_mock(), GNN_BENCH_ONE_DEVICE='1', OMP_NUM_THREADS='2')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'): env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--steps', '2', '--warmup', '1', '--nodes', '60000',
-           '--exchange', exchange, '--no-cpu-baseline', '--no-other-configs']
+           '--exchange', exchange, '--full', '--no-cpu-baseline', '--no-other-configs']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])

@@ -7,7 +7,7 @@ OUT=gpurun_out/ab_$1.txt; ROUNDS=$2; shift 2
 for r in $(seq $ROUNDS); do
   for n in "$@"; do
     if [ "$n" = product ]; then L=$PWD/gnn_tf_2.x_amd/GNN/libgnn_hip.so; else L=$PWD/gnn_tf_2.x_amd/GNN/libgnn_hip_ab_$n.so; fi
-    GNN_HIP_LIBRARY=$L python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs ${AB_BENCH_ARGS} 2>>$OUT.err | python3 -c "
+    GNN_HIP_LIBRARY=$L python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-configs ${AB_BENCH_ARGS} 2>>$OUT.err | python3 -c "
 import json,sys
 for l in sys.stdin:
     try: j=json.loads(l)

@@ -44,7 +44,7 @@ fig = {'kernel': k, 'hbm_bytes_per_launch': out['hbm_bytes_per_launch'],
        'effective_clock_ghz': cycles / (prof_ms_all * 1e6) if prof_ms_all else None, 'profiled_avg_launch_ms': prof_ms, 'profiled_avg_launch_ms_all_launches': prof_ms_all,
        'definitions': 'mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x kernel cycles); valu_busy = 4 x SQ_ACTIVE_INST_VALU (quad-cycles) / '
                       'the same; kernel cycles = GRBM_GUI_ACTIVE / 8 XCDs; lds_bank_conflict_share = SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS; '
-                      'per launch averages over all launches of the kernel in `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline`'}
+                      'per launch averages over all launches of the kernel in `python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline`'}
 json.dump(fig, open(f'profiles/{tag}_pmc.json', 'w'), indent=1)
 shutil.copy(d + 'summary.txt', f'profiles/{tag}_rocprofv3_summary.txt')
 shutil.copy(d + 'stats/stats_kernel_stats.csv', f'profiles/{tag}_kernel_stats.csv')
@@ -55,7 +55,7 @@ rows = [r for r in csv.DictReader(open(d + 'stats/stats_kernel_trace.csv')) if r
 dur = [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e6 for r in rows]
 loops = [dur[i:i + 30] for i in range(0, len(dur) - len(dur) % 30, 30)]
 with open(f'profiles/{tag}_fused_kernel_per_loop.txt', 'w') as fo:
-    fo.write(f'{k}\n{len(dur)} launches in the rocprofv3 kernel trace of `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline`, mean {sum(dur) / len(dur):.4f} ms\n')
+    fo.write(f'{k}\n{len(dur)} launches in the rocprofv3 kernel trace of `python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline`, mean {sum(dur) / len(dur):.4f} ms\n')
     names = ['warm-up Loop', 'timed step 1', 'timed step 2', 'exact-path comparison / cold-aggregates Loop', 'cold-aggregates Loop', 'PCIe-inclusive Loop']
     for i, l in enumerate(loops):
         fo.write(f'Loop {i} ({names[i] if i < len(names) else "extra"}): mean of its 30 launches {sum(l) / len(l):.4f} ms, min {min(l):.4f}, max {max(l):.4f}\n')

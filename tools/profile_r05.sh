@@ -6,12 +6,12 @@
 #  tools/collect_profile.py r05.
 export TMPDIR=/tmp
 O=gpurun_out
-python3 bench.py > $O/bench_r05.json 2> $O/bench_r05.err
+python3 bench.py --full > $O/bench_r05.json 2> $O/bench_r05.err
 bash tools/profile.sh r05 > $O/profile_r05.log 2>&1
 tail -25 $O/profile_r05.log
 OUT=$O/prof_r05x
 mkdir -p $OUT
-BENCH="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs"
+BENCH="python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_COEXEC_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR -d $OUT/coexec -o pmc --output-format csv -- $BENCH > $OUT/coexec.log 2>&1
 rocprofv3 --kernel-trace --pmc TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum -d $OUT/tcp -o pmc --output-format csv -- $BENCH > $OUT/tcp.log 2>&1
 rocprofv3 --kernel-trace --pmc TA_TA_BUSY_sum TA_BUFFER_READ_WAVEFRONTS_sum TCP_TCC_WRITE_REQ_sum GRBM_GUI_ACTIVE -d $OUT/ta -o pmc --output-format csv -- $BENCH > $OUT/ta.log 2>&1

@@ -18,7 +18,7 @@ SMALL_ONLY=1 rocprofv3 --kernel-trace --stats -d $O/prof_train_mutag -o train --
 tail -3 $O/train_mutag.log
 # 2. stand-in rehearsals: 4 rank processes on this one GPU over tests/mock_rccl (timings are those of /dev/shm and a shared GPU, NOT of xGMI)
 for ex in halo full slice; do
-  GNN_RCCL_LIBRARY=$PWD/tests/mock_rccl/libmock_rccl.so GNN_BENCH_ONE_DEVICE=1 OMP_NUM_THREADS=2 timeout -k 10 500 python3 bench.py --gpus 4 --steps 1 --warmup 1 --exchange $ex > $O/standin_$ex.json 2> $O/standin_$ex.err
+  GNN_RCCL_LIBRARY=$PWD/tests/mock_rccl/libmock_rccl.so GNN_BENCH_ONE_DEVICE=1 OMP_NUM_THREADS=2 timeout -k 10 500 python3 bench.py --gpus 4 --steps 1 --warmup 1 --full --exchange $ex > $O/standin_$ex.json 2> $O/standin_$ex.err
   python3 -c "
 import json,sys
 j=json.load(open('$O/standin_$ex.json'))

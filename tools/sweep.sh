@@ -6,7 +6,7 @@ OUT=gpurun_out/sweep_${1:-x}.txt
 : > $OUT
 run() {
   echo "== $*" >> $OUT
-  env "$@" python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs 2>>$OUT | python3 -c "
+  env "$@" python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-other-configs 2>>$OUT | python3 -c "
 import json,sys
 for l in sys.stdin:
     try: j=json.loads(l)
