@@ -20,7 +20,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_mlp_create', 'gnn_mlp_set_weights', 'gnn_mlp_get_weights', 'gnn_mlp_reset_optimizer', 'gnn_mlp_forward', 'gnn_mlp_destroy', 'gnn_loop_create',
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
-           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
+           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
 
@@ -54,6 +54,17 @@ def loss_grad(loss_kind: int, targets, out, sample_weights):
     loss = C.c_double()
     _check(lib().gnn_loss_grad(C.c_int(loss_kind), C.c_int64(o.shape[0]), C.c_int(o.shape[1]), _fp(t), _fp(o), _fp(w), C.byref(loss), _fp(d)))
     return float(loss.value), d
+
+
+def split_f16(values, exponent=None):
+    """The host-side fp16 x 2 cut of the default path's weight image (gnn_split_f16 / gnn_split_f16_exponent): returns (p0, p1, e) with
+    p0 = fp16(v 2^e), p1 = fp16(v 2^e - p0); e defaults to the weight-scale exponent of max |values|."""
+    v = np.ascontiguousarray(values, np.float32).ravel()
+    if exponent is None:
+        exponent = int(lib().gnn_split_f16_exponent(C.c_float(float(np.max(np.abs(v))) if v.size else 0.0)))
+    p0, p1 = np.empty(v.size, np.uint16), np.empty(v.size, np.uint16)
+    lib().gnn_split_f16(v.ctypes.data_as(C.c_void_p), C.c_int(v.size), C.c_int(int(exponent)), p0.ctypes.data_as(C.c_void_p), p1.ctypes.data_as(C.c_void_p))
+    return p0.view(np.float16), p1.view(np.float16), int(exponent)
 
 
 def _check(rc: int):
@@ -570,6 +581,20 @@ class Loop:
         often that has happened on this loop)."""
         a, b = C.c_int(0), C.c_int(0)
         _check(lib().gnn_loop_gate_info(self._h, C.byref(a), C.byref(b)))
+        return bool(a.value), int(b.value)
+
+    def set_pieces(self, pieces: int) -> int:
+        """gnn_loop_set_pieces: piece format of impl 2 - 2 = two fp16 pieces per operand (default), 3 = three bf16 pieces.  For A/B runs and
+        tests, not a user-facing mode."""
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_pieces(self._h, C.c_int(int(pieces)), C.byref(used)))
+        return used.value
+
+    def range_info(self) -> tuple:
+        """gnn_loop_range_info: (the last run was repeated with bf16 pieces because an activation left the fp16 range, how often that has
+        happened on this loop)."""
+        a, b = C.c_int(0), C.c_int(0)
+        _check(lib().gnn_loop_range_info(self._h, C.byref(a), C.byref(b)))
         return bool(a.value), int(b.value)
 
     def set_persistent(self, enable: bool) -> bool:

@@ -227,8 +227,9 @@ struct gnn_mlp {
     // fused-kernel weight image (see gnn_fused.hip), rebuilt by set_weights
     float *packed = nullptr;
     size_t packed_floats = 0;
-    int *packed_split = nullptr;        // bf16-piece weight image of the split-arithmetic fused kernel (impl 2)
+    int *packed_split = nullptr;        // piece weight images of the split-arithmetic fused kernel (impl 2): [bf16 x 3 | fp16 x 2]
     size_t packed_split_dwords = 0;
+    int split_exp[3] = {0, 0, 0};       // fp16 x 2 image: power-of-two exponent e_w of every layer's weight scale (gnn_fused_pack)
     int pack_nlc = -1;                  // node-label columns of the concat the split image was laid out for (alignment hole)
     bool pack_dirty = true;             // the images are rebuilt on the next fused use (training rewrites the weights every step)
     uint64_t version = 0;
@@ -275,9 +276,13 @@ struct gnn_loop {
     float *feats = nullptr, *out = nullptr, *otmp[2] = {nullptr, nullptr};
     int *flags = nullptr;                   // [(max_iter+2), world, GNN_FLAG_WORDS]
     int *tile_ctr = nullptr;                // fused path: one tile counter per iteration [max_iter + 1]
-    int *kfinal_dev = nullptr, *kfinal_host = nullptr;   // device [4]: k, status word of the persistent loop, "a gate of this run is not certified" (impl 2), pad; host mirror [4]
+    int *kfinal_dev = nullptr, *kfinal_host = nullptr;   // device [4]: k, status word of the persistent loop, "a gate of this run is not certified" (impl 2),
+                                                         // "an operand left the fp16 range" (impl 2, format 2); host mirror [4]
     int certified_reruns = 0;               // Loops of this handle that were repeated on impl 1 because a gate of the impl-2 run was not certified
     bool last_run_rerun = false;
+    int pieces = 2;                         // gnn_loop_set_pieces: piece format of impl 2 (2 = fp16 x 2, 3 = bf16 x 3)
+    int range_reruns = 0;                   // Loops repeated in format 3 because an activation left the fp16 range (kfinal word 3)
+    bool last_run_range_rerun = false;
     bool small_words_clean = false;         // the double-buffered gate words of the persistent loop are zero / in their run-parity state
     unsigned small_runs = 0;
     float *small_xs = nullptr;              // the persistent loop's padded exchange rows (gnn_small.hip), allocated with its first run

@@ -397,6 +397,15 @@ __global__ void k_finalize(const int *flags, int world, int max_iter, int *kfina
     }
     amb = __any(amb) ? 1 : 0;
     if (lane == 0) kfinal[2] = amb;
+    // range guard of the fp16-piece format (gnn_fused_kernel.h, gnn_flag_raise_range): word 3 of the gates 1 .. k_final written by the bodies
+    // that ran.  The other arithmetic never raises it.
+    int range = 0;
+    for (int k = 1 + lane; k <= k_final && k <= max_iter; k += 64) {
+        const int *gate = flags + (size_t)k * world * GNN_FLAG_WORDS;
+        for (int p = 0; p < world * GNN_FLAG_SLOTS; ++p) range |= gate[p * GNN_FLAG_STRIDE + 3];
+    }
+    range = __any(range) ? 1 : 0;
+    if (lane == 0) kfinal[3] = range;
 }
 
 // apply_filters(): feats[m] = [state_final[row_m] | nodes[row_m] (iff D > 0)]
@@ -1340,7 +1349,7 @@ extern "C" int gnn_loop_create(gnn_graph *g, gnn_mlp *net_state, gnn_mlp *net_ou
     if (!rc) rc = dev_alloc(&l->kfinal_dev, 4);        // k, status word of the persistent loop, "gate not certified", pad
     if (!rc) rc = dev_alloc(&l->tile_ctr, (2 * ((size_t)max_iter + 1) + 3) & ~(size_t)3);      // one ticket counter per body (the second half is spare: a partial last tile used to get a launch of its own)
     if (!rc && hipHostMalloc((void **)&l->kfinal_host, 4 * sizeof(int)) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipHostMalloc");
-    if (!rc) l->kfinal_host[1] = l->kfinal_host[2] = 0;
+    if (!rc) l->kfinal_host[1] = l->kfinal_host[2] = l->kfinal_host[3] = 0;
     if (!rc && hipHostMalloc((void **)&l->gate_host, sizeof(int) * (size_t)world * GNN_FLAG_WORDS) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipHostMalloc");
     if (!edge_width) {      // the edge-based buffers are sized in gnn_loop_set_edge_readout
         if (!rc) rc = dev_alloc(&l->feats, (size_t)g->n_masked * l->wf);
@@ -1372,6 +1381,22 @@ extern "C" int gnn_loop_set_impl(gnn_loop *l, int impl, int *used)
     ARGCHK(l && impl >= 0 && impl <= 2, "impl must be 0 (unfused), 1 (fused, exact f32 MFMA) or 2 (fused, split bf16 MFMA)");
     l->impl_req = impl;
     if (used) *used = (impl >= 1 && gnn_fused_supported(l)) ? impl : 0;
+    return GNN_OK;
+}
+
+extern "C" int gnn_loop_set_pieces(gnn_loop *l, int pieces, int *used)
+{
+    ARGCHK(l && (pieces == 2 || pieces == 3), "pieces must be 2 (fp16 x 2) or 3 (bf16 x 3)");
+    l->pieces = pieces;
+    if (used) *used = pieces;
+    return GNN_OK;
+}
+
+extern "C" int gnn_loop_range_info(const gnn_loop *l, int *last_run_repeated, int *repeats_total)
+{
+    ARGCHK(l, "loop is NULL");
+    if (last_run_repeated) *last_run_repeated = l->last_run_range_rerun ? 1 : 0;
+    if (repeats_total) *repeats_total = l->range_reruns;
     return GNN_OK;
 }
 
@@ -1834,7 +1859,7 @@ static int loop_finish(gnn_loop *l, bool finalize, bool output_done)
     }
     if (finalize) {
         HIPCHK(hipMemcpyAsync(l->kfinal_host, l->kfinal_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(l->kfinal_host + 2, l->kfinal_dev + 2, sizeof(int), hipMemcpyDeviceToHost, st));      // "a gate was not certified"
+        HIPCHK(hipMemcpyAsync(l->kfinal_host + 2, l->kfinal_dev + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, st));      // "a gate was not certified", "out of fp16 range"
     }
     if (output_done) return GNN_OK;     // (the persistent loop wrote k into the pinned host words and ran the output stage itself)
     const float *own0 = l->state[0] + (size_t)l->own_off * l->Ds, *own1 = l->state[1] + (size_t)l->own_off * l->Ds;
@@ -1989,7 +2014,25 @@ static int run_loops(gnn_loop **ls, int n, float *k_out)
     // Certified gate (gnn_common.h): a gate of this impl-2 run was decided by a borderline node and no robust mover - its k is not
     // guaranteed to be the bit-exact chain's.  The Loop is repeated on impl 1 and THAT run's k / state / output are what the caller gets.
     // Every rank reads the same exchanged flag words, so all ranks of a sharded job take this branch together.
-    for (int r = 0; r < n; ++r) ls[r]->last_run_rerun = false;
+    for (int r = 0; r < n; ++r) ls[r]->last_run_rerun = ls[r]->last_run_range_rerun = false;
+    // Range guard of the fp16-piece format: some body of this run cut an operand past the fp16 range (its results may hold infinities).  The
+    // Loop is repeated in the bf16-piece format, which takes the whole fp32 range; that run applies the certified gate below itself.  The flag
+    // words are exchanged like the gate words, so every rank takes this branch together.
+    if (!small && fused[0] && ls[0]->impl_req == 2 && ls[0]->pieces == 2 && ls[0]->kfinal_host[3] != 0) {
+        static bool told_range = false;
+        if (!told_range && !getenv("GNN_QUIET")) {
+            told_range = true;
+            fprintf(stderr, "libgnn_hip: an activation of a default-path Loop left the range of the fp16-piece arithmetic: the Loop is repeated with bf16 "
+                            "pieces (gnn_loop_range_info counts these)\n");
+        }
+        for (int r = 0; r < n; ++r) ls[r]->pieces = 3;
+        rc = run_loops(ls, n, k_out);
+        for (int r = 0; r < n; ++r) {
+            ls[r]->pieces = 2;
+            if (rc == GNN_OK) { ls[r]->last_run_range_rerun = true; ++ls[r]->range_reruns; }
+        }
+        return rc;
+    }
     if (!small && fused[0] && ls[0]->impl_req == 2 && ls[0]->kfinal_host[2] != 0) {
         static bool told = false;       // once per process: the caller gets the exact path's results, at the exact path's price
         if (!told && !getenv("GNN_QUIET")) {
@@ -2075,7 +2118,7 @@ extern "C" int gnn_loop_run_many(gnn_loop **loops, int n, float *k_out /* [n] */
         gnn_loop *l = loops[i];
         bool fused = false;
         if ((rc = loop_prepare(l, &fused))) return drain(rc);
-        l->last_run_rerun = false;                      // (the persistent path is exact arithmetic and never repeats; run_loops sets it for the others)
+        l->last_run_rerun = l->last_run_range_rerun = false;      // (the persistent path is exact arithmetic and never repeats; run_loops sets it for the others)
         if (!(fused && gnn_small_supported(l))) continue;
         const long wgs = (long)((l->g->n_rows + 15) / 16);      // upper bound of the launch's grid (16- or 32-node tiles)
         if (in_flight && in_flight + wgs > cap && (rc = collect())) return drain(rc);

@@ -6,6 +6,10 @@
 constexpr int GNN_FUSED_MAXL = 3;
 constexpr int GNN_FUSED_WAVES = 8;                 // waves per (persistent) workgroup; w and w + 4 share a SIMD
 constexpr int GNN_FUSED_THREADS = 64 * GNN_FUSED_WAVES;
+// fp16-piece format of the split arithmetic (gnn_fused_kernel.h): activations are cut at the fixed scale 2^GNN_F16_EX, and a scaled activation
+// of magnitude >= GNN_F16_LIMIT (the largest finite fp16) sends the Loop back to the bf16-piece format
+#define GNN_F16_EX 4
+#define GNN_F16_LIMIT 65504.0f
 
 struct GnnFusedArgs {
     // graph
@@ -33,10 +37,14 @@ struct GnnFusedArgs {
     int *tile_ctr;           // device-wide tile counter of this iteration (zeroed at the start of gnn_loop_run)
     int wstride;             // 1 normally; 0 (GNN_FUSED_DEBUG=1, timing experiments only) makes every K-step re-read step 0
     int stagger;             // s_sleep(127) rounds the second half of the waves waits before its first tile
-    // split arithmetic (impl 2): per layer the bf16-piece weight image [chunk][out tile][piece][lane][8 bf16], and the number
+    // split arithmetic (impl 2): per layer the piece weight image [chunk][out tile][piece][lane][8 bf16 / fp16], and the number
     // of K = 16 chunks of layer 0
     const int *Ws[GNN_FUSED_MAXL];
     int chunks0;
+    // piece format (gnn_loop_set_pieces): 3 = three bf16 pieces, 2 = two fp16 pieces.  Format 2 scales weights and activations by powers of
+    // two: bsc[l] = 2^(e_w + e_x) multiplies layer l's bias where its accumulator starts, usc[l] = 2^-(e_w + e_x) undoes it (1 in format 3)
+    int pieces;
+    float bsc[GNN_FUSED_MAXL], usc[GNN_FUSED_MAXL];
     // the same image through one buffer descriptor: base pointer, size and the byte offset of every layer, so that the weight
     // loads of the unrolled layers are buffer_load(rsrc, lane * 16, scalar offset) without any per-load vector address arithmetic
     const int *Ws_base;

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "gnn_common.h"
@@ -25,9 +26,10 @@ struct FusedPlan {
     int nt[MAXL] = {0, 0, 0};       // tiles of each layer's output
     int kk[MAXL] = {0, 0, 0};       // K-steps of each layer
     size_t w_off[MAXL] = {0, 0, 0}, b_off[MAXL] = {0, 0, 0}, bn_off = 0, total = 0;
-    // split arithmetic (impl 2): K = 16 chunks per layer and the dword offsets of the bf16-piece images
+    // split arithmetic (impl 2): K = 16 chunks per layer and the dword offsets of the piece images, bf16 x 3 (s_off) and fp16 x 2 (h_off),
+    // one after the other in one buffer
     int chunks[MAXL] = {0, 0, 0};
-    size_t s_off[MAXL] = {0, 0, 0}, s_total = 0;
+    size_t s_off[MAXL] = {0, 0, 0}, h_off[MAXL] = {0, 0, 0}, s_total = 0;
 };
 
 constexpr int GNN_FUSED_VARIANT_DEFAULT = 1;      // bit 0: raised wave priority during the gather (measured: -1 %)
@@ -84,6 +86,10 @@ bool make_plan(const gnn_mlp *m, int nlc, FusedPlan &p)
         p.s_off[l] = soff;
         soff += (size_t)(p.chunks[l] + (l == 0 ? S_SLACK : 0)) * p.nt[l] * 3 * 256;
     }
+    for (int l = 0; l < p.layers; ++l) {
+        p.h_off[l] = soff;
+        soff += (size_t)(p.chunks[l] + (l == 0 ? S_SLACK : 0)) * p.nt[l] * 2 * 256;
+    }
     p.s_total = soff;
     return true;
 }
@@ -139,6 +145,28 @@ bool gnn_fused_pair_selected(const gnn_loop *l)
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+// fp16 x 2 pieces (piece format 2, gnn_fused_kernel.h): the exponent e of a layer's weight scale 2^e puts max |W| 2^e into [2^14, 2^15) - the
+// largest scaled weight stays a factor 2 below the fp16 maximum 65504, the smallest normal fp16 piece (2^-14) sits 2^28 - 2^29 below the
+// largest weight.  A zero layer keeps e = 0.
+extern "C" int gnn_split_f16_exponent(float max_abs)
+{
+    if (!(max_abs > 0.0f) || !std::isfinite(max_abs)) return 0;
+    int e2 = 0;
+    (void)std::frexp(max_abs, &e2);          // max_abs = f 2^e2, f in [0.5, 1): max_abs 2^(15 - e2) in [2^14, 2^15)
+    return std::min(60, std::max(-60, 15 - e2));      // (bounded: the bias times 2^(e + GNN_F16_EX) stays far inside the fp32 range)
+}
+// pieces of n values at scale 2^e, round-to-nearest-even: p0 = fp16(v 2^e), p1 = fp16(v 2^e - p0) (the difference is exact in fp32)
+extern "C" void gnn_split_f16(const float *v, int n, int e, uint16_t *p0, uint16_t *p1)
+{
+    for (int i = 0; i < n; ++i) {
+        const float s = std::ldexp(v[i], e);
+        const _Float16 h0 = (_Float16)s;
+        const _Float16 h1 = (_Float16)(s - (float)h0);
+        memcpy(p0 + i, &h0, 2);
+        memcpy(p1 + i, &h1, 2);
+    }
+}
+
 int gnn_fused_pack(gnn_mlp *m, int nlc)
 {
     FusedPlan p;
@@ -173,6 +201,7 @@ int gnn_fused_pack(gnn_mlp *m, int nlc)
             fold = (float)((in_folded ? SCALE / LOG2E : 1.0) * (out_folded ? LOG2E : 1.0));
         }
         uint32_t *sp = simg.data() + p.s_off[l];
+        std::vector<float> wf((size_t)p.chunks[l] * nt * 64 * 8);      // the folded weights in image order
         for (int c = 0; c < p.chunks[l]; ++c)
             for (int jt = 0; jt < nt; ++jt)
                 for (int lane = 0; lane < 64; ++lane)
@@ -183,6 +212,7 @@ int gnn_fused_pack(gnn_mlp *m, int nlc)
                         const int j = 32 * jt + (lane & 31);
                         float v = (k < n_in && j < n_out) ? W[(size_t)k * n_out + j] : 0.0f;
                         v *= fold;
+                        wf[(((size_t)c * nt + jt) * 64 + lane) * 8 + i] = v;
                         for (int pc = 0; pc < 3; ++pc) {          // truncation split: v == p0 + p1 + p2 exactly
                             uint32_t bits;
                             memcpy(&bits, &v, 4);
@@ -193,6 +223,22 @@ int gnn_fused_pack(gnn_mlp *m, int nlc)
                             uint32_t &d = sp[((((size_t)c * nt + jt) * 3 + pc) * 64 + lane) * 4 + i / 2];
                             d |= (i & 1) ? hi : (hi >> 16);
                         }
+                    }
+        // fp16 x 2 image of the same (folded) weights in the same order: [chunk][out tile][piece][lane][8 fp16], at the layer's scale 2^e
+        float mw = 0.0f;
+        for (float v : wf) mw = std::max(mw, std::fabs(v));
+        const int e = gnn_split_f16_exponent(mw);
+        m->split_exp[l] = e;
+        std::vector<uint16_t> h0(wf.size()), h1(wf.size());
+        gnn_split_f16(wf.data(), (int)wf.size(), e, h0.data(), h1.data());
+        uint16_t *hp = reinterpret_cast<uint16_t *>(simg.data() + p.h_off[l]);
+        for (int c = 0; c < p.chunks[l]; ++c)
+            for (int jt = 0; jt < nt; ++jt)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int i = 0; i < 8; ++i) {
+                        const size_t src = (((size_t)c * nt + jt) * 64 + lane) * 8 + i;
+                        hp[((((size_t)c * nt + jt) * 2 + 0) * 64 + lane) * 8 + i] = h0[src];
+                        hp[((((size_t)c * nt + jt) * 2 + 1) * 64 + lane) * 8 + i] = h1[src];
                     }
     }
     if (m->has_bn) {
@@ -300,7 +346,14 @@ static int fused_args(gnn_loop *l, int k, bool split, FusedPlan &p, GnnFusedArgs
     a.chunks0 = p.chunks[0];
     a.Ws_base = m->packed_split;
     a.ws_bytes = (int)(p.s_total * sizeof(uint32_t));
-    for (int i = 0; i < p.layers; ++i) a.ws_off[i] = (int)(p.s_off[i] * sizeof(uint32_t));
+    // piece format (gnn_loop_set_pieces): the image of the format, and in format 2 the scales of every layer's accumulator, 2^(e_w + e_x)
+    a.pieces = l->pieces == 2 ? 2 : 3;
+    for (int i = 0; i < p.layers; ++i) {
+        a.ws_off[i] = (int)((a.pieces == 2 ? p.h_off[i] : p.s_off[i]) * sizeof(uint32_t));
+        const int e = a.pieces == 2 ? m->split_exp[i] + GNN_F16_EX : 0;
+        a.bsc[i] = std::ldexp(1.0f, e);
+        a.usc[i] = std::ldexp(1.0f, -e);
+    }
     a.variant = GNN_FUSED_VARIANT_DEFAULT;
     a.bn_scale = m->has_bn ? m->packed + p.bn_off : nullptr;
     a.bn_shift = m->has_bn ? m->packed + p.bn_off + 32 * p.NTL : nullptr;

@@ -213,9 +213,10 @@ __device__ __forceinline__ float act_fast(float v)
 // LDS: the three vectors were staged in LDS at kernel start (last layer of the tile loop: no global round trips per tile)
 // NOBIAS: the accumulator was started from the bias (split arithmetic, bias_tile)
 // fmax: features >= fmax are padding of the tile (never stored): groups of registers that hold only such features are skipped
+// us: scale of the accumulator undone first (NOBIAS: the fp16-piece format's 2^-(e_w + e_x), else 1)
 template <int ACT, bool BN, bool FAST = false, bool LDS = false, bool NOBIAS = false>
 __device__ __forceinline__ void tile_epilogue(f32x16 &a, const float *bias, const float *bn_scale, const float *bn_shift,
-                                              int jt, int half, int fmax = 1 << 30)
+                                              int jt, int half, int fmax = 1 << 30, float us = 1.0f)
 {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -234,7 +235,7 @@ __device__ __forceinline__ void tile_epilogue(f32x16 &a, const float *bias, cons
         if constexpr (FAST) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                float v = NOBIAS ? a[4 * q + t] : a[4 * q + t] + bb[t];
+                float v = NOBIAS ? a[4 * q + t] * us : a[4 * q + t] + bb[t];
                 v = act_fast<ACT>(v);
                 if (BN) { const float m = v * sc[t]; v = m + sh[t]; }
                 a[4 * q + t] = v;
@@ -471,6 +472,89 @@ __device__ __forceinline__ void split_pair(float v0, float v1, int &p0, int &p1,
     p2 = (int)__builtin_amdgcn_perm(__float_as_uint(br2), __float_as_uint(ar2), 0x07060302u);
 }
 
+// ---- piece format 2 (the default): fp32 operands as two fp16 pieces on v_mfma_f32_32x32x16_f16 ----
+// A value is scaled by a power of two s (exact), then cut with round-to-nearest-even: p0 = f16(v s), p1 = f16(v s - p0) (the remainder is
+// exact in fp32); p0 + p1 carries 22 - 24 significant bits, and of the four piece products the three of relative weight >= 2^-12 are
+// accumulated (p1 q0, p0 q1, p0 q0); the dropped p1 q1 is <= 2^-24 |x w|.  Weights are scaled per layer (gnn_fused_pack: max |W s| in
+// [2^14, 2^15)), activations by the fixed 2^GNN_F16_EX (keeps p1 of values down to ~1e-3 out of the fp16 subnormals); the accumulator,
+// started from the bias times the same 2^(e_w + e_x), is scaled back by 2^-(e_w + e_x) (exact) where the activation reads it.  A scaled
+// activation of magnitude >= GNN_F16_LIMIT would round to an fp16 infinity: the wave raises the range word of its flag slot, and the host
+// repeats the Loop in format 3 (run_loops).  The fp16 operand lane map is the bf16 one, so the k orders above hold unchanged.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f32x16 mfma_f16(v4i a, v4i b, f32x16 c)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// one (even, odd) element pair: scale, fp16 pieces of both into dword j of the two operands (v_pk_mul_f32, v_cvt_pk_f16_f32, 2 v_cvt_f32_f16,
+// v_pk_add_f32, v_cvt_pk_f16_f32), and the running max |scaled value| of the range guard (one v_max3_f32 with |abs| modifiers)
+__device__ __forceinline__ void split_pair_f16(float v0, float v1, int &p0, int &p1, float &mx)
+{
+    constexpr float S = (float)(1 << GNN_F16_EX);
+    const v2f s = v2f{v0, v1} * v2f{S, S};
+    mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(s.x), __builtin_fabsf(s.y)));
+    const f16x2 h0 = __builtin_convertvector(s, f16x2);
+    const v2f r = s - __builtin_convertvector(h0, v2f);
+    const f16x2 h1 = __builtin_convertvector(r, f16x2);
+    p0 = __builtin_bit_cast(int, h0);
+    p1 = __builtin_bit_cast(int, h1);
+}
+__device__ __forceinline__ void split8_f16(const float (&v)[8], v4i &p0, v4i &p1, float &mx)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int q0, q1;
+        split_pair_f16(v[2 * j], v[2 * j + 1], q0, q1, mx);
+        p0[j] = q0; p1[j] = q1;
+    }
+}
+// Range guard of a hidden layer's operand: max |accumulator| x us x 2^GNN_F16_EX bounds every scaled activation the cut will see (every
+// activation has |act(v)| <= max(|v|, 2.5): the folded SELU's negative branch stays above -2.42), so it is taken once over the accumulators
+// instead of inside the cut, by k_fused between the layers (a running maximum threaded through the pipelined cuts, or this check at the top
+// of layer_split_from_regs, raised the register peak of the headline instantiation past 256: 180 - 272 bytes of scratch).
+template <int NI>
+__device__ __forceinline__ float hidden_range(const f32x16 (&h)[NI], float us)
+{
+    float m = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NI; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(h[t][r]), __builtin_fabsf(h[t][r + 1])));
+    return m * (us * (float)(1 << GNN_F16_EX));
+}
+
+// Product terms of one chunk, smallest first, for piece format PC: weight piece PA[t] times activation piece PB[t]
+template <int PC> struct SplitTerms;
+template <> struct SplitTerms<3> {
+    static constexpr int N = 6;
+    static constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+};
+template <> struct SplitTerms<2> {
+    static constexpr int N = 3;
+    static constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
+};
+template <int PC>
+__device__ __forceinline__ f32x16 mfma_piece(v4i a, v4i b, f32x16 c)
+{
+    if constexpr (PC == 2) return mfma_f16(a, b, c);
+    else return mfma_bf16(a, b, c);
+}
+// the operand pieces of 8 consecutive elements in format PC (mx: range guard of format 2, untouched by format 3)
+template <int PC>
+__device__ __forceinline__ void split8_pc(const float (&v)[8], v4i (&p)[PC], float &mx)
+{
+    if constexpr (PC == 2) split8_f16(v, p[0], p[1], mx);
+    else split8(v, p[0], p[1], p[2]);
+}
+// a wave whose cuts met an out-of-range value raises word 3 of its flag slot (exchanged between ranks with the gate words)
+__device__ __forceinline__ void gnn_flag_raise_range(int *flag_rank_base, float mx)
+{
+    if (__any(mx >= GNN_F16_LIMIT) && (threadIdx.x & 63) == 0) {
+        int *w = flag_rank_base + (blockIdx.x & (GNN_FLAG_SLOTS - 1)) * GNN_FLAG_STRIDE + 3;
+        if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(w, 1);
+    }
+}
+
 // the six piece products of one K = 16 chunk on T output tiles; consecutive MFMAs go to different accumulators
 template <int T>
 __device__ __forceinline__ void mfma_split(const v4i (&w)[T][3], v4i b0, v4i b1, v4i b2, f32x16 *acc)
@@ -492,17 +576,18 @@ __device__ __forceinline__ void mfma_split(const v4i (&w)[T][3], v4i b0, v4i b1,
 // layer 0: input = LDS tile.  xr = X + (lane & 31) * KP + 8 * (lane >> 5); wl = split image of the layer + 4 * lane.
 // Two register sets: the weights / tile values of chunk c + 1 are requested before the MFMAs of chunk c.  The image has
 // two zero chunks of slack and the LDS allocation 128 B, so the look-ahead never leaves them; it is never consumed.
-template <int NO, bool AL16>
+template <int NO, bool AL16, int PC = 3>
 __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rsrc_t wrs, int voff, int soff, int n_chunks, f32x16 (&acc)[NO],
-                                             const float *bias_lds, int half)
+                                             const float *bias_lds, int half, float &mx)
 {
-    v4i wa[NO][3], wb[NO][3];
+    using TM = SplitTerms<PC>;
+    v4i wa[NO][PC], wb[NO][PC];
     float xa[8], xb[8];
-    v4i pa[3], pb[3];                                  // operand pieces of the chunk whose weights sit in wa / wb
+    v4i pa[PC], pb[PC];                                // operand pieces of the chunk whose weights sit in wa / wb
     WStream ws(soff);                                  // chunks are requested in ascending order: 0, 1, 2, ...
 #define GNN_S0_LOAD(W, XV, C)                                                                       \
     _Pragma("unroll") for (int jt = 0; jt < NO; ++jt)                                               \
-        _Pragma("unroll") for (int pc = 0; pc < 3; ++pc)                                            \
+        _Pragma("unroll") for (int pc = 0; pc < PC; ++pc)                                           \
             W[jt][pc] = ws.next(wrs, voff);                                                         \
     if constexpr (AL16) {                                                                           \
         const v4f lo_ = *reinterpret_cast<const v4f *>(xr + 16 * (C)), hi_ = *reinterpret_cast<const v4f *>(xr + 16 * (C) + 4);   \
@@ -511,36 +596,55 @@ __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rs
         _Pragma("unroll") for (int i = 0; i < 8; ++i) XV[i] = xr[16 * (C) + i];                     \
     }                                                                                               \
     __builtin_amdgcn_sched_barrier(0);
-    // the six piece products of the chunk in W / P; after the first NO MFMAs the pieces of the NEXT chunk (values XN, already
-    // in registers) are cut in the shadow of the matrix pipe, one element pair per following MFMA
-#define GNN_S0_MFMA(W, P, XN, PN, Z)                                                                \
+    // the piece products of the chunk in W / P; after the first NO MFMAs the pieces of the NEXT chunk (values XN, already in registers)
+    // are cut in the shadow of the matrix pipe: format 3 one element pair per following MFMA, format 2 (2 NO MFMAs left) spread evenly
+#define GNN_S0_MFMA(W, P, XN, PN, Z, LIVE)                                                          \
     {                                                                                               \
-        constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};                       \
-        _Pragma("unroll") for (int term = 0; term < 6; ++term)                                      \
+        float mn_ = 0.0f;                                                                           \
+        _Pragma("unroll") for (int term = 0; term < TM::N; ++term)                                  \
             _Pragma("unroll") for (int t = 0; t < NO; ++t) {                                        \
-                acc[t] = mfma_bf16(W[t][PA[term]], P[PB[term]], (Z && term == 0) ? bias_tile(bias_lds, t, half) : acc[t]);       \
+                acc[t] = mfma_piece<PC>(W[t][TM::PA[term]], P[TM::PB[term]], (Z && term == 0) ? bias_tile(bias_lds, t, half) : acc[t]);   \
                 const int m = term * NO + t;                                                        \
-                if (m >= NO && m < NO + 4) {                                                        \
-                    const int j = m - NO;                                                           \
-                    int q0, q1, q2;                                                                 \
-                    split_pair(XN[2 * j], XN[2 * j + 1], q0, q1, q2);                               \
-                    PN[0][j] = q0; PN[1][j] = q1; PN[2][j] = q2;                                    \
+                constexpr int SL = TM::N * NO - NO;                                                 \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                     \
+                    const bool due = PC == 3 ? (m == NO + j) : (m >= NO && (m - NO) == j * SL / 4); \
+                    if (due) {                                                                      \
+                        if constexpr (PC == 3) {                                                    \
+                            int q0, q1, q2;                                                         \
+                            split_pair(XN[2 * j], XN[2 * j + 1], q0, q1, q2);                       \
+                            PN[0][j] = q0; PN[1][j] = q1; PN[PC - 1][j] = q2;                       \
+                        } else {                                                                    \
+                            int q0, q1;                                                             \
+                            split_pair_f16(XN[2 * j], XN[2 * j + 1], q0, q1, mn_);                  \
+                            PN[0][j] = q0; PN[1][j] = q1;                                           \
+                        }                                                                           \
+                    }                                                                               \
                 }                                                                                   \
                 __builtin_amdgcn_sched_barrier(0);                                                  \
             }                                                                                       \
+        if (PC == 2 && (LIVE)) mx = __builtin_fmaxf(mx, mn_);   /* (the look-ahead past the last chunk is not guarded) */   \
     }
     GNN_S0_LOAD(wa, xa, 0)
-    split8(xa, pa[0], pa[1], pa[2]);
+    split8_pc<PC>(xa, pa, mx);
     GNN_S0_LOAD(wb, xb, 1)
-    GNN_S0_MFMA(wa, pa, xb, pb, true)                  // chunk 0 starts the accumulators from the layer's bias
+    GNN_S0_MFMA(wa, pa, xb, pb, true, 1 < n_chunks)    // chunk 0 starts the accumulators from the layer's bias
     for (int c = 1; c < n_chunks; c += 2) {
         GNN_S0_LOAD(wa, xa, c + 1)
-        GNN_S0_MFMA(wb, pb, xa, pa, false)
+        GNN_S0_MFMA(wb, pb, xa, pa, false, c + 1 < n_chunks)
         GNN_S0_LOAD(wb, xb, c + 2)
-        if (c + 1 < n_chunks) GNN_S0_MFMA(wa, pa, xb, pb, false)
+        if (c + 1 < n_chunks) GNN_S0_MFMA(wa, pa, xb, pb, false, c + 2 < n_chunks)
     }
 #undef GNN_S0_LOAD
 #undef GNN_S0_MFMA
+}
+
+// format 3 without the range guard (the training kernels of gnn_train.hip)
+template <int NO, bool AL16>
+__device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rsrc_t wrs, int voff, int soff, int n_chunks, f32x16 (&acc)[NO],
+                                             const float *bias_lds, int half)
+{
+    float mx = 0.0f;
+    layer0_split<NO, AL16, 3>(xr, wrs, voff, soff, n_chunks, acc, bias_lds, half, mx);
 }
 
 // hidden / last layer: input = accumulator tiles of the previous layer; its epilogue (bias + activation; bias_prev points to the
@@ -549,20 +653,22 @@ __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rs
 // an MFMA runs while the matrix pipe executes it): while the 6 NO MFMAs of chunk c are issued, the 8 elements of chunk
 // c + 2 get bias + activation (E) and the elements of chunk c + 1 are cut into bf16 pieces (S), one task per few MFMAs.
 // Units of (chunk, pair of output tiles), fully unrolled, weights requested DEPTH units ahead.
-template <int NI, int NO, int ACT>
+// PC: piece format (3 = bf16 x 3, 2 = fp16 x 2: hin holds the previous layer's accumulators times 2^(e_w + e_x); us = 2^-(e_w + e_x)).
+template <int NI, int NO, int ACT, int PC = 3>
 __device__ __forceinline__ void layer_split_from_regs(f32x16 (&hin)[NI], const float *bias_lds, int half, f32x16 (&acc)[NO],
-                                                      __amdgpu_buffer_rsrc_t wrs, int voff, int soff)
+                                                      __amdgpu_buffer_rsrc_t wrs, int voff, int soff, float us, float &mx)
 {
+    using TM = SplitTerms<PC>;
     constexpr int TPU = NO >= 2 ? 2 : 1, UPC = NO / TPU, CH = 2 * NI, U = CH * UPC;
     constexpr int DEPTH = (NI + NO >= 8) ? 1 : 3;       // 24 VGPRs per unit in flight next to 16 (NI + NO) of activations (128 -> 128: depth 2 spills ~40 VGPRs and is slower)
-    constexpr int NM = 6 * NO, NTASK = 12;              // MFMAs per chunk; VALU tasks per chunk: 8 E elements, then 4 S pairs (late:
+    constexpr int NM = TM::N * NO, NTASK = 12;              // MFMAs per chunk; VALU tasks per chunk: 8 E elements, then 4 S pairs (late:
                                                         // the pieces of chunk c + 1 become live when b2 / b1 of chunk c are dead)
-    v4i w[U][TPU][3];
-    int bp[2][3][4];                                    // operand pieces of chunk c (bp[c & 1]) and c + 1
+    v4i w[U][TPU][PC];
+    int bp[2][PC][4];                                    // operand pieces of chunk c (bp[c & 1]) and c + 1
     WStream ws(soff);                                   // units are requested in ascending order = image order
 #define GNN_S1_LOAD(UU)                                                                             \
     _Pragma("unroll") for (int t = 0; t < TPU; ++t)                                                 \
-        _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) w[UU][t][pc] = ws.next(wrs, voff);
+        _Pragma("unroll") for (int pc = 0; pc < PC; ++pc) w[UU][t][pc] = ws.next(wrs, voff);
     // (the previous layer's accumulators already contain its bias: bias_tile)
 #define GNN_S1_H(C, I) hin[(C) >> 1][8 * ((C) & 1) + (I)]
     // SELU between dense layers, folded (gnn_fused_pack scales the split image to match): the accumulator holds v' = log2(e) v, the
@@ -571,10 +677,12 @@ __device__ __forceinline__ void layer_split_from_regs(f32x16 (&hin)[NI], const f
 #define GNN_S1_E(C, I)                                                                              \
     if constexpr (ACT == GNN_ACT_SELU) {                                                            \
         constexpr float AL2_ = 1.6732632423543772f * 1.44269504088896341f;                          \
-        const float v_ = GNN_S1_H(C, I);                                                            \
+        const float v_ = PC == 2 ? GNN_S1_H(C, I) * us : GNN_S1_H(C, I);                            \
         GNN_S1_H(C, I) = v_ > 0.0f ? v_ : __builtin_fmaf(__builtin_amdgcn_exp2f(v_), AL2_, -AL2_);  \
-    } else GNN_S1_H(C, I) = act_fast<ACT>(GNN_S1_H(C, I));
-#define GNN_S1_S(C, J, DST) split_pair(GNN_S1_H(C, 2 * (J)), GNN_S1_H(C, 2 * (J) + 1), DST[0][J], DST[1][J], DST[2][J]);
+    } else GNN_S1_H(C, I) = act_fast<ACT>(PC == 2 ? GNN_S1_H(C, I) * us : GNN_S1_H(C, I));
+#define GNN_S1_S(C, J, DST)                                                                         \
+    if constexpr (PC == 2) { float mz_ = 0.0f; split_pair_f16(GNN_S1_H(C, 2 * (J)), GNN_S1_H(C, 2 * (J) + 1), DST[0][J], DST[1][J], mz_); }   \
+    else split_pair(GNN_S1_H(C, 2 * (J)), GNN_S1_H(C, 2 * (J) + 1), DST[0][J], DST[1][J], DST[PC - 1][J]);
     // (Halving the tasks - one half per MFMA gap instead of a whole task after every second MFMA - was measured: 5 % slower.)
 #pragma unroll
     for (int u = 0; u < DEPTH && u < U; ++u) { GNN_S1_LOAD(u) }
@@ -594,18 +702,17 @@ __device__ __forceinline__ void layer_split_from_regs(f32x16 (&hin)[NI], const f
             const int u = c * UPC + up;
             if (u + DEPTH < U) { GNN_S1_LOAD(u + DEPTH) }
             // term order as mfma_split: smallest products first
-            constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
-            for (int term = 0; term < 6; ++term) {
+            for (int term = 0; term < TM::N; ++term) {
 #pragma unroll
                 for (int t = 0; t < TPU; ++t) {
-                    const int *bq = bp[c & 1][PB[term]];
+                    const int *bq = bp[c & 1][TM::PB[term]];
                     // the first MFMA of an accumulator takes the layer's bias as C (no zeroed register tile, no bias add later)
-                    acc[up * TPU + t] = mfma_bf16(w[u][t][PA[term]], v4i{bq[0], bq[1], bq[2], bq[3]},
+                    acc[up * TPU + t] = mfma_piece<PC>(w[u][t][TM::PA[term]], v4i{bq[0], bq[1], bq[2], bq[3]},
                                                   (c == 0 && term == 0) ? bias_tile(bias_lds, up * TPU + t, half) : acc[up * TPU + t]);
                     // VALU tasks due after MFMA number m of the chunk: [(m - 1) NTASK / NM, m NTASK / NM).  (Grouping the tasks of 2 or 4
                     // consecutive MFMAs behind the last of them was measured in round 4: no effect, DESIGN.md appendix.)
-                    const int m = (up * 6 + term) * TPU + t + 1;
+                    const int m = (up * TM::N + term) * TPU + t + 1;
                     const int k0 = (m - 1) * NTASK / NM, k1 = m * NTASK / NM;
 #pragma unroll
                     for (int k = 0; k < NTASK; ++k) {
@@ -623,6 +730,14 @@ __device__ __forceinline__ void layer_split_from_regs(f32x16 (&hin)[NI], const f
 #undef GNN_S1_E
 #undef GNN_S1_S
 #undef GNN_S1_H
+}
+
+template <int NI, int NO, int ACT>
+__device__ __forceinline__ void layer_split_from_regs(f32x16 (&hin)[NI], const float *bias_lds, int half, f32x16 (&acc)[NO],
+                                                      __amdgpu_buffer_rsrc_t wrs, int voff, int soff)
+{
+    float mx = 0.0f;
+    layer_split_from_regs<NI, NO, ACT, 3>(hin, bias_lds, half, acc, wrs, voff, soff, 1.0f, mx);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1221,7 +1336,8 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N])
 // are not compiled in at all, which frees registers and scalar registers for the tuned ones.
 // GIVEN (with FULL): the aggregated states come from a.agg_in (feature-sliced exchange) - row copies instead of the gather.  A
 // template parameter, not a branch: a wave-uniform branch in the tile loop of the full-tile kernel cost 3 % (0.700 -> 0.721 ms).
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false>
+// PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedArgs a0)
 {
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
@@ -1256,12 +1372,12 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     float *ep = lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32 + GNN_FUSED_WAVES * 36;
     for (int t = threadIdx.x; t < 3 * 32 * NTL; t += blockDim.x) {
         const int which = t / (32 * NTL), f = t - which * 32 * NTL;
-        ep[t] = which == 0 ? a.bias[LAYERS - 1][f] : (a.bn_scale ? (which == 1 ? a.bn_scale[f] : a.bn_shift[f]) : 0.0f);
+        ep[t] = which == 0 ? a.bias[LAYERS - 1][f] * (SPLIT ? a.bsc[LAYERS - 1] : 1.0f) : (a.bn_scale ? (which == 1 ? a.bn_scale[f] : a.bn_shift[f]) : 0.0f);
     }
     float *hb = ep + 3 * 32 * NTL;                    // hidden-layer biases (split path): [LAYERS - 1][32 NT]
-    if constexpr (SPLIT && LAYERS > 1)
+    if constexpr (SPLIT && LAYERS > 1)                // (x 2^(e_w + e_x) of the layer in the fp16-piece format: bsc)
         for (int t = threadIdx.x; t < (LAYERS - 1) * 32 * NT; t += blockDim.x)
-            hb[t] = a.bias[t / (32 * NT)][t % (32 * NT)] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f);      // folded SELU: see GNN_S1_E
+            hb[t] = a.bias[t / (32 * NT)][t % (32 * NT)] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f) * a.bsc[t / (32 * NT)];   // folded SELU: see GNN_S1_E
     __syncthreads();
     // Start-up spread.  All waves of the chip run the same phases on tiles of similar cost: started together they gather together
     // (HBM saturated, 3-4 us per round trip) and compute together (HBM idle).  Every wave therefore waits a different fraction of
@@ -1326,27 +1442,30 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     const int half = lane >> 5;
     const float *xb = X + (lane & 31) * KP + half;
     f32x16 out[NTL];
+    float mx = 0.0f;                                  // range guard of the fp16-piece format: max |scaled operand| of this tile's cuts
     if constexpr (SPLIT) {
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(a.Ws_base), 0, a.ws_bytes, 0x00020000);
         const int wv = lane * 16;
         const float *xr = X + (lane & 31) * KP + 8 * half;
         if constexpr (LAYERS == 1) {
-            layer0_split<NTL, false>(xr, wrs, wv, a.ws_off[0], a.chunks0, out, ep, half);
+            layer0_split<NTL, false, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, out, ep, half, mx);
         } else {
             f32x16 h1[NT];
-            if constexpr (FULL) layer0_split<NT, true>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half);
+            if constexpr (FULL) layer0_split<NT, true, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);
             else {
-                if (Ds == 64) layer0_split<NT, true>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half);    // 16-byte aligned tile layout
-                else layer0_split<NT, false>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half);
+                if (Ds == 64) layer0_split<NT, true, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);    // 16-byte aligned tile layout
+                else layer0_split<NT, false, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);
             }
             GNN_STAMP(3);
             GNN_STAMP(4);
+            if constexpr (PC == 2) { asm volatile("" : "+v"(mx)); mx = __builtin_fmaxf(mx, hidden_range<NT>(h1, a.usc[0])); asm volatile("" : "+v"(mx)); }
             if constexpr (LAYERS == 2) {
-                layer_split_from_regs<NT, NTL, ACT>(h1, ep, half, out, wrs, wv, a.ws_off[1]);
+                layer_split_from_regs<NT, NTL, ACT, PC>(h1, ep, half, out, wrs, wv, a.ws_off[1], a.usc[0], mx);
             } else {
                 f32x16 h2[NT];
-                layer_split_from_regs<NT, NT, ACT>(h1, hb + 32 * NT, half, h2, wrs, wv, a.ws_off[1]);
-                layer_split_from_regs<NT, NTL, ACT>(h2, ep, half, out, wrs, wv, a.ws_off[2]);
+                layer_split_from_regs<NT, NT, ACT, PC>(h1, hb + 32 * NT, half, h2, wrs, wv, a.ws_off[1], a.usc[0], mx);
+                if constexpr (PC == 2) { asm volatile("" : "+v"(mx)); mx = __builtin_fmaxf(mx, hidden_range<NT>(h2, a.usc[1])); asm volatile("" : "+v"(mx)); }
+                layer_split_from_regs<NT, NTL, ACT, PC>(h2, ep, half, out, wrs, wv, a.ws_off[2], a.usc[1], mx);
             }
         }
     } else if constexpr (LAYERS == 1) {
@@ -1384,6 +1503,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     int src_next = 0;
     float w_next = 0.0f;
     if (FULL || Ds == 64) tile_first_ids(a, ip_next, lane, src_next, w_next);
+    if constexpr (SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
     GnnFlagPeek peek = {0, 0, 0};                             // the gate words of this wave's slot: on their way across the epilogue arithmetic
     if (SPLIT && NTL == 2 && lane == 0) peek = gnn_flag_peek(a.flag_out);
     bool finished = false;
@@ -1391,8 +1511,8 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         if (fast64) {                                         // registers -> norms, LDS (16-byte pieces), row stores
 #pragma unroll
             for (int jt = 0; jt < NTL; ++jt) {
-                if (a.bn_scale) tile_epilogue<ACT, true, true, true, true>(out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half);
-                else tile_epilogue<ACT, false, true, true, true>(out[jt], ep, nullptr, nullptr, jt, half);
+                if (a.bn_scale) tile_epilogue<ACT, true, true, true, true>(out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, a.usc[LAYERS - 1]);
+                else tile_epilogue<ACT, false, true, true, true>(out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, a.usc[LAYERS - 1]);
             }
             GNN_STAMP(6);
             if (nvalid == 32) finish_fast64_aligned(a, X, out, i0, lane, KP, c_aggs, peek);
@@ -1403,8 +1523,9 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     if (!(FULL && SPLIT && NTL == 2) && !finished) {
 #pragma unroll
         for (int jt = 0; jt < NTL; ++jt) {
-            if (a.bn_scale) tile_epilogue<ACT, true, SPLIT, true, SPLIT>(out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half);
-            else tile_epilogue<ACT, false, SPLIT, true, SPLIT>(out[jt], ep, nullptr, nullptr, jt, half);
+            const float us = SPLIT ? a.usc[LAYERS - 1] : 1.0f;
+            if (a.bn_scale) tile_epilogue<ACT, true, SPLIT, true, SPLIT>(out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, us);
+            else tile_epilogue<ACT, false, SPLIT, true, SPLIT>(out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, us);
             float *x = X + (lane & 31) * KP + c_aggs;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1431,18 +1552,25 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
   }
 }
 
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false>
-inline void launch_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false, int PC = 3>
+inline void launch_one_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     static bool raised[64] = {false};   // dynamic LDS above 64 KiB has to be requested once per kernel AND device
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !raised[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (dev >= 0 && dev < 64) raised[dev] = true;
     }
-    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
+    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
+}
+// the split arithmetic in the piece format of the launch (a.pieces); the exact path has one
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false>
+inline void launch_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+{
+    if (SPLIT && a.pieces == 2) launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, 2>(a, grid, lds_bytes, st);
+    else launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, 3>(a, grid, lds_bytes, st);
 }
 
 // a.full_tiles: the host asks for the full-tile specialisation (state width 64); it exists for NTL == 2

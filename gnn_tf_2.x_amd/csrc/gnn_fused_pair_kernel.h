@@ -1,6 +1,6 @@
 // Fused iteration kernel, WAVE-PAIR form (round 5; device code).  Included by gnn_fused_p{2,3}.hip.
 //
-// Same contract as k_fused<.., SPLIT = true, FULL = true> (gnn_fused_kernel.h): one launch = one iteration of GNN.Loop (reference
+// Same contract as k_fused<.., SPLIT = true, FULL = true, .., PC> (gnn_fused_kernel.h): one launch = one iteration of GNN.Loop (reference
 // GNN/GNN.py:223-242 + :202-220) in the split arithmetic of the default path (fp32 operands as three exact bf16 pieces on
 // v_mfma_f32_32x32x16_bf16), state width 64, 128-wide hidden layers, identical results bit for bit.  What changes is who does what:
 //
@@ -149,21 +149,22 @@ __device__ __forceinline__ float pair_act(float v)
 }
 
 // One dense layer of a wave's feature half.  B operand: the pieces of all 32 nodes in P (CH chunks); A operand: the wave's T tiles of
-// the layer, 3 T fragments per chunk, requested DEPTH chunks ahead; accumulators start from the bias.  Fully unrolled.
-template <int CH, int T, int STRIDE, int DEPTH>
+// the layer, PC T fragments per chunk, requested DEPTH chunks ahead; accumulators start from the bias.  Fully unrolled.
+template <int CH, int T, int STRIDE, int DEPTH, int PC>
 __device__ __forceinline__ void pair_layer(const v4i *P, int lane, __amdgpu_buffer_rsrc_t wrs, int voff, int soff, f32x16 (&acc)[T],
                                            const float *bias_lds, int jt0, int half)
 {
-    v4i w[CH][T][3];
-    v4i b[CH][3];
-    WStreamHalf<3 * T, STRIDE> ws(soff);
+    using TM = SplitTerms<PC>;
+    v4i w[CH][T][PC];
+    v4i b[CH][PC];
+    WStreamHalf<PC * T, STRIDE> ws(soff);
 #define GNN_PAIR_LOADW(C)                                                                           \
     {                                                                                               \
         _Pragma("unroll") for (int t = 0; t < T; ++t)                                               \
-            _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) w[C][t][pc] = ws.load(3 * t + pc, wrs, voff);   \
+            _Pragma("unroll") for (int pc = 0; pc < PC; ++pc) w[C][t][pc] = ws.load(PC * t + pc, wrs, voff);   \
         ws.advance();                                                                               \
     }
-#define GNN_PAIR_LOADB(C) _Pragma("unroll") for (int pc = 0; pc < 3; ++pc) b[C][pc] = P[((C) * 3 + pc) * 64 + lane];
+#define GNN_PAIR_LOADB(C) _Pragma("unroll") for (int pc = 0; pc < PC; ++pc) b[C][pc] = P[((C) * PC + pc) * 64 + lane];
 #pragma unroll
     for (int c = 0; c < DEPTH && c < CH; ++c) GNN_PAIR_LOADW(c)
     GNN_PAIR_LOADB(0)
@@ -173,12 +174,11 @@ __device__ __forceinline__ void pair_layer(const v4i *P, int lane, __amdgpu_buff
         if (c + DEPTH < CH) GNN_PAIR_LOADW(c + DEPTH)
         if (c + 1 < CH) { GNN_PAIR_LOADB(c + 1) }
         __builtin_amdgcn_sched_barrier(0);
-        constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};      // term order as mfma_split: smallest products first
 #pragma unroll
-        for (int term = 0; term < 6; ++term)
+        for (int term = 0; term < TM::N; ++term)      // term order as k_fused: smallest products first
 #pragma unroll
             for (int t = 0; t < T; ++t)
-                acc[t] = mfma_bf16(w[c][t][PA[term]], b[c][PB[term]], (c == 0 && term == 0) ? bias_tile(bias_lds, jt0 + t, half) : acc[t]);
+                acc[t] = mfma_piece<PC>(w[c][t][TM::PA[term]], b[c][TM::PB[term]], (c == 0 && term == 0) ? bias_tile(bias_lds, jt0 + t, half) : acc[t]);
         __builtin_amdgcn_sched_barrier(0);
     }
 #undef GNN_PAIR_LOADW
@@ -186,21 +186,24 @@ __device__ __forceinline__ void pair_layer(const v4i *P, int lane, __amdgpu_buff
 }
 
 // activation + cut of a wave's T output tiles into operand pieces (registers): chunk 2 t + q of the wave's half = accumulator registers 8 q .. 8 q + 7 of tile t
-template <int T, int ACT>
-__device__ __forceinline__ void pair_cut(f32x16 (&h)[T], v4i (&pp)[2 * T][3])
+// (format 2: h holds the accumulators times 2^(e_w + e_x), us undoes it - the same arithmetic as GNN_S1_E / GNN_S1_S of k_fused)
+template <int T, int ACT, int PC>
+__device__ __forceinline__ void pair_cut(f32x16 (&h)[T], v4i (&pp)[2 * T][PC], float us, float &mx)
 {
+    if constexpr (PC == 2) mx = __builtin_fmaxf(mx, hidden_range<T>(h, us));     // (the range guard of layer_split_from_regs)
 #pragma unroll
     for (int t = 0; t < T; ++t)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             float v[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = pair_act<ACT>(h[t][8 * q + i]);
-            split8(v, pp[2 * t + q][0], pp[2 * t + q][1], pp[2 * t + q][2]);
+            for (int i = 0; i < 8; ++i) v[i] = pair_act<ACT>(PC == 2 ? h[t][8 * q + i] * us : h[t][8 * q + i]);
+            float mz = 0.0f;
+            split8_pc<PC>(v, pp[2 * t + q], mz);
         }
 }
 
-template <int LAYERS, int ACT>
+template <int LAYERS, int ACT, int PC>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFusedArgs a0)
 {
     constexpr int NT = 4, NTL = 2, CH0 = GNN_PAIR_CH0;
@@ -236,10 +239,10 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
     if (threadIdx.x < 16) words[threadIdx.x] = 0;
     for (int t = threadIdx.x; t < 3 * 32 * NTL; t += blockDim.x) {
         const int which = t / (32 * NTL), f = t - which * 32 * NTL;
-        ep[t] = which == 0 ? a.bias[LAYERS - 1][f] : (a.bn_scale ? (which == 1 ? a.bn_scale[f] : a.bn_shift[f]) : 0.0f);
+        ep[t] = which == 0 ? a.bias[LAYERS - 1][f] * a.bsc[LAYERS - 1] : (a.bn_scale ? (which == 1 ? a.bn_scale[f] : a.bn_shift[f]) : 0.0f);
     }
     for (int t = threadIdx.x; t < (LAYERS - 1) * 32 * NT; t += blockDim.x)
-        hb[t] = a.bias[t / (32 * NT)][t % (32 * NT)] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f);
+        hb[t] = a.bias[t / (32 * NT)][t % (32 * NT)] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f) * a.bsc[t / (32 * NT)];
     // zero columns of this side's rows, once: the alignment hole, the padding behind the concat (nothing in a tile's life writes them)
     {
         const int hole0 = a.NLc, holew = ca - hole0, pad0 = a.in_s - 64, padw = 16 * CH0 - 64 - pad0;
@@ -321,6 +324,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     GNN_PSTAMP(1);
     // ---- layer-0 operand: this side's rows cut into pieces, chunks of parity cp per lane ----
+    float mx = 0.0f;                                              // range guard of the fp16-piece format (k_fused)
     {
         const int pl = 16 * side + nl + 32 * ch;                  // MFMA lane (node of the tile, k-half) this lane produces the pieces of
 #pragma unroll
@@ -336,12 +340,13 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
                 const v4f lo = *reinterpret_cast<const v4f *>(xr + cq), hi = *reinterpret_cast<const v4f *>(xr + cq + 4);
                 v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
             }
-            v4i p0, p1, p2;
-            split8(v, p0, p1, p2);
+            v4i pq[PC];
+            float mc = mx;
+            split8_pc<PC>(v, pq, mc);
             if (c < CH0) {
-                P[(c * 3 + 0) * 64 + pl] = p0;
-                P[(c * 3 + 1) * 64 + pl] = p1;
-                P[(c * 3 + 2) * 64 + pl] = p2;
+                mx = mc;
+#pragma unroll
+                for (int pc = 0; pc < PC; ++pc) P[(c * PC + pc) * 64 + pl] = pq[pc];
             }
         }
     }
@@ -353,35 +358,35 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
     f32x16 out[1];
     {
         f32x16 h1[2];
-        pair_layer<CH0, 2, NT * 3072, 3>(P, lane, wrs, wv, a.ws_off[0] + side * 6144, h1, hb, 2 * side, half);
+        pair_layer<CH0, 2, NT * PC * 1024, 3, PC>(P, lane, wrs, wv, a.ws_off[0] + side * 2 * PC * 1024, h1, hb, 2 * side, half);
         GNN_PSTAMP(4);
-        v4i pp[4][3];
-        pair_cut<2, ACT>(h1, pp);
+        v4i pp[4][PC];
+        pair_cut<2, ACT, PC>(h1, pp, a.usc[0], mx);
         GNN_PSTAMP(5);
         pair_meet(words, wave, partner, phase, lane);             // (2) both waves have read the layer-0 operand
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) P[((4 * side + c) * 3 + pc) * 64 + lane] = pp[c][pc];
+            for (int pc = 0; pc < PC; ++pc) P[((4 * side + c) * PC + pc) * 64 + lane] = pp[c][pc];
     }
     pair_meet(words, wave, partner, phase, lane);                 // (3) hidden activations of layer 0 complete
     GNN_PSTAMP(6);
     if constexpr (LAYERS == 3) {
         f32x16 h2[2];
-        pair_layer<2 * NT, 2, NT * 3072, 3>(P, lane, wrs, wv, a.ws_off[1] + side * 6144, h2, hb + 32 * NT, 2 * side, half);
+        pair_layer<2 * NT, 2, NT * PC * 1024, 3, PC>(P, lane, wrs, wv, a.ws_off[1] + side * 2 * PC * 1024, h2, hb + 32 * NT, 2 * side, half);
         GNN_PSTAMP(7);
-        v4i pp[4][3];
-        pair_cut<2, ACT>(h2, pp);
+        v4i pp[4][PC];
+        pair_cut<2, ACT, PC>(h2, pp, a.usc[1], mx);
         GNN_PSTAMP(8);
         pair_meet(words, wave, partner, phase, lane);             // (4)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) P[((4 * side + c) * 3 + pc) * 64 + lane] = pp[c][pc];
+            for (int pc = 0; pc < PC; ++pc) P[((4 * side + c) * PC + pc) * 64 + lane] = pp[c][pc];
         pair_meet(words, wave, partner, phase, lane);             // (5)
         GNN_PSTAMP(9);
     }
-    pair_layer<2 * NT, 1, NTL * 3072, 4>(P, lane, wrs, wv, a.ws_off[LAYERS - 1] + side * 3072, out, ep, side, half);
+    pair_layer<2 * NT, 1, NTL * PC * 1024, 4, PC>(P, lane, wrs, wv, a.ws_off[LAYERS - 1] + side * PC * 1024, out, ep, side, half);
     GNN_PSTAMP(10);
     // ---- requests behind the last weight loads (vector-memory results return in order): ticket, next tile's first ids, gate words ----
     int next2_tile = 0x3fffffff;
@@ -390,11 +395,12 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
     int src_next = 0;
     float w_next = 0.0f;
     pair_first_ids(a, ip_next, lane, src_next, w_next);
+    if constexpr (PC == 2) gnn_flag_raise_range(a.flag_out, mx);
     GnnFlagPeek peek = {0, 0, 0};
     if (lane == 0) peek = gnn_flag_peek(a.flag_out);
     // ---- last-layer epilogue of this wave's 32 features, new state into X' over the aggregated-state columns ----
-    if (a.bn_scale) tile_epilogue<ACT, true, true, true, true>(out[0], ep, ep + 32 * NTL, ep + 64 * NTL, side, half);
-    else tile_epilogue<ACT, false, true, true, true>(out[0], ep, nullptr, nullptr, side, half);
+    if (a.bn_scale) tile_epilogue<ACT, true, true, true, true>(out[0], ep, ep + 32 * NTL, ep + 64 * NTL, side, half, 1 << 30, a.usc[LAYERS - 1]);
+    else tile_epilogue<ACT, false, true, true, true>(out[0], ep, nullptr, nullptr, side, half, 1 << 30, a.usc[LAYERS - 1]);
     {
         float *xrow = X + (lane & 31) * XS + ca + 32 * side + 4 * half;
 #pragma unroll
@@ -441,17 +447,23 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
   }
 }
 
-template <int LAYERS, int ACT>
-inline void launch_pair_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+template <int LAYERS, int ACT, int PC>
+inline void launch_pair_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     static bool raised[64] = {false};
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !raised[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused_pair<LAYERS, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused_pair<LAYERS, ACT, PC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (dev >= 0 && dev < 64) raised[dev] = true;
     }
-    hipLaunchKernelGGL((k_fused_pair<LAYERS, ACT>), grid, GNN_FUSED_THREADS, lds_bytes, st, a);
+    hipLaunchKernelGGL((k_fused_pair<LAYERS, ACT, PC>), grid, GNN_FUSED_THREADS, lds_bytes, st, a);
+}
+template <int LAYERS, int ACT>
+inline void launch_pair_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+{
+    if (a.pieces == 2) launch_pair_pc<LAYERS, ACT, 2>(a, grid, lds_bytes, st);
+    else launch_pair_pc<LAYERS, ACT, 3>(a, grid, lds_bytes, st);
 }
 
 template <int LAYERS>

@@ -229,10 +229,13 @@ int gnn_loss_grad(int loss_kind, int64_t n_rows, int n_out, const float *targets
  *   0 = unfused reference kernels (one kernel per TF op), bit-identical to oracle/gnn_oracle.c;
  *   1 = fused gather + MLP kernel with the dense layers on the f32 MFMA: the same k-ordered fmaf chains, bit-identical
  *       to the oracle;
- *   2 = (default) fused kernel with the dense layers on the bf16 MFMA: every fp32 operand is cut into three exact bf16
- *       pieces and the six leading piece products are accumulated in fp32 (error per product <= 3 * 2^-24, i.e. fp32
- *       rounding level), activations through v_exp_f32 / v_rcp_f32; results within fp32 rounding noise of 0 / 1
- *       (tests: 1e-5 against the float64 oracle, the tolerance of BASELINE.json), not bit for bit.
+ *   2 = (default) fused kernel with the dense layers on the 16-bit MFMA: every fp32 operand is scaled by a power of two (exact) and
+ *       cut into two fp16 pieces (round to nearest even, 22 - 24 bits together) and the three leading piece products are accumulated
+ *       in fp32 on v_mfma_f32_32x32x16_f16 (dropped term <= 2^-24 per product, i.e. fp32 rounding level); activations through
+ *       v_exp_f32 / v_rcp_f32; results within fp32 rounding noise of 0 / 1 (tests: 1e-5 against the float64 oracle, the
+ *       tolerance of BASELINE.json), not bit for bit.  A Loop in which an activation leaves the fp16 range is repeated with
+ *       three bf16 pieces per operand (six products on v_mfma_f32_32x32x16_bf16), the format of earlier releases
+ *       (gnn_loop_set_pieces, gnn_loop_range_info).
  * 1 and 2 fall back to 0 when the shapes are not covered.  *used (may be NULL) reports the choice.
  * k contract of impl 2 (reference GNN/GNN.py:202-220: `distance > threshold * norm`, reduce_any, k < max_iteration): its iteration count
  * is the bit-exact chain's.  Every body also records whether some node moved by a margin ("robust") and whether some node's test lay
@@ -244,6 +247,18 @@ int gnn_loop_set_impl(gnn_loop *l, int impl, int *used);
 /* Outcome of the certified gate: *last_run_repeated = 1 when the last gnn_loop_run / _run_group / _run_many of this loop was repeated on
  * impl 1 (its results are the exact path's), *repeats_total = how often that has happened on this handle.  Either pointer may be NULL. */
 int gnn_loop_gate_info(const gnn_loop *l, int *last_run_repeated, int *repeats_total);
+/* Piece format of impl 2, for A/B measurements and tests (not a user-facing mode): 2 = two fp16 pieces per operand (default), 3 = three
+ * bf16 pieces.  Format 2 takes |activation| < 65504 / 16 (4094): a Loop in which some body cut a larger one (or an infinity) raises a flag
+ * word beside the gate words, and gnn_loop_run repeats that Loop in format 3 before it returns; k, state and output are then THAT run's.
+ * *used (may be NULL) = the format set. */
+int gnn_loop_set_pieces(gnn_loop *l, int pieces, int *used);
+/* Outcome of the range guard: *last_run_repeated = 1 when the last run of this loop was repeated in format 3, *repeats_total = how often
+ * that has happened on this handle.  Either pointer may be NULL. */
+int gnn_loop_range_info(const gnn_loop *l, int *last_run_repeated, int *repeats_total);
+/* Host-side piece cut of format 2 (exported for tests): the weight-scale exponent e of a layer with max |W| = max_abs (max_abs 2^e in
+ * [2^14, 2^15)), and the pieces p0 = fp16(v 2^e), p1 = fp16(v 2^e - p0) of n values (round to nearest even). */
+int gnn_split_f16_exponent(float max_abs);
+void gnn_split_f16(const float *v, int n, int e, uint16_t *p0, uint16_t *p1);
 /* Small graphs (every 32-node tile resident at once: <= 8,192 owned nodes, single GPU) with a net_state no wider than 32 run
  * the whole tf.while_loop of GNN/GNN.py:271 - initial state, first condition, every body with a grid barrier in between - in
  * ONE persistent launch when impl is 1 or 2 (exact f32-MFMA arithmetic in both cases, bit-identical to the oracle).  enable = 0
