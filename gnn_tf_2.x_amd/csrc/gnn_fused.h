@@ -63,7 +63,7 @@ struct GnnFusedArgs {
     int lds_floats;
 };
 
-// control block of the persistent small-graph loop (gnn_small.hip)
+// control block of the persistent small-graph loop (gnn_small_common.h)
 struct GnnSmallCtl {
     float *state0, *state1;  // the two state replicas (ping-pong), all rows
     const float *init;       // initial state of the owned rows [n_rows, Ds] (injected / drawn state, or the node labels for D == 0)
@@ -71,7 +71,7 @@ struct GnnSmallCtl {
     int *flags;              // word [b]: barrier + gate of body b (low half arrivals, high half movers), zeroed before the launch
     int *host_result;        // pinned host memory (zero-copy): [k, status]; status: set to 1 by a workgroup whose barrier spin gave up, never cleared by the
                              // kernel (sticky), zeroed by the host before the launch
-    float *xs;               // padded exchange rows [2][tiles * 32][DP] (gnn_small.hip, small_gather_padded): the state between bodies
+    float *xs;               // padded exchange rows [2][tiles * rows per tile][DP] (gnn_small_common.h, small_gather): the state between bodies
     int DP;                  // 16 (Ds <= 16) or 32 floats per exchange row
     int rnd;                 // arcs per gather round for DP == 16 (4, or 8 when some row has more than 8 arcs)
     // 16-node-tile form (gnn_small16.hip): the Keras-layout kernels W[din][dout] (its A operands are read from them directly) and the
@@ -97,11 +97,37 @@ struct GnnSmallCtl {
     int G, ro_word;
     int ecache;              // arcs of a tile whose ids / weights may be kept in LDS (GNN_SMALL_ECACHE; 0: none)
 };
+
+// LDS layout of the persistent small-graph loop (gnn_small_common.h), in 4-byte words, for ROWS = 32 (k_small_loop) or 16 (k_small16) rows
+// per tile: the tile [ROWS][KP] at the start of the dynamic allocation, everything else at the constant offsets below from the tile's end.
+// The kernels carve their pointers from it; the host sizes the allocation with bytes(KP).
+constexpr int GNN_SMALL_ECACHE = 1024;             // arcs of a tile whose ids / weights are kept in LDS
+constexpr int GNN_SMALL16_HP = 36;                 // row stride of k_small16's hidden-activation copy (floats): 16-byte rows, (4 n + g) banks
+template <int ROWS>
+struct GnnSmallLds {
+    static_assert(ROWS == 16 || ROWS == 32, "16- or 32-node tiles");
+    static constexpr int H = 0;                                         // k_small16: hidden activations [16][GNN_SMALL16_HP]
+    static constexpr int IPT = ROWS == 16 ? 16 * GNN_SMALL16_HP : 32;   // row pointers [ROWS + 1] (+3); k_small_loop: behind 32 words of slack
+    static constexpr int EP = IPT + ROWS + 4;                           // last-layer bias, BatchNormalization scale / shift [3][32]
+    static constexpr int HB = EP + 96;                                  // biases of the hidden layers [2][32]
+    static constexpr int HW = HB + 64;                                  // net_output head: W [wf * T <= 512], then b | BN scale | BN shift [3][8]
+    static constexpr int SCR = HW + 544;                                // scratch: [ROWS][32] the tile's rows in [row][Ds] order (initial / final state),
+    static constexpr int LABELS = 32 * ROWS;                            // ... then from scr + LABELS its label rows [ROWS][32]
+    static constexpr int EC_SRC = SCR + 2 * LABELS;                     // the tile's arc ids / weights [GNN_SMALL_ECACHE] each, kept for every body
+    static constexpr int EC_W = EC_SRC + GNN_SMALL_ECACHE;
+    static constexpr int END = EC_W + GNN_SMALL_ECACHE + 4;
+    static constexpr size_t bytes(int KP) { return sizeof(float) * ((size_t)ROWS * KP + END); }
+};
+
+// Instantiated K-step counts of layer 0 (the host picks the smallest that covers the concat width, the launcher dispatches on the same list)
+template <int... V> struct GnnSteps { static constexpr int values[] = {V...}; };
+using GnnSmallKK0 = GnnSteps<8, 12, 16, 24, 32, 36, 40, 48>;     // k_small_loop: K-steps of 2 (v_mfma_f32_32x32x2_f32)
+using GnnSmall16S0 = GnnSteps<4, 8, 12, 16, 20, 24>;             // k_small16: K-steps of 4 (v_mfma_f32_16x16x4_f32)
+
+// false = no instantiation for (layers, act, kk0 / s0)
 bool gnn_small_launch(int layers, int act, int kk0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes,
                       hipStream_t st);
-
 bool gnn_small16_launch(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
-size_t gnn_small16_lds_bytes(int kp16);
 
 // one per translation unit gnn_fused_l{1,2,3}.hip; false = no instantiation for (act, nt, ntl)
 bool gnn_fused_launch_l1(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);

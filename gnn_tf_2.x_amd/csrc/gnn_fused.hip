@@ -469,7 +469,7 @@ int gnn_fused_iteration(gnn_loop *l, int k)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// persistent small-graph loop (device code: gnn_small.hip)
+// persistent small-graph loop (device code: gnn_small_common.h, gnn_small.hip, gnn_small16.hip)
 // ---------------------------------------------------------------------------------------------------------------------
 bool gnn_small_supported(const gnn_loop *l)
 {
@@ -496,9 +496,16 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
     c.init = l->D ? l->state_init : g->nodes + (size_t)g->own_off * g->NL;      // D == 0: NL == Ds (GNN.py:265)
     c.kfinal = l->kfinal_dev;
     c.host_result = l->kfinal_host;                                   // pinned, device-visible: no copy back
-    // 16-node tiles (gnn_small16.hip) while twice the workgroups are still resident at once: a body is a chain of latencies, and a
-    // 16-node tile's dense layers and activations are half as long
-    bool tile16 = g->n_rows <= 16 * 256 && a.in_s <= 96;
+    // K-steps of layer 0 the kernels keep in registers: the smallest instantiated count that covers the concat width (32-node tiles: the
+    // packed image has p.kk0 >= that many; the steps dropped are zero rows of the image)
+    int kk_small = p.kk0, s0 = 0;
+    for (int cand : GnnSmallKK0::values)
+        if (2 * cand >= a.in_s && cand <= p.kk0) { kk_small = cand; break; }
+    for (int cand : GnnSmall16S0::values)
+        if (4 * cand >= a.in_s) { s0 = cand; break; }
+    // 16-node tiles (gnn_small16.hip) while twice the workgroups are still resident at once (and an instantiation covers the concat width,
+    // in_s <= 96): a body is a chain of latencies, and a 16-node tile's dense layers and activations are half as long
+    bool tile16 = g->n_rows <= 16 * 256 && s0 > 0;
 #ifdef GNN_DIAG
     static const int tile_env = getenv("GNN_SMALL_TILE") ? atoi(getenv("GNN_SMALL_TILE")) : 0;
     if (tile_env == 32) tile16 = false;
@@ -517,10 +524,10 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
         c.xs = l->small_xs;
     }
     c.max_iter = l->max_iter;
-    c.ecache = 1024;                                                  // = GNN_SMALL_ECACHE (gnn_small.hip)
+    c.ecache = GNN_SMALL_ECACHE;
 #ifdef GNN_DIAG
-    static const int ecache_env = getenv("GNN_SMALL_ECACHE") ? atoi(getenv("GNN_SMALL_ECACHE")) : 1024;
-    c.ecache = std::min(1024, ecache_env);
+    static const int ecache_env = getenv("GNN_SMALL_ECACHE") ? atoi(getenv("GNN_SMALL_ECACHE")) : GNN_SMALL_ECACHE;
+    c.ecache = std::min(GNN_SMALL_ECACHE, ecache_env);
 #endif
     // Gate words: one per body, double-buffered by run parity at the start of the flag block.  This launch polls its own half
     // and zeroes the other half for the next run, so a run costs no memset; both halves are cleared by the host only after
@@ -561,13 +568,7 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
             }
         }
     }
-    const size_t lds = sizeof(float) * ((size_t)32 * p.KP + 32 + 36 + 160 + 544 + 2048 + 2 * 1024 + 4);    // tile, row pointers, epilogue vectors, head, scratch, arc cache (GNN_SMALL_ECACHE)
     c.rnd = g->sh->max_degree > 8 ? 8 : 4;                       // entries per gather round
-    // K-steps of layer 0 the kernel keeps in registers: the smallest instantiated count that covers the concat width (the packed
-    // image has p.kk0 >= that many; the steps dropped are zero rows of the image)
-    int kk_small = p.kk0;
-    for (int cand : {8, 12, 16, 24, 32, 36, 40, 48})
-        if (2 * cand >= a.in_s && cand <= p.kk0) { kk_small = cand; break; }
 #ifdef GNN_DIAG
     static const char *small_stamp_file = getenv("GNN_SMALL_STAMPS");
     static unsigned long long *small_stamp_buf = nullptr;
@@ -581,13 +582,13 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
     if (tile16) {
         const gnn_mlp *m = l->st;
         for (int q = 0; q < p.layers; ++q) { c.Wraw[q] = m->W[q]; c.din[q] = m->dims[q]; c.dout[q] = m->dims[q + 1]; }
-        int s0 = (a.in_s + 3) / 4;
-        s0 = (s0 + 3) / 4 * 4;                                       // instantiated: 4, 8, ..., 24 K-steps of 4
         c.KP16 = std::max((a.in_s + 3) / 4 * 4, 4 * s0);
         if (c.KP16 % 8 == 0) c.KP16 += 4;                            // rows 16 bytes apart in the banks: the B-operand column reads do not conflict
-        a.lds_floats = gnn_poison_enabled() ? (int)(gnn_small16_lds_bytes(c.KP16) / sizeof(float)) : 0;
-        launched = gnn_small16_launch(p.layers, p.act, s0, a, c, grid, gnn_small16_lds_bytes(c.KP16), l->stream);
+        const size_t lds = GnnSmallLds<16>::bytes(c.KP16);
+        a.lds_floats = gnn_poison_enabled() ? (int)(lds / sizeof(float)) : 0;
+        launched = gnn_small16_launch(p.layers, p.act, s0, a, c, grid, lds, l->stream);
     } else {
+        const size_t lds = GnnSmallLds<32>::bytes(p.KP);
         a.lds_floats = gnn_poison_enabled() ? (int)(lds / sizeof(float)) : 0;
         launched = gnn_small_launch(p.layers, p.act, kk_small, a, c, grid, lds, l->stream);
     }

@@ -469,15 +469,7 @@ inline void launch_pair_one(const GnnFusedArgs &a, unsigned grid, size_t lds_byt
 template <int LAYERS>
 inline bool launch_pair_act(int act, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    switch (act) {
-    case GNN_ACT_LINEAR: launch_pair_one<LAYERS, GNN_ACT_LINEAR>(a, grid, lds_bytes, st); return true;
-    case GNN_ACT_RELU: launch_pair_one<LAYERS, GNN_ACT_RELU>(a, grid, lds_bytes, st); return true;
-    case GNN_ACT_SELU: launch_pair_one<LAYERS, GNN_ACT_SELU>(a, grid, lds_bytes, st); return true;
-    case GNN_ACT_ELU: launch_pair_one<LAYERS, GNN_ACT_ELU>(a, grid, lds_bytes, st); return true;
-    case GNN_ACT_TANH: launch_pair_one<LAYERS, GNN_ACT_TANH>(a, grid, lds_bytes, st); return true;
-    case GNN_ACT_SIGMOID: launch_pair_one<LAYERS, GNN_ACT_SIGMOID>(a, grid, lds_bytes, st); return true;
-    default: return false;
-    }
+    return dispatch_act(act, [&](auto A) { launch_pair_one<LAYERS, A.value>(a, grid, lds_bytes, st); return true; });
 }
 
 }   // namespace gnn_fused_dev
