@@ -476,7 +476,9 @@ __device__ __forceinline__ void split_pair(float v0, float v1, int &p0, int &p1,
 // A value is scaled by a power of two s (exact), then cut with round-to-nearest-even: p0 = f16(v s), p1 = f16(v s - p0) (the remainder is
 // exact in fp32); p0 + p1 carries 22 - 24 significant bits, and of the four piece products the three of relative weight >= 2^-12 are
 // accumulated (p1 q0, p0 q1, p0 q0); the dropped p1 q1 is <= 2^-24 |x w|.  Weights are scaled per layer (gnn_fused_pack: max |W s| in
-// [2^14, 2^15)), activations by the fixed 2^GNN_F16_EX (keeps p1 of values down to ~1e-3 out of the fp16 subnormals); the accumulator,
+// [2^14, 2^15)), activations by the fixed 2^GNN_F16_EX.  p1 is an fp16 subnormal for every |x| < 2^-7 (and for some x up to 2^-3); the
+// conversion and the MFMA keep subnormals (tests/test_fp16_edges.py, bit for bit), so the cut's error there is at most 2^-29 absolute:
+// relative max(2^-23, 2^-29 / |x|), 2^-19 at |x| = 1e-3, 2^-23 from 2^-6 on.  The accumulator,
 // started from the bias times the same 2^(e_w + e_x), is scaled back by 2^-(e_w + e_x) (exact) where the activation reads it.  A scaled
 // activation of magnitude >= GNN_F16_LIMIT would round to an fp16 infinity: the wave raises the range word of its flag slot, and the host
 // repeats the Loop in format 3 (run_loops).  The fp16 operand lane map is the bf16 one, so the k orders above hold unchanged.

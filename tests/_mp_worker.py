@@ -48,6 +48,28 @@ def main():
             res[f'{layout}_{impl}_max'] = np.float64(comm.allreduce_max(float(rank + 1)))
             lp.close()
         comm.close()
+    # ---- the range guard of the fp16-piece format across the rank processes: one node label past the fp16 range on the LAST rank only
+    # (test_fp16_edges.last_rank_trip_case); word 3 travels with the gate words, so every rank repeats the Loop in format 3 together
+    from test_fp16_edges import last_rank_trip_case
+    gf, stf, ouf, s0f = last_rank_trip_case(5151, 3000, world)
+    ipf, srcf, wf, awf, alf = S._csr_parts(gf)
+    maskf = np.logical_and(gf['set_mask'], gf['output_mask'])
+    os.environ['GNN_BENCH_RDV'] = os.path.join(out_dir, 'id_range')
+    uid, _ = bench.rendezvous_id(rank, world, e)
+    comm = e.Comm(uid, rank, world, 0)
+    rb, nr, ip, src, w, aw, al_ = e.shard_csr(3000, rank, world, ipf, srcf, wf, awf, alf)
+    grf = e.Graph(3000, ip, src, w, aw, al_, gf['nodes'], maskf[rb:rb + nr], row_begin=rb)
+    for pieces in (2, 3):
+        lp = e.Loop(grf, e.Mlp(stf['weights'], stf['activations'], True), e.Mlp(ouf['weights'], ouf['activations'], True), 64, 6, 0.0, comm)
+        assert lp.set_pieces(pieces) == pieces
+        lp.set_state0(s0f[rb:rb + nr])
+        res[f'range_{pieces}_k'] = np.float64(lp.run())
+        res[f'range_{pieces}_state'] = lp.state()
+        res[f'range_{pieces}_out'] = lp.output()
+        res[f'range_{pieces}_info'] = np.array(lp.range_info())
+        lp.close()
+    comm.close()
+
     # ---- the graph readout on shards (GNN.py:331-332; gnn_loop_readout on an RCCL communicator: per-rank partial [G, T], all-gathered, added in
     # rank order) - all-true masks, graphs that straddle shard boundaries among them
     gr_, stg, oug, s0g = S._case(911, 960, 8)

@@ -107,8 +107,9 @@ def test_fp16_pieces_match_bf16_pieces(n, act, hidden):
 
 @pytest.mark.gpu
 def test_small_magnitude_states_stay_accurate():
-    """States of about 1e-3 (small weights and biases, tanh, no BatchNormalization shift): the activation scale keeps the second fp16
-    piece out of the subnormals - within 1e-5 of the exact chain, and far closer in relative terms."""
+    """States of about 1e-3 (small weights and biases, tanh, no BatchNormalization shift): the second fp16 piece is a subnormal in almost
+    every cut at this magnitude (below 2^-7 always), so the cut is exact to 2^-29 absolute, about 2^-19 relative (test_fp16_edges.py,
+    test_cut_precision_curve) - within 1e-5 of the exact chain, and far closer in relative terms."""
     from GNN import GNN_utils as utils
     from util import make_mlp
     e = _engine()

@@ -74,6 +74,13 @@ def test_ranks_as_processes_match_oracle(world):
             assert {float(r[f'{layout}_{impl}_max']) for r in res} == {float(world)}      # gnn_comm_allreduce_max over the ranks
 
 
+    # ---- range guard on shards: the out-of-range label lives on the last rank only, every process repeats the Loop in format 3, and the
+    # ranks' rows together are bit-equal to the same job in format 3
+    assert all(tuple(r['range_2_info']) == (1, 1) and tuple(r['range_3_info']) == (0, 0) for r in res)
+    assert {float(r['range_2_k']) for r in res} == {float(res[0]['range_3_k'])}
+    for part in ('state', 'out'):
+        assert np.array_equal(np.concatenate([r[f'range_2_{part}'] for r in res]), np.concatenate([r[f'range_3_{part}'] for r in res]))
+
     # ---- graph readout on shards: every rank returns the same [G, T], the oracle's up to the rounding of graphs that straddle a shard boundary
     gr_, stg, oug, s0g = S._case(911, 960, 8)
     gr_['set_mask'] = np.ones(960, bool); gr_['output_mask'] = np.ones(960, bool)
