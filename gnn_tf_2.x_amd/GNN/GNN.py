@@ -183,8 +183,9 @@ class GNNnodeBased(BaseClass):
 
     def training_step(self, g: GraphTensor, mean: bool, *, state0=None, masks_state=None, masks_output=None) -> dict:
         """One batch: device gradients (gnn_loop_train_step), net_state gradients divided by the iteration count when
-        ``mean`` (reference GNN_BaseClass.py:241), optimizer update, BatchNormalization moving statistics.  Returns the raw
-        result of the device step (loss, k, gradients) for inspection."""
+        ``mean`` (reference GNN_BaseClass.py:241), optimizer update, BatchNormalization moving statistics.  L1L2 kernel / bias
+        regularizers and the optimizer's clipvalue / clipnorm / global_clipnorm are part of the device step.  Returns the raw
+        result of the device step (loss with the penalty, k, gradients with the regularizer terms) for inspection."""
         from GNN import losses
         if isinstance(g, GraphObject): g = GraphTensor.fromGraphObject(g)
         if self.optimizer is None or not hasattr(self.optimizer, 'apply_gradients'):
@@ -202,12 +203,17 @@ class GNNnodeBased(BaseClass):
         self._train_calls = getattr(self, '_train_calls', 0) + 1
         from GNN import regularizers
         dev_s, dev_o = self.net_state.device_mlp(self.device), self.net_output.device_mlp(self.device)
-        # Device-side optimizer step (weights, slots and gradients stay in HBM) when nothing of the step lives on the host:
-        # an optimizer that knows the engine's update rules and no kernel / bias regularizers (their gradients are host-side).
-        on_device = (getattr(self, 'device_optimizer', True) and not regularizers.any_regularizer(self.get_dense_layers())
+        # Device-side optimizer step (weights, slots and gradients stay in HBM) when nothing of the step lives on the host: an
+        # optimizer that knows the engine's update rules, and kernel / bias regularizers that are L1L2 (or none): their gradients,
+        # the penalty and the optimizer's gradient clipping run on the device too.  A custom Regularizer keeps the host path.
+        coef_s, coef_o = regularizers.device_coefficients(self.net_state.dense_layers), regularizers.device_coefficients(self.net_output.dense_layers)
+        on_device = (getattr(self, 'device_optimizer', True) and coef_s is not None and coef_o is not None
                      and hasattr(self.optimizer, 'device_step_args'))
         step_args = self.optimizer.device_step_args() if on_device else None
+        dev_s.set_regularizers(coef_s if step_args is not None else None)       # (host path: the terms are added below, in NumPy)
+        dev_o.set_regularizers(coef_o if step_args is not None else None)
         if step_args is not None:
+            loop.set_clipping(*self.optimizer.device_clip_args())
             self.net_state.bind_optimizer(self.optimizer)
             self.net_output.bind_optimizer(self.optimizer)
             bn_s, bn_o = self.net_state.layers[-1], self.net_output.layers[-1]

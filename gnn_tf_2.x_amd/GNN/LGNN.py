@@ -277,6 +277,15 @@ class LGNN(BaseClass):
             pairs = [_engine.loss_grad(kind, targets, o, weights) for o in outs]
             loss = float(np.mean([p[0] for p in pairs]))
             d_outs = [p[1] / L for p in pairs]
+        # kernel / bias regularizers that are L1L2 (or none) run on the device: every backward pass below then returns gradients that
+        # include their terms.  A custom Regularizer subclass, or device_optimizer = False, keeps all of the update on the host.
+        from GNN import regularizers
+        coefs = [(regularizers.device_coefficients(gnn.net_state.dense_layers), regularizers.device_coefficients(gnn.net_output.dense_layers)) for gnn in self.gnns]
+        on_device = (getattr(self, 'device_optimizer', True) and hasattr(self.optimizer, 'device_step_args')
+                     and all(cs is not None and co is not None for cs, co in coefs))
+        for gnn, (cs, co) in zip(self.gnns, coefs):
+            gnn.net_state.device_mlp(gnn.device).set_regularizers(cs if on_device else None)
+            gnn.net_output.device_mlp(gnn.device).set_regularizers(co if on_device else None)
         # ---- backward, last layer first ----
         ng = np.asarray(g.NodeGraph, dtype=np.float32) if graph_based else None
         results = [None] * L
@@ -297,17 +306,27 @@ class LGNN(BaseClass):
                 if self.get_output:     # the previous output sits on the arc labels of an edge-based layer, else on the node labels
                     d_out_extra = res['d_arcs'][mask, ALb:ALb + prev.T] if edge_based else res['d_nodes'][mask, c:c + prev.T]
         # ---- update: net_state gradients / k when mean (GNN_BaseClass.py:241); one optimizer over all layers (:244-247) ----
-        from GNN import regularizers
         # Device-side update (gnn_loop_optimizer_step per layer: gradients, weights and optimizer slots stay in HBM) when nothing of
-        # it lives on the host: an optimizer that knows the engine's update rules and no kernel / bias regularizers
-        if (getattr(self, 'device_optimizer', True) and hasattr(self.optimizer, 'device_step_args')
-                and not regularizers.any_regularizer(self.get_dense_layers())):
+        # it lives on the host: an optimizer that knows the engine's update rules and regularizers the device knows (above)
+        if on_device:
             kind_o, hyper = self.optimizer.device_step_args()           # one optimizer step over all layers (reference :244-247)
-            for gnn, loop, k in zip(self.gnns, loops, K):
+            clipvalue, clipnorm, global_clipnorm = self.optimizer.device_clip_args()
+            scales = [(1.0 / k) if (mean and k) else 1.0 for k in K]
+            for loop in loops: loop.set_clipping(clipvalue, clipnorm, 0.0)     # (the global norm spans the layers: it is taken here)
+            grad_scale = None
+            if global_clipnorm or regularizers.any_regularizer(self.get_dense_layers()):
+                # one read-back per layer: the penalties join the loss computed above, the sums of squares (of the scaled, value-clipped
+                # gradients of every layer) make the one global norm of the step
+                sq_pen = [loop.grad_sqnorm(sc) for loop, sc in zip(loops, scales)]
+                loss += sum(p for _, p in sq_pen)
+                if global_clipnorm:
+                    grad_scale = global_clipnorm / max(float(np.sqrt(sum(q for q, _ in sq_pen))), global_clipnorm)
+            for gnn, loop, sc in zip(self.gnns, loops, scales):
                 gnn.net_state.bind_optimizer(self.optimizer)
                 gnn.net_output.bind_optimizer(self.optimizer)
-                loop.optimizer_step(kind_o, hyper, (1.0 / k) if (mean and k) else 1.0, getattr(gnn.net_state.layers[-1], 'momentum', 0.99),
-                                    getattr(gnn.net_output.layers[-1], 'momentum', 0.99))
+                moms = getattr(gnn.net_state.layers[-1], 'momentum', 0.99), getattr(gnn.net_output.layers[-1], 'momentum', 0.99)
+                if grad_scale is None: loop.optimizer_step(kind_o, hyper, sc, *moms)
+                else: loop.optimizer_step_scaled(kind_o, hyper, sc, grad_scale, *moms)
                 gnn.net_state.mark_device_newer()
                 gnn.net_output.mark_device_newer()
             self.optimizer.device_step_done()

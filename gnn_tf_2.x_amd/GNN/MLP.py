@@ -338,7 +338,9 @@ def MLP(input_dim: int, layers: list[int], activations, kernel_initializer, bias
         dropout_rate, dropout_pos = [], []
     broadcast = lambda v: v if type(v) == list else [v for _ in layers]
     activations, kernel_initializer, bias_initializer = broadcast(activations), broadcast(kernel_initializer), broadcast(bias_initializer)
-    kernel_regularizer, bias_regularizer = broadcast(kernel_regularizer), broadcast(bias_regularizer)
+    from GNN import regularizers
+    kernel_regularizer = [regularizers.get(r) for r in broadcast(kernel_regularizer)]       # (the reference starter hands over Keras names)
+    bias_regularizer = [regularizers.get(r) for r in broadcast(bias_regularizer)]
     if type(dropout_pos) == int: dropout_pos = [dropout_pos]
     if type(dropout_rate) == float: dropout_rate = [dropout_rate for _ in dropout_pos]
     if len({len(x) for x in (activations, kernel_initializer, bias_initializer, kernel_regularizer, bias_regularizer, layers)}) > 1:

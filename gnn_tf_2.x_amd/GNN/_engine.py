@@ -20,6 +20,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_mlp_create', 'gnn_mlp_set_weights', 'gnn_mlp_get_weights', 'gnn_mlp_reset_optimizer', 'gnn_mlp_forward', 'gnn_mlp_destroy', 'gnn_loop_create',
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
+           'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
@@ -342,6 +343,20 @@ class Mlp:
         """gnn_mlp_reset_optimizer: zero optimizer slots for the next device-side step (a new optimizer object took over)."""
         _check(lib().gnn_mlp_reset_optimizer(self._h))
 
+    def set_regularizers(self, coefficients):
+        """gnn_mlp_set_regularizers: ([l1 per array], [l2 per array]) in [W1, b1, W2, b2, ...] order (GNN.regularizers.device_coefficients);
+        None clears them.  Remembered here, so that the call per training step costs nothing while they stay the same."""
+        key = None if coefficients is None else (tuple(coefficients[0]), tuple(coefficients[1]))
+        if key is not None and not any(key[0]) and not any(key[1]): key = None
+        if key == getattr(self, '_reg_set', None):
+            return
+        if key is None:
+            _check(lib().gnn_mlp_set_regularizers(self._h, None, None))
+        else:
+            if len(key[0]) != 2 * self.n or len(key[1]) != 2 * self.n: raise ValueError(f'expected {2 * self.n} coefficients per list')
+            _check(lib().gnn_mlp_set_regularizers(self._h, (C.c_double * (2 * self.n))(*key[0]), (C.c_double * (2 * self.n))(*key[1])))
+        self._reg_set = key
+
     def forward(self, x):
         x = _f32(x)
         if x.ndim != 2 or x.shape[1] != self.dims[0]:
@@ -512,6 +527,26 @@ class Loop:
         h = _f32(np.asarray(list(hyper) + [0.0] * (4 - len(hyper)), np.float32))
         _check(lib().gnn_loop_optimizer_step(self._h, C.c_int(kind), _fp(h), C.c_float(state_grad_scale), C.c_float(bn_momentum_state),
                                              C.c_float(bn_momentum_output)))
+
+    def set_clipping(self, clipvalue: float = 0.0, clipnorm: float = 0.0, global_clipnorm: float = 0.0):
+        """gnn_loop_set_clipping (0 = off): holds for every later armed train_step() / optimizer_step() of this loop."""
+        key = (float(clipvalue), float(clipnorm), float(global_clipnorm))
+        if key != getattr(self, '_clip_set', (0.0, 0.0, 0.0)):
+            _check(lib().gnn_loop_set_clipping(self._h, C.c_double(key[0]), C.c_double(key[1]), C.c_double(key[2])))
+            self._clip_set = key
+
+    def grad_sqnorm(self, state_grad_scale: float = 1.0):
+        """gnn_loop_grad_sqnorm: (sum of squares of this loop's scaled and value-clipped gradients, regularizer penalty of both nets)."""
+        sq, pen = C.c_double(), C.c_double()
+        _check(lib().gnn_loop_grad_sqnorm(self._h, C.c_float(state_grad_scale), C.byref(sq), C.byref(pen)))
+        return sq.value, pen.value
+
+    def optimizer_step_scaled(self, kind: int, hyper, state_grad_scale: float, grad_scale: float, bn_momentum_state: float = 0.99,
+                              bn_momentum_output: float = 0.99):
+        """gnn_loop_optimizer_step_scaled: optimizer_step() with the factor of a global norm that spans several loops."""
+        h = _f32(np.asarray(list(hyper) + [0.0] * (4 - len(hyper)), np.float32))
+        _check(lib().gnn_loop_optimizer_step_scaled(self._h, C.c_int(kind), _fp(h), C.c_float(state_grad_scale), C.c_double(grad_scale),
+                                                    C.c_float(bn_momentum_state), C.c_float(bn_momentum_output)))
 
     @staticmethod
     def _grad_shapes(net: 'Mlp'):

@@ -222,6 +222,9 @@ struct gnn_mlp {
     // slots of the device-side optimizer (gnn_loop_optimizer_step), laid out like the gradient vector
     // (dW1, db1, ..., dgamma, dbeta); allocated on first use, zero at that point
     float *opt_a = nullptr, *opt_b = nullptr;
+    // L1 / L2 coefficients of the kernel / bias regularizers per array, [W1, b1, W2, b2, ...] (gnn_mlp_set_regularizers);
+    // empty = none.  The training step adds their gradient and penalty on the device (gnn_train.hip: k_grad_prepare)
+    std::vector<double> reg_l1, reg_l2;
     bool has_bn = false;
     float eps = 1e-3f;
     // fused-kernel weight image (see gnn_fused.hip), rebuilt by set_weights

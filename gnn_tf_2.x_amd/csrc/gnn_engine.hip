@@ -1108,6 +1108,20 @@ extern "C" int gnn_mlp_reset_optimizer(gnn_mlp *m)
     return GNN_OK;
 }
 
+extern "C" int gnn_mlp_set_regularizers(gnn_mlp *m, const double *l1, const double *l2)
+{
+    ARGCHK(m && ((l1 == nullptr) == (l2 == nullptr)), "mlp is NULL, or only one of l1 / l2 given (both NULL clears the regularizers)");
+    const int n = 2 * m->n_layers;
+    bool any = false;
+    for (int a = 0; l1 && a < n; ++a) {
+        ARGCHK(std::isfinite(l1[a]) && std::isfinite(l2[a]) && l1[a] >= 0.0 && l2[a] >= 0.0, "array %d: regularizer coefficients must be finite and >= 0", a);
+        any = any || l1[a] != 0.0 || l2[a] != 0.0;
+    }
+    if (any) { m->reg_l1.assign(l1, l1 + n); m->reg_l2.assign(l2, l2 + n); }
+    else { m->reg_l1.clear(); m->reg_l2.clear(); }
+    return GNN_OK;
+}
+
 extern "C" int gnn_mlp_forward(gnn_mlp *m, int64_t n_rows, const float *x, float *y)
 {
     ARGCHK(m && n_rows >= 0 && (n_rows == 0 || (x && y)), "bad arguments");

@@ -2008,6 +2008,8 @@ struct TrainArena {
     // optimizer armed for the next gnn_loop_train_step (gnn_loop_arm_optimizer): applied behind the backward pass, before the
     // step's only wait for the device
     struct { bool armed = false; int kind = 0; float h[4] = {0, 0, 0, 0}; bool mean = false; float mom_s = 0.99f, mom_o = 0.99f; } opt;
+    // gradient clipping of every optimizer update of this loop (gnn_loop_set_clipping); 0 = off
+    struct { float value = 0.0f; double norm = 0.0, global = 0.0; } clip;
     // pinned host words for the results the host waits for (iteration gates, loss partials)
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -2643,6 +2645,13 @@ struct TrainCtx {
     int64_t N_global = 0, M_global = 0;   // sharded forward: the rows / masked rows of all ranks
     bool backward_done = false;   // the gradients are complete (and the activations spent)
     bool applied = false;         // gnn_loop_optimizer_step has consumed them
+    // regularizer penalty, per-block partials of k_grad_prepare: net_state's blocks, then net_output's (0 blocks: no regularizer there)
+    double *pen_part = nullptr;
+    unsigned pen_blocks[2] = {0, 0};
+    // gradient clipping (clip_prepare): per-block partial sums of squares of both nets, their sums per array [2][CLIP_SLOTS] and
+    // over all arrays [1], and the factor of every array [2][CLIP_SLOTS]
+    double *sq_part[2] = {nullptr, nullptr}, *sq = nullptr;
+    float *factor = nullptr;
 };
 
 constexpr int TRAIN_CHUNK = 5;     // bodies enqueued between two looks at the iteration gates (see train_forward)
@@ -2664,6 +2673,190 @@ void gnn_train_arena_free(gnn_loop *l)
         l->train_arena = nullptr;
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Between the backward pass and the update, on the device: the regularizer terms of the taped loss (reference
+// GNN_BaseClass.py:223-235) and the gradient clipping of tf.keras optimizers (clipvalue, clipnorm, global_clipnorm).
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int CLIP_SLOTS = 35;    // arrays of one net: 16 layers x (W, b) + gamma + beta at most
+
+struct ParamMap {                 // gradient vector index -> parameter array
+    int n = 0;
+    int goff[CLIP_SLOTS + 1];     // [n + 1]
+    float *p[CLIP_SLOTS];
+};
+
+ParamMap param_map(const gnn_mlp *m, const Net &net)
+{
+    ParamMap mp;
+    const int L = m->n_layers;
+    for (int l = 0; l < L; ++l) {
+        mp.goff[2 * l] = (int)net.g_off[2 * l]; mp.p[2 * l] = m->W[l];
+        mp.goff[2 * l + 1] = (int)net.g_off[2 * l + 1]; mp.p[2 * l + 1] = m->b[l];
+    }
+    mp.n = 2 * L;
+    if (m->has_bn) {
+        const int F = m->dims.back();
+        mp.goff[mp.n] = (int)net.g_off[2 * L]; mp.p[mp.n] = m->bn_raw; ++mp.n;
+        mp.goff[mp.n] = (int)net.g_off[2 * L + 1]; mp.p[mp.n] = m->bn_raw + F; ++mp.n;
+    }
+    mp.goff[mp.n] = (int)net.g_total;
+    return mp;
+}
+
+inline size_t mlp_grad_floats(const gnn_mlp *m)
+{
+    size_t t = 0;
+    for (int l = 0; l < m->n_layers; ++l) t += (size_t)m->dims[l] * m->dims[l + 1] + (size_t)m->dims[l + 1];
+    return t + (m->has_bn ? (size_t)2 * m->dims.back() : 0);
+}
+
+struct RegCoef { double l1[CLIP_SLOTS], l2[CLIP_SLOTS]; };
+
+// sum of the 256 values of a block, the same tree in every run; the result is valid in thread 0
+__device__ inline double block_sum256(double *red, double v)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// g <- g + l1 sign(w) + 2 l2 w (sign(0) = 0; the term is rounded to float first, like the host mirror GNN/regularizers.py), and the
+// block's share of the penalty l1 sum |w| + l2 sum w^2 (GNN_BaseClass.py:223-228) -> pen_part[block]
+__global__ void __launch_bounds__(256) k_grad_prepare(ParamMap mp, RegCoef rc, float *g, double *pen_part)
+{
+    __shared__ double red[256];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    double pen = 0.0;
+    if (j < mp.goff[mp.n]) {
+        int a = 0;
+        while (j >= mp.goff[a + 1]) ++a;
+        const double l1 = rc.l1[a], l2 = rc.l2[a];
+        if (l1 != 0.0 || l2 != 0.0) {
+            const double w = (double)mp.p[a][j - mp.goff[a]];
+            const double sgn = w > 0.0 ? 1.0 : (w < 0.0 ? -1.0 : 0.0);
+            g[j] += (float)(l1 * sgn + 2.0 * l2 * w);
+            pen = l1 * fabs(w) + l2 * w * w;
+        }
+    }
+    pen = block_sum256(red, pen);
+    if (threadIdx.x == 0) pen_part[blockIdx.x] = pen;
+}
+
+__device__ inline float clip_value(float v, float c) { return c > 0.0f ? (v > c ? c : (v < -c ? -c : v)) : v; }
+
+// Segmented sum of squares of the scaled and value-clipped gradients: block b leaves, for every array a with entries in
+// [256 b, 256 b + 256), their sum of squares in part[a * gridDim.x + b] (the other entries of part are never read).
+__global__ void __launch_bounds__(256) k_grad_sqnorm(ParamMap mp, const float *g, float gscale, float clipvalue, double *part)
+{
+    __shared__ double red[256];
+    const int b0 = blockIdx.x * 256, j = b0 + threadIdx.x, total = mp.goff[mp.n];
+    int a = -1;
+    double sq = 0.0;
+    if (j < total) {
+        a = 0;
+        while (j >= mp.goff[a + 1]) ++a;
+        const float v = clip_value(g[j] * gscale, clipvalue);
+        sq = (double)v * (double)v;
+    }
+    const int last = min(b0 + 256, total) - 1;       // the arrays of this block: first .. until (the same in every thread)
+    int first = 0;
+    while (b0 >= mp.goff[first + 1]) ++first;
+    int until = first;
+    while (last >= mp.goff[until + 1]) ++until;
+    for (int s = first; s <= until; ++s) {
+        const double r = block_sum256(red, a == s ? sq : 0.0);
+        if (threadIdx.x == 0) part[(size_t)s * gridDim.x + blockIdx.x] = r;
+    }
+}
+
+struct ClipJob {
+    int n[2], blocks[2];
+    int goff[2][CLIP_SLOTS + 1];
+    const double *part[2];
+};
+
+// One block: the partials of every array added in block order -> sq[net * CLIP_SLOTS + a], all of them in index order ->
+// sq[2 CLIP_SLOTS]; factor of array a = clipnorm / max(|g_a|, clipnorm) * global / max(|g|, global) * extra (a threshold of 0: 1)
+__global__ void __launch_bounds__(128) k_clip_factors(ClipJob cj, double clipnorm, double global_clipnorm, double extra, double *sq, float *factor)
+{
+    __shared__ double s_sq[2 * CLIP_SLOTS];
+    for (int idx = threadIdx.x; idx < 2 * CLIP_SLOTS; idx += blockDim.x) {
+        const int net = idx / CLIP_SLOTS, a = idx - net * CLIP_SLOTS;
+        double s = 0.0;
+        if (a < cj.n[net] && cj.goff[net][a + 1] > cj.goff[net][a]) {
+            const int bf = cj.goff[net][a] / 256, bl = (cj.goff[net][a + 1] - 1) / 256;
+            for (int b = bf; b <= bl; ++b) s += cj.part[net][(size_t)a * cj.blocks[net] + b];
+        }
+        s_sq[idx] = s;
+        sq[idx] = s;
+    }
+    __syncthreads();
+    double tot = 0.0;
+    for (int idx = 0; idx < 2 * CLIP_SLOTS; ++idx) tot += s_sq[idx];
+    if (threadIdx.x == 0) sq[2 * CLIP_SLOTS] = tot;
+    for (int idx = threadIdx.x; idx < 2 * CLIP_SLOTS; idx += blockDim.x) {
+        double f = extra;
+        if (clipnorm > 0.0) f *= clipnorm / fmax(sqrt(s_sq[idx]), clipnorm);
+        if (global_clipnorm > 0.0) f *= global_clipnorm / fmax(sqrt(tot), global_clipnorm);
+        factor[idx] = (float)f;
+    }
+}
+
+// the regularizer terms of both nets, behind the backward pass and in front of every reader of the gradients
+int grad_prepare(gnn_loop *l, TrainCtx *cx, hipStream_t st)
+{
+    struct { gnn_mlp *m; Net *net; } nets[2] = {{l->st, &cx->ns}, {l->ou, &cx->no_}};
+    unsigned blocks[2] = {0, 0};
+    for (int i = 0; i < 2; ++i)
+        if (!nets[i].m->reg_l1.empty()) blocks[i] = cdiv((int64_t)nets[i].net->g_total, 256);
+    if (!blocks[0] && !blocks[1]) return GNN_OK;
+    ARGCHK(l->st->n_layers <= 16 && l->ou->n_layers <= 16, "too many layers");
+    int rc;
+    if ((rc = cx->buf.get(&cx->pen_part, (size_t)blocks[0] + blocks[1]))) return rc;
+    for (int i = 0; i < 2; ++i) {
+        cx->pen_blocks[i] = blocks[i];
+        if (!blocks[i]) continue;
+        const gnn_mlp *m = nets[i].m;
+        RegCoef co;
+        for (int a = 0; a < CLIP_SLOTS; ++a) {
+            const bool dense = a < 2 * m->n_layers;        // BatchNormalization's gamma / beta carry no regularizer
+            co.l1[a] = dense ? m->reg_l1[a] : 0.0; co.l2[a] = dense ? m->reg_l2[a] : 0.0;
+        }
+        hipLaunchKernelGGL(k_grad_prepare, blocks[i], 256, 0, st, param_map(m, *nets[i].net), co, nets[i].net->grads, cx->pen_part + (i ? blocks[0] : 0));
+        HIPCHK(hipGetLastError());
+    }
+    return GNN_OK;
+}
+
+// cx->sq and cx->factor from the gradients as they are now (net_state's scaled by gscale_state), on the stream
+int clip_prepare(gnn_loop *l, TrainCtx *cx, hipStream_t st, float gscale_state, float clipvalue, double clipnorm, double global_clipnorm, double extra)
+{
+    struct { gnn_mlp *m; Net *net; float gscale; } nets[2] = {{l->st, &cx->ns, gscale_state}, {l->ou, &cx->no_, 1.0f}};
+    ClipJob cj;
+    int rc;
+    if (!cx->sq && ((rc = cx->buf.get(&cx->sq, (size_t)2 * CLIP_SLOTS + 1)) || (rc = cx->buf.get(&cx->factor, (size_t)2 * CLIP_SLOTS)))) return rc;
+    for (int i = 0; i < 2; ++i) {
+        const ParamMap mp = param_map(nets[i].m, *nets[i].net);
+        const unsigned blocks = cdiv((int64_t)nets[i].net->g_total, 256);
+        if (!cx->sq_part[i] && (rc = cx->buf.get(&cx->sq_part[i], (size_t)mp.n * blocks))) return rc;
+        hipLaunchKernelGGL(k_grad_sqnorm, blocks, 256, 0, st, mp, nets[i].net->grads, nets[i].gscale, clipvalue, cx->sq_part[i]);
+        HIPCHK(hipGetLastError());
+        cj.n[i] = mp.n; cj.blocks[i] = (int)blocks; cj.part[i] = cx->sq_part[i];
+        for (int a = 0; a <= mp.n; ++a) cj.goff[i][a] = mp.goff[a];
+    }
+    hipLaunchKernelGGL(k_clip_factors, 1, 128, 0, st, cj, clipnorm, global_clipnorm, extra, cx->sq, cx->factor);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+}   // namespace
 
 extern "C" int gnn_loss_grad(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out, const float *sample_weights,
                              double *loss, float *d_out)
@@ -3056,6 +3249,7 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
             HIPCHK(hipGetLastError());
         }
     }
+    if ((rc = grad_prepare(l, cx, st))) return rc;     // the gradients the caller gets include the regularizer terms (gnn_mlp_set_regularizers)
     HIPCHK(hipMemcpyAsync(grads_state, ns.grads, sizeof(float) * ns.g_total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(grads_output, no_.grads, sizeof(float) * no_.g_total, hipMemcpyDeviceToHost, st));
     if (bn_batch_state && l->st->has_bn && k > 0)      // the statistics of the calls are adjacent, in call order
@@ -3087,22 +3281,20 @@ extern "C" int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, co
 // both nets; Keras BatchNormalization moving statistics): the weights, the optimizer slots and the gradients never leave HBM.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-struct ParamMap {                 // gradient vector index -> parameter array
-    int n = 0;
-    int goff[36];                 // [n + 1]
-    float *p[35];
-};
-
 // kind 0, SGD: h = {learning rate, momentum}: v <- momentum v - lr g, p <- p + v
 // kind 1, Adam (Keras): h = {lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), b1, b2, epsilon}: m, v updated, p <- p - lr_t m / (sqrt(v) + epsilon)
-__global__ void k_optimizer(ParamMap mp, const float *g, float gscale, float *sa, float *sb, int kind, float h0, float h1, float h2, float h3)
+// CLIP: the scaled gradient is clipped by value and multiplied by its array's factor (k_clip_factors) first
+template <bool CLIP>
+__global__ void k_optimizer(ParamMap mp, const float *g, float gscale, float clipvalue, const float *factor, float *sa, float *sb, int kind, float h0,
+                            float h1, float h2, float h3)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= mp.goff[mp.n]) return;
     int a = 0;
     while (j >= mp.goff[a + 1]) ++a;
     float *p = mp.p[a] + (j - mp.goff[a]);
-    const float gr = g[j] * gscale;
+    float gr = g[j] * gscale;
+    if (CLIP) gr = clip_value(gr, clipvalue) * factor[a];
     if (kind == 1) {
         const float m = h1 * sa[j] + (1.0f - h1) * gr;
         const float v = h2 * sb[j] + (1.0f - h2) * gr * gr;
@@ -3128,7 +3320,9 @@ __global__ void k_bn_moving(int F, int calls, const float *stats_all, float mome
     raw[2 * F + j] = mean; raw[3 * F + j] = var;
 }
 
-int optimizer_apply(hipStream_t st, gnn_mlp *m, const Net &net, int calls, int kind, const float *h, float gscale, float bn_momentum)
+// factor: the per-array clip factors of this net on the device (clip_prepare), NULL = no clipping
+int optimizer_apply(hipStream_t st, gnn_mlp *m, const Net &net, int calls, int kind, const float *h, float gscale, float bn_momentum, float clipvalue = 0.0f,
+                    const float *factor = nullptr)
 {
     const size_t total = net.g_total;
     if (!m->opt_a) {
@@ -3137,20 +3331,13 @@ int optimizer_apply(hipStream_t st, gnn_mlp *m, const Net &net, int calls, int k
         HIPCHK(hipMemsetAsync(m->opt_a, 0, sizeof(float) * total, st));
         HIPCHK(hipMemsetAsync(m->opt_b, 0, sizeof(float) * total, st));
     }
-    ParamMap mp;
-    const int L = m->n_layers;
-    for (int l = 0; l < L; ++l) {
-        mp.goff[2 * l] = (int)net.g_off[2 * l]; mp.p[2 * l] = m->W[l];
-        mp.goff[2 * l + 1] = (int)net.g_off[2 * l + 1]; mp.p[2 * l + 1] = m->b[l];
-    }
-    mp.n = 2 * L;
-    if (m->has_bn) {
-        const int F = m->dims.back();
-        mp.goff[mp.n] = (int)net.g_off[2 * L]; mp.p[mp.n] = m->bn_raw; ++mp.n;
-        mp.goff[mp.n] = (int)net.g_off[2 * L + 1]; mp.p[mp.n] = m->bn_raw + F; ++mp.n;
-    }
-    mp.goff[mp.n] = (int)total;
-    hipLaunchKernelGGL(k_optimizer, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, m->opt_a, m->opt_b, kind, h[0], h[1], h[2], h[3]);
+    const ParamMap mp = param_map(m, net);
+    if (factor)
+        hipLaunchKernelGGL(k_optimizer<true>, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, clipvalue, factor, m->opt_a, m->opt_b, kind, h[0],
+                           h[1], h[2], h[3]);
+    else
+        hipLaunchKernelGGL(k_optimizer<false>, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, 0.0f, nullptr, m->opt_a, m->opt_b, kind, h[0],
+                           h[1], h[2], h[3]);
     HIPCHK(hipGetLastError());
     if (m->has_bn) {
         const int F = m->dims.back();
@@ -3163,10 +3350,22 @@ int optimizer_apply(hipStream_t st, gnn_mlp *m, const Net &net, int calls, int k
     m->pack_dirty = true;
     return GNN_OK;
 }
-}   // namespace
 
-extern "C" int gnn_loop_optimizer_step(gnn_loop *l, int kind, const float *hyper, float state_grad_scale, float bn_momentum_state,
-                                       float bn_momentum_output)
+// The update of both nets with the loop's clipping (gnn_loop_set_clipping): the norms of both nets are on the device before either
+// net changes.  own_global: the loop's global_clipnorm applies (else the caller's norm spans more than this loop: `extra` carries it).
+int update_both(gnn_loop *l, TrainCtx *cx, hipStream_t st, int kind, const float *h, float gscale_state, float mom_s, float mom_o, bool own_global, double extra)
+{
+    const TrainArena *arena = static_cast<const TrainArena *>(l->train_arena);
+    const float cv = arena ? arena->clip.value : 0.0f;
+    const double cn = arena ? arena->clip.norm : 0.0, cg = (arena && own_global) ? arena->clip.global : 0.0;
+    const bool clip = cv > 0.0f || cn > 0.0 || cg > 0.0 || extra != 1.0;
+    int rc;
+    if (clip && (rc = clip_prepare(l, cx, st, gscale_state, cv, cn, cg, extra))) return rc;
+    if ((rc = optimizer_apply(st, l->st, cx->ns, cx->k, kind, h, gscale_state, mom_s, cv, clip ? cx->factor : nullptr))) return rc;
+    return optimizer_apply(st, l->ou, cx->no_, cx->M > 0 ? 1 : 0, kind, h, 1.0f, mom_o, cv, clip ? cx->factor + CLIP_SLOTS : nullptr);
+}
+
+int optimizer_step(gnn_loop *l, int kind, const float *hyper, float state_grad_scale, float bn_momentum_state, float bn_momentum_output, bool own_global, double extra)
 {
     ARGCHK(l && hyper && (kind == 0 || kind == 1), "bad arguments (kind: 0 SGD, 1 Adam)");
     TrainCtx *cx = static_cast<TrainCtx *>(l->train_ctx);
@@ -3174,11 +3373,62 @@ extern "C" int gnn_loop_optimizer_step(gnn_loop *l, int kind, const float *hyper
     ARGCHK(l->st->n_layers <= 16 && l->ou->n_layers <= 16, "too many layers");
     HIPCHK(hipSetDevice(l->device));
     hipStream_t st = l->stream;
-    int rc = optimizer_apply(st, l->st, cx->ns, cx->k, kind, hyper, state_grad_scale, bn_momentum_state);
-    if (!rc) rc = optimizer_apply(st, l->ou, cx->no_, cx->M > 0 ? 1 : 0, kind, hyper, 1.0f, bn_momentum_output);
+    int rc = update_both(l, cx, st, kind, hyper, state_grad_scale, bn_momentum_state, bn_momentum_output, own_global, extra);
     cx->applied = true;
     if (!rc) HIPCHK(hipStreamSynchronize(st));   // other loops (other streams) may use these weights next
     return rc;
+}
+}   // namespace
+
+extern "C" int gnn_loop_optimizer_step(gnn_loop *l, int kind, const float *hyper, float state_grad_scale, float bn_momentum_state,
+                                       float bn_momentum_output)
+{
+    return optimizer_step(l, kind, hyper, state_grad_scale, bn_momentum_state, bn_momentum_output, true, 1.0);
+}
+
+extern "C" int gnn_loop_optimizer_step_scaled(gnn_loop *l, int kind, const float *hyper, float state_grad_scale, double grad_scale,
+                                              float bn_momentum_state, float bn_momentum_output)
+{
+    ARGCHK(std::isfinite(grad_scale) && grad_scale > 0.0, "grad_scale must be finite and > 0");
+    return optimizer_step(l, kind, hyper, state_grad_scale, bn_momentum_state, bn_momentum_output, false, grad_scale);
+}
+
+extern "C" int gnn_loop_set_clipping(gnn_loop *l, double clipvalue, double clipnorm, double global_clipnorm)
+{
+    ARGCHK(l, "loop is NULL");
+    ARGCHK(std::isfinite(clipvalue) && std::isfinite(clipnorm) && std::isfinite(global_clipnorm) && clipvalue >= 0.0 && clipnorm >= 0.0 && global_clipnorm >= 0.0,
+           "clipvalue, clipnorm and global_clipnorm must be finite and >= 0 (0 = off)");
+    ARGCHK(clipvalue == 0.0 || (float)clipvalue > 0.0f, "clipvalue is below the float32 range of the gradients");
+    ARGCHK(!(clipnorm > 0.0 && global_clipnorm > 0.0), "clipnorm and global_clipnorm exclude each other (as in tf.keras)");
+    if (!l->train_arena) l->train_arena = new TrainArena();
+    TrainArena *arena = static_cast<TrainArena *>(l->train_arena);
+    arena->clip.value = (float)clipvalue; arena->clip.norm = clipnorm; arena->clip.global = global_clipnorm;
+    return GNN_OK;
+}
+
+extern "C" int gnn_loop_grad_sqnorm(gnn_loop *l, float state_grad_scale, double *sqnorm, double *penalty)
+{
+    ARGCHK(l && (sqnorm || penalty), "bad arguments");
+    TrainCtx *cx = static_cast<TrainCtx *>(l->train_ctx);
+    if (!cx || !cx->backward_done || cx->applied) return gnn_fail(GNN_ERR_STATE, "no fresh gradients: run gnn_loop_train_step (or forward + backward) first");
+    ARGCHK(l->st->n_layers <= 16 && l->ou->n_layers <= 16, "too many layers");
+    HIPCHK(hipSetDevice(l->device));
+    hipStream_t st = l->stream;
+    const TrainArena *arena = static_cast<const TrainArena *>(l->train_arena);
+    int rc;
+    if (sqnorm) {
+        if ((rc = clip_prepare(l, cx, st, state_grad_scale, arena ? arena->clip.value : 0.0f, 0.0, 0.0, 1.0))) return rc;
+        HIPCHK(hipMemcpyAsync(sqnorm, cx->sq + 2 * CLIP_SLOTS, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    const unsigned pb = cx->pen_blocks[0] + cx->pen_blocks[1];
+    std::vector<double> part(pb);
+    if (penalty && pb) HIPCHK(hipMemcpyAsync(part.data(), cx->pen_part, sizeof(double) * pb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (penalty) {
+        *penalty = 0.0;
+        for (unsigned b = 0; b < pb; ++b) *penalty += part[b];
+    }
+    return GNN_OK;
 }
 
 extern "C" int gnn_loop_update_moving_statistics(gnn_loop *l, float bn_momentum_state, float bn_momentum_output)
@@ -3245,7 +3495,9 @@ extern "C" int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const
     const int64_t nt = n_targets;
     const unsigned lblocks = nt ? cdiv(nt, 256) : 0;
     double loss = 0.0;
-    double *h_lp = static_cast<double *>(arena->host(std::max<size_t>(sizeof(double) * lblocks, 4096)));
+    // (behind the loss partials: the penalty partials of the regularizers, gnn_mlp_set_regularizers - at most one per 256 trainable floats)
+    const size_t pen_max = (l->st->reg_l1.empty() ? 0 : cdiv((int64_t)mlp_grad_floats(l->st), 256)) + (l->ou->reg_l1.empty() ? 0 : cdiv((int64_t)mlp_grad_floats(l->ou), 256));
+    double *h_lp = static_cast<double *>(arena->host(std::max<size_t>(sizeof(double) * (lblocks + pen_max), 4096)));
     if (!h_lp) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
     // the step's small inputs, packed into pinned memory and uploaded in one transfer: targets | sample weights | NodeGraph^T CSR
     const int64_t ne = n_graphs > 0 ? ng_indptr[n_graphs] : 0;
@@ -3284,15 +3536,17 @@ extern "C" int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const
     if (lblocks) HIPCHK(hipMemcpyAsync(h_lp, d_lp, sizeof(double) * lblocks, hipMemcpyDeviceToHost, st));
     rc = train_backward(l, d_dnodes, nullptr, nullptr, grads_state, grads_output, bn_batch_state, bn_batch_output, nullptr, nullptr, false);
     if (rc) return rc;
+    const unsigned pblocks = cx->pen_blocks[0] + cx->pen_blocks[1];       // the penalty is part of the loss (GNN_BaseClass.py:223-235)
+    if (pblocks > pen_max) return gnn_fail(GNN_ERR_STATE, "internal: more penalty partials than announced");
+    if (pblocks) HIPCHK(hipMemcpyAsync(h_lp + lblocks, cx->pen_part, sizeof(double) * pblocks, hipMemcpyDeviceToHost, st));
     if (arena->opt.armed) {                        // gnn_loop_arm_optimizer: the update rides on this step's stream work
         arena->opt.armed = false;
         const float gscale = (arena->opt.mean && cx->k > 0) ? 1.0f / (float)cx->k : 1.0f;
-        if ((rc = optimizer_apply(st, l->st, cx->ns, cx->k, arena->opt.kind, arena->opt.h, gscale, arena->opt.mom_s))) return rc;
-        if ((rc = optimizer_apply(st, l->ou, cx->no_, cx->M > 0 ? 1 : 0, arena->opt.kind, arena->opt.h, 1.0f, arena->opt.mom_o))) return rc;
+        if ((rc = update_both(l, cx, st, arena->opt.kind, arena->opt.h, gscale, arena->opt.mom_s, arena->opt.mom_o, true, 1.0))) return rc;
         cx->applied = true;
     }
     HIPCHK(hipStreamSynchronize(st));
-    for (unsigned b = 0; b < lblocks; ++b) loss += h_lp[b];
+    for (unsigned b = 0; b < lblocks + pblocks; ++b) loss += h_lp[b];
     *loss_out = (float)loss;
     return GNN_OK;
 }

@@ -47,6 +47,8 @@ norm_arcs_range: Optional[tuple] = None
 activations_net_state: str = 'selu'
 kernel_init_net_state: str = 'lecun_normal'
 bias_init_net_state: str = 'lecun_normal'
+kernel_reg_net_state: Optional[str] = None          # 'l1' / 'l2' / 'l1_l2' or a GNN.regularizers object (reference starter.py:55-56)
+bias_reg_net_state: Optional[str] = None
 dropout_rate_st: float = 0.1
 dropout_pos_st: Union[list, int] = 0
 hidden_units_net_state: Optional[Union[list, int]] = None
@@ -54,6 +56,8 @@ hidden_units_net_state: Optional[Union[list, int]] = None
 activations_net_output: str = 'softmax'
 kernel_init_net_output: str = 'glorot_normal'
 bias_init_net_output: str = 'glorot_normal'
+kernel_reg_net_output: Optional[str] = None
+bias_reg_net_output: Optional[str] = None
 dropout_rate_out: float = 0.1
 dropout_pos_out: Union[list, int] = 0
 hidden_units_net_output: Optional[Union[list, int]] = None
@@ -91,7 +95,7 @@ if normalize:
     utils.normalize_graphs(gTr, gVa, gTe, based_on='gTr', norm_rangeN=norm_nodes_range, norm_rangeA=norm_arcs_range)
 
 # ---- models ----------------------------------------------------------------------------------------------------------------
-def _nets(net_name, hidden, activations, kinit, binit, drate, dpos):
+def _nets(net_name, hidden, activations, kinit, binit, kreg, breg, drate, dpos):
     dims = [get_inout_dims(net_name=net_name, dim_node_label=gGen.DIM_NODE_LABEL, dim_arc_label=gGen.DIM_ARC_LABEL,
                            dim_target=gGen.DIM_TARGET, problem_based=problem_based, dim_state=dim_state, hidden_units=hidden,
                            layer=i, get_state=get_state, get_output=get_output) for i in range(layers)]
@@ -101,10 +105,13 @@ def _nets(net_name, hidden, activations, kinit, binit, drate, dpos):
     # layer off for net_output (what tools/run_starter.py does to show the training loop learning).
     bn = net_name != 'output' or os.environ.get('GNN_STARTER_OUTPUT_BN', '1') != '0'
     return [MLP(input_dim=i, layers=j, activations=activations, kernel_initializer=kinit, bias_initializer=binit,
+                kernel_regularizer=kreg, bias_regularizer=breg,
                 dropout_rate=drate, dropout_pos=dpos, batch_normalization=bn) for i, j in dims]
 
-nets_St = _nets('state', hidden_units_net_state, activations_net_state, kernel_init_net_state, bias_init_net_state, dropout_rate_st, dropout_pos_st)
-nets_Out = _nets('output', hidden_units_net_output, activations_net_output, kernel_init_net_output, bias_init_net_output, dropout_rate_out, dropout_pos_out)
+nets_St = _nets('state', hidden_units_net_state, activations_net_state, kernel_init_net_state, bias_init_net_state,
+                kernel_reg_net_state, bias_reg_net_state, dropout_rate_st, dropout_pos_st)
+nets_Out = _nets('output', hidden_units_net_output, activations_net_output, kernel_init_net_output, bias_init_net_output,
+                 kernel_reg_net_output, bias_reg_net_output, dropout_rate_out, dropout_pos_out)
 
 gnntype = {'n': GNNnodeBased, 'a': GNNedgeBased, 'g': GNNgraphBased}[problem_based]
 gnns = [gnntype(net_state=st, net_output=out, optimizer=optimizer.__class__(**optimizer.get_config()), loss_function=lossF, loss_arguments=lossArguments,

@@ -225,6 +225,35 @@ int gnn_loop_optimizer_step(gnn_loop *l, int kind, const float *hyper, float sta
                             float bn_momentum_output);
 int gnn_loss_grad(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out,
                   const float *sample_weights, double *loss, float *d_out);
+/* Kernel / bias regularizers on the device (reference starter.py:55-66 hands them to MLP(), GNN/MLP.py:11-13; their penalties are
+ * summed into the taped loss, GNN_BaseClass.py:223-235).  l1 / l2: [2 n_layers] coefficients per array in [W1, b1, W2, b2, ...]
+ * order (BatchNormalization's gamma / beta never carry one); both NULL clears them; a negative or non-finite coefficient is
+ * GNN_ERR_ARG.  From then on every backward pass of a loop with this net (gnn_loop_train_step, gnn_loop_train_backward) adds
+ * l1 sign(w) + 2 l2 w (sign(0) = 0, w = the array before the update) to the gradient of every array before the gradients are
+ * copied back or applied - the returned gradients include the term, still raw (not divided by k) - and gnn_loop_train_step adds the
+ * penalty sum_a l1_a sum |w| + l2_a sum w^2 to *loss_out (its partial sums are read at the step's one wait). */
+int gnn_mlp_set_regularizers(gnn_mlp *m, const double *l1, const double *l2);
+/* Gradient clipping of the device-side update, as tf.keras optimizers define it (reference starter.py:81 takes any Keras
+ * optimizer; the update is GNN_BaseClass.py:243-247).  0 = off; clipnorm together with global_clipnorm, a negative or a
+ * non-finite value is GNN_ERR_ARG.  Applies to every later armed gnn_loop_train_step and every gnn_loop_optimizer_step of this
+ * loop until changed.  On the gradients after the regularizer terms and after the division of net_state's by k (:241), in this
+ * order: clipvalue c: g <- min(max(g, -c), c) per entry; clipnorm c: g_a <- g_a c / max(|g_a|_2, c) per array; global_clipnorm
+ * c: g <- g c / max(|g|_2, c) with the norm over ALL arrays of both nets.  (The order value, norm, global is a definition of
+ * this library, written down from memory of Keras' OptimizerV2; it has not been checked against TensorFlow.)  clipvalue is applied
+ * as a float32 (the gradients' format), the two norm thresholds in double.  The sums of
+ * squares are accumulated in double, per block and then in block order (the same bits in every run), and stay on the device:
+ * the armed step gains no wait for the device. */
+int gnn_loop_set_clipping(gnn_loop *l, double clipvalue, double clipnorm, double global_clipnorm);
+/* For one optimizer step over SEVERAL loops (the LGNN joint step, reference GNN_BaseClass.py:244-247 over the variables of every
+ * layer) with a global norm that spans them:
+ *   gnn_loop_grad_sqnorm            after the backward pass: *sqnorm = sum of squares of this loop's gradients (both nets;
+ *                                   net_state's times state_grad_scale; after the loop's clipvalue), *penalty = the regularizer
+ *                                   penalty of both nets (either may be NULL).  Waits for the device.
+ *   gnn_loop_optimizer_step_scaled  gnn_loop_optimizer_step with every clipped gradient multiplied by grad_scale (> 0) in place
+ *                                   of the loop's own global_clipnorm: the caller's c / max(sqrt(sum of the loops' sqnorm), c). */
+int gnn_loop_grad_sqnorm(gnn_loop *l, float state_grad_scale, double *sqnorm, double *penalty);
+int gnn_loop_optimizer_step_scaled(gnn_loop *l, int kind, const float *hyper, float state_grad_scale, double grad_scale,
+                                   float bn_momentum_state, float bn_momentum_output);
 /* selects the implementation:
  *   0 = unfused reference kernels (one kernel per TF op), bit-identical to oracle/gnn_oracle.c;
  *   1 = fused gather + MLP kernel with the dense layers on the f32 MFMA: the same k-ordered fmaf chains, bit-identical
