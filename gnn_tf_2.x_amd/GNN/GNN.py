@@ -184,7 +184,8 @@ class GNNnodeBased(BaseClass):
     def training_step(self, g: GraphTensor, mean: bool, *, state0=None, masks_state=None, masks_output=None) -> dict:
         """One batch: device gradients (gnn_loop_train_step), net_state gradients divided by the iteration count when
         ``mean`` (reference GNN_BaseClass.py:241), optimizer update, BatchNormalization moving statistics.  L1L2 kernel / bias
-        regularizers and the optimizer's clipvalue / clipnorm / global_clipnorm are part of the device step.  Returns the raw
+        regularizers, the optimizer's clipvalue / clipnorm / global_clipnorm and the loss with its label_smoothing / delta
+        (``loss_arguments``) are part of the device step.  Returns the raw
         result of the device step (loss with the penalty, k, gradients with the regularizer terms) for inspection."""
         from GNN import losses
         if isinstance(g, GraphObject): g = GraphTensor.fromGraphObject(g)
@@ -195,6 +196,7 @@ class GNNnodeBased(BaseClass):
             raise ValueError('graph-based GNN needs set_mask and output_mask all True')
         loop = self._device_loop(g.device_graph(self.device))
         self._prepare_loop(g, loop)
+        loop.set_loss_params(*losses.device_loss_params(self.loss_function, self.loss_args))
         if self.state_vect_dim > 0:
             self.seed += 1
             loop.set_state0(state0, self.seed)

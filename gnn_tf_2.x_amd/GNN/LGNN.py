@@ -225,6 +225,7 @@ class LGNN(BaseClass):
         if self.optimizer is None or not hasattr(self.optimizer, 'apply_gradients'):
             raise TypeError('train() needs an optimizer with apply_gradients, e.g. GNN.optimizers.Adam()')
         kind = losses.device_loss_kind(self.loss_function, self.loss_args)
+        loss_params = losses.device_loss_params(self.loss_function, self.loss_args)
         graph_based = self.GNNS_TYPE == GNNgraphBased
         if graph_based and not g.loop_mask().all():
             raise ValueError('graph-based GNN needs set_mask and output_mask all True')
@@ -246,6 +247,7 @@ class LGNN(BaseClass):
         for idx, gnn in enumerate(self.gnns):
             loop = gnn._device_loop(current)
             if edge_based: gnn._prepare_loop(g, loop, own_labels=current is not base)
+            loop.set_loss_params(*loss_params)         # (the joint loss is taken below by the host helper; the loop's own setting agrees with it)
             if gnn.state_vect_dim > 0:
                 gnn.seed += 1
                 loop.set_state0(state0[idx], gnn.seed)
@@ -271,10 +273,10 @@ class LGNN(BaseClass):
                 current = nxt
         # ---- loss (reference LGNN.py:219-222) ----
         if self.training_mode == 'residual':
-            loss, d = _engine.loss_grad(kind, targets, np.mean(outs, axis=0, dtype=np.float32), weights)
+            loss, d = _engine.loss_grad(kind, targets, np.mean(outs, axis=0, dtype=np.float32), weights, *loss_params)
             d_outs = [d / L] * L
         else:
-            pairs = [_engine.loss_grad(kind, targets, o, weights) for o in outs]
+            pairs = [_engine.loss_grad(kind, targets, o, weights, *loss_params) for o in outs]
             loss = float(np.mean([p[0] for p in pairs]))
             d_outs = [p[1] / L for p in pairs]
         # kernel / bias regularizers that are L1L2 (or none) run on the device: every backward pass below then returns gradients that

@@ -20,6 +20,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_mlp_create', 'gnn_mlp_set_weights', 'gnn_mlp_get_weights', 'gnn_mlp_reset_optimizer', 'gnn_mlp_forward', 'gnn_mlp_destroy', 'gnn_loop_create',
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
+           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -47,13 +48,14 @@ def lib():
     return _lib
 
 
-def loss_grad(loss_kind: int, targets, out, sample_weights):
-    """gnn_loss_grad: (sum_i w_i L(t_i, out_i), d / d out) for loss_kind 0 categorical_crossentropy / 1 mean_squared_error."""
+def loss_grad(loss_kind: int, targets, out, sample_weights, label_smoothing: float = 0.0, huber_delta: float = 1.0):
+    """gnn_loss_grad_ex: (sum_i w_i L(t_i, out_i), d / d out) for the loss_kind codes of gnn_loop_train_step (GNN.losses.device_loss_kind)."""
     t, o, w = _f32(targets), _f32(out), _f32(sample_weights)
     if t.shape != o.shape or w.shape != (o.shape[0],): raise ValueError(f'targets {t.shape}, outputs {o.shape}, weights {w.shape} do not match')
     d = np.zeros_like(o)
     loss = C.c_double()
-    _check(lib().gnn_loss_grad(C.c_int(loss_kind), C.c_int64(o.shape[0]), C.c_int(o.shape[1]), _fp(t), _fp(o), _fp(w), C.byref(loss), _fp(d)))
+    _check(lib().gnn_loss_grad_ex(C.c_int(loss_kind), C.c_int64(o.shape[0]), C.c_int(o.shape[1]), _fp(t), _fp(o), _fp(w), C.c_double(label_smoothing),
+                                  C.c_double(huber_delta), C.byref(loss), _fp(d)))
     return float(loss.value), d
 
 
@@ -534,6 +536,13 @@ class Loop:
         if key != getattr(self, '_clip_set', (0.0, 0.0, 0.0)):
             _check(lib().gnn_loop_set_clipping(self._h, C.c_double(key[0]), C.c_double(key[1]), C.c_double(key[2])))
             self._clip_set = key
+
+    def set_loss_params(self, label_smoothing: float = 0.0, huber_delta: float = 1.0):
+        """gnn_loop_set_loss_params: label smoothing and Huber delta of the loss inside every later train_step() of this loop."""
+        key = (float(label_smoothing), float(huber_delta))
+        if key != getattr(self, '_loss_params_set', (0.0, 1.0)):
+            _check(lib().gnn_loop_set_loss_params(self._h, C.c_double(key[0]), C.c_double(key[1])))
+            self._loss_params_set = key
 
     def grad_sqnorm(self, state_grad_scale: float = 1.0):
         """gnn_loop_grad_sqnorm: (sum of squares of this loop's scaled and value-clipped gradients, regularizer penalty of both nets)."""

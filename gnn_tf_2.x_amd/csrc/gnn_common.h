@@ -222,6 +222,8 @@ struct gnn_mlp {
     // slots of the device-side optimizer (gnn_loop_optimizer_step), laid out like the gradient vector
     // (dW1, db1, ..., dgamma, dbeta); allocated on first use, zero at that point
     float *opt_a = nullptr, *opt_b = nullptr;
+    float *opt_c = nullptr;             // third slot, only for a kind that has one (Adam amsgrad, centered RMSprop)
+    int opt_kind = -1;                  // update rule that last wrote the slots; a step of another kind zeroes them first
     // L1 / L2 coefficients of the kernel / bias regularizers per array, [W1, b1, W2, b2, ...] (gnn_mlp_set_regularizers);
     // empty = none.  The training step adds their gradient and penalty on the device (gnn_train.hip: k_grad_prepare)
     std::vector<double> reg_l1, reg_l2;

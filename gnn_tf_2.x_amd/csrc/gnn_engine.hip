@@ -1103,8 +1103,9 @@ extern "C" int gnn_mlp_reset_optimizer(gnn_mlp *m)
     ARGCHK(m, "mlp is NULL");
     HIPCHK(hipSetDevice(m->device));
     HIPCHK(hipDeviceSynchronize());
-    (void)hipFree(m->opt_a); (void)hipFree(m->opt_b);
-    m->opt_a = nullptr; m->opt_b = nullptr;      // allocated and zeroed again by the next device-side optimizer step
+    (void)hipFree(m->opt_a); (void)hipFree(m->opt_b); (void)hipFree(m->opt_c);
+    m->opt_a = nullptr; m->opt_b = nullptr; m->opt_c = nullptr;      // allocated and zeroed again by the next device-side optimizer step
+    m->opt_kind = -1;
     return GNN_OK;
 }
 
@@ -1149,7 +1150,7 @@ extern "C" int gnn_mlp_destroy(gnn_mlp *m)
     (void)hipSetDevice(m->device);
     (void)hipFree(m->slab);
     (void)hipFree(m->bn_scale); (void)hipFree(m->bn_shift); (void)hipFree(m->bn_raw);
-    (void)hipFree(m->opt_a); (void)hipFree(m->opt_b);
+    (void)hipFree(m->opt_a); (void)hipFree(m->opt_b); (void)hipFree(m->opt_c);
     gnn_fused_release(m);
     delete m;
     return GNN_OK;

@@ -2010,6 +2010,8 @@ struct TrainArena {
     struct { bool armed = false; int kind = 0; float h[4] = {0, 0, 0, 0}; bool mean = false; float mom_s = 0.99f, mom_o = 0.99f; } opt;
     // gradient clipping of every optimizer update of this loop (gnn_loop_set_clipping); 0 = off
     struct { float value = 0.0f; double norm = 0.0, global = 0.0; } clip;
+    // parameters of the loss inside gnn_loop_train_step (gnn_loop_set_loss_params)
+    struct { double smoothing = 0.0, delta = 1.0; } lossp;
     // pinned host words for the results the host waits for (iteration gates, loss partials)
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -2431,90 +2433,96 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
     return GNN_OK;
 }
 
+// One target row of the loss: returns w L(t, o) and writes d / d o [T], arithmetic in double.  `smooth` is label_smoothing (applied to
+// the targets first: t <- t (1 - s) + s / T for the categorical kinds, + s / 2 for the binary ones), `delta` the Huber threshold.
+//   0 categorical_crossentropy (probabilities, renormalised, clipped to [1e-7, 1 - 1e-7]: no gradient where clipped)
+//   1 mean_squared_error        2 categorical_crossentropy(from_logits=True): softmax inside the loss, no clipping
+//   3 binary_crossentropy (probabilities, clipped like 0)       4 binary_crossentropy(from_logits=True)
+//   5 mean_absolute_error (sign(0) = 0)                          6 huber (quadratic up to and including |e| = delta)
+enum { LOSS_KINDS = 7 };
+#define LOSS_KIND_TEXT "loss_kind: 0 categorical_crossentropy, 1 mean_squared_error, 2 categorical_crossentropy(from_logits=True), 3 binary_crossentropy, " \
+                       "4 binary_crossentropy(from_logits=True), 5 mean_absolute_error, 6 huber"
+
+__host__ __device__ inline double loss_row(int kind, int T, const float *ti, const float *oi, double wi, double smooth, double delta, float *d)
+{
+    const double keep = 1.0 - smooth, add = (kind == 3 || kind == 4) ? smooth / 2 : smooth / T;
+    double li = 0.0;
+    if (kind == 0) {
+        double s = 0.0, gp = 0.0;
+        for (int j = 0; j < T; ++j) s += oi[j];
+        for (int j = 0; j < T; ++j) {
+            const double tj = ti[j] * keep + add, pj = oi[j] / s;
+            const bool in = pj >= 1e-7 && pj <= 1.0 - 1e-7;
+            const double pc = fmin(fmax(pj, 1e-7), 1.0 - 1e-7);
+            li -= tj * log(pc);
+            gp += (in ? -tj / pc : 0.0) * pj;
+        }
+        for (int j = 0; j < T; ++j) {
+            const double tj = ti[j] * keep + add, pj = oi[j] / s;
+            const bool in = pj >= 1e-7 && pj <= 1.0 - 1e-7;
+            const double pc = fmin(fmax(pj, 1e-7), 1.0 - 1e-7);
+            d[j] = (float)(wi * ((in ? -tj / pc : 0.0) - gp) / s);
+        }
+        return wi * li;
+    }
+    if (kind == 2) {
+        double mx = oi[0], s = 0.0, st = 0.0;
+        for (int j = 1; j < T; ++j) mx = fmax(mx, (double)oi[j]);
+        for (int j = 0; j < T; ++j) { s += exp(oi[j] - mx); st += ti[j] * keep + add; }
+        for (int j = 0; j < T; ++j) {
+            const double tj = ti[j] * keep + add, logp = (oi[j] - mx) - log(s);
+            li -= tj * logp;
+            d[j] = (float)(wi * (exp(logp) * st - tj));
+        }
+        return wi * li;
+    }
+    for (int j = 0; j < T; ++j) {
+        const double o = oi[j];
+        if (kind == 3) {
+            const double tj = ti[j] * keep + add;
+            const bool in = o >= 1e-7 && o <= 1.0 - 1e-7;
+            const double pc = fmin(fmax(o, 1e-7), 1.0 - 1e-7);
+            li -= tj * log(pc) + (1.0 - tj) * log(1.0 - pc);
+            d[j] = (float)(in ? wi * ((1.0 - tj) / (1.0 - pc) - tj / pc) / T : 0.0);
+        } else if (kind == 4) {
+            const double tj = ti[j] * keep + add, en = exp(-fabs(o));
+            li += fmax(o, 0.0) - o * tj + log1p(en);
+            const double sig = o >= 0.0 ? 1.0 / (1.0 + en) : en / (1.0 + en);
+            d[j] = (float)(wi * (sig - tj) / T);
+        } else if (kind == 5) {
+            const double e = o - ti[j];
+            li += fabs(e);
+            d[j] = (float)(wi * (e > 0.0 ? 1.0 : e < 0.0 ? -1.0 : 0.0) / T);
+        } else if (kind == 6) {
+            const double e = o - ti[j], ae = fabs(e);
+            li += ae <= delta ? 0.5 * e * e : delta * (ae - 0.5 * delta);
+            d[j] = (float)(wi * (ae <= delta ? e : (e > 0.0 ? delta : -delta)) / T);
+        } else {
+            const double e = o - ti[j];
+            li += e * e;
+            d[j] = (float)(wi * 2.0 * e / T);
+        }
+    }
+    return wi * li / T;
+}
+
 // host side of the loss (rows are few): sum_i w_i L(t_i, o_i) and d / d o
-void loss_host(int kind, int64_t n, int T, const float *t, const float *o, const float *w, double *loss, std::vector<float> &d_o)
+void loss_host(int kind, int64_t n, int T, const float *t, const float *o, const float *w, double smooth, double delta, double *loss, std::vector<float> &d_o)
 {
     d_o.assign((size_t)n * T, 0.0f);
     double total = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-        const float *ti = t + i * T, *oi = o + i * T;
-        if (kind == 0) {                           // categorical_crossentropy, from_logits=False
-            double s = 0.0;
-            for (int j = 0; j < T; ++j) s += oi[j];
-            std::vector<double> p(T), g(T);
-            double li = 0.0, gp = 0.0;
-            for (int j = 0; j < T; ++j) {
-                p[j] = oi[j] / s;
-                const bool in = p[j] >= 1e-7 && p[j] <= 1.0 - 1e-7;
-                const double pc = std::min(std::max(p[j], 1e-7), 1.0 - 1e-7);
-                li -= ti[j] * log(pc);
-                g[j] = in ? -ti[j] / pc : 0.0;
-                gp += g[j] * p[j];
-            }
-            for (int j = 0; j < T; ++j) d_o[i * T + j] = (float)(w[i] * (g[j] - gp) / s);
-            total += w[i] * li;
-        } else if (kind == 2) {                    // categorical_crossentropy, from_logits=True: softmax inside the loss, no clipping
-            double mx = oi[0], s = 0.0, st = 0.0, li = 0.0;
-            for (int j = 1; j < T; ++j) mx = std::max(mx, (double)oi[j]);
-            for (int j = 0; j < T; ++j) { s += exp(oi[j] - mx); st += ti[j]; }
-            for (int j = 0; j < T; ++j) {
-                const double logp = (oi[j] - mx) - log(s);
-                li -= ti[j] * logp;
-                d_o[i * T + j] = (float)(w[i] * (exp(logp) * st - ti[j]));
-            }
-            total += w[i] * li;
-        } else {                                   // mean_squared_error
-            double li = 0.0;
-            for (int j = 0; j < T; ++j) { const double e = (double)oi[j] - ti[j]; li += e * e; d_o[i * T + j] = (float)(w[i] * 2.0 * e / T); }
-            total += w[i] * li / T;
-        }
-    }
+    for (int64_t i = 0; i < n; ++i) total += loss_row(kind, T, t + i * T, o + i * T, w[i], smooth, delta, d_o.data() + i * T);
     *loss = total;
 }
 
 // The same on the device, one thread per target row: d_o [n, T] and, per block of 256 rows, the sum of w_i L_i (fixed tree, double)
-__global__ void __launch_bounds__(256) k_loss_rows(int kind, int64_t n, int T, const float *t, const float *o, const float *w, float *d_o, double *loss_part)
+__global__ void __launch_bounds__(256) k_loss_rows(int kind, int64_t n, int T, const float *t, const float *o, const float *w, double smooth, double delta,
+                                                   float *d_o, double *loss_part)
 {
     __shared__ double sl[256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double lw = 0.0;
-    if (i < n) {
-        const float *ti = t + i * T, *oi = o + i * T;
-        const double wi = w[i];
-        if (kind == 0) {
-            double s = 0.0;
-            for (int j = 0; j < T; ++j) s += oi[j];
-            double li = 0.0, gp = 0.0;
-            for (int j = 0; j < T; ++j) {
-                const double pj = oi[j] / s;
-                const bool in = pj >= 1e-7 && pj <= 1.0 - 1e-7;
-                const double pc = fmin(fmax(pj, 1e-7), 1.0 - 1e-7);
-                li -= ti[j] * log(pc);
-                gp += (in ? -ti[j] / pc : 0.0) * pj;
-            }
-            for (int j = 0; j < T; ++j) {
-                const double pj = oi[j] / s;
-                const bool in = pj >= 1e-7 && pj <= 1.0 - 1e-7;
-                const double pc = fmin(fmax(pj, 1e-7), 1.0 - 1e-7);
-                d_o[i * T + j] = (float)(wi * ((in ? -ti[j] / pc : 0.0) - gp) / s);
-            }
-            lw = wi * li;
-        } else if (kind == 2) {
-            double mx = oi[0], s = 0.0, st = 0.0, li = 0.0;
-            for (int j = 1; j < T; ++j) mx = fmax(mx, (double)oi[j]);
-            for (int j = 0; j < T; ++j) { s += exp(oi[j] - mx); st += ti[j]; }
-            for (int j = 0; j < T; ++j) {
-                const double logp = (oi[j] - mx) - log(s);
-                li -= ti[j] * logp;
-                d_o[i * T + j] = (float)(wi * (exp(logp) * st - ti[j]));
-            }
-            lw = wi * li;
-        } else {
-            double li = 0.0;
-            for (int j = 0; j < T; ++j) { const double e = (double)oi[j] - ti[j]; li += e * e; d_o[i * T + j] = (float)(wi * 2.0 * e / T); }
-            lw = wi * li / T;
-        }
-    }
+    if (i < n) lw = loss_row(kind, T, t + i * T, o + i * T, w[i], smooth, delta, d_o + i * T);
     sl[threadIdx.x] = lw;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
@@ -2858,17 +2866,24 @@ int clip_prepare(gnn_loop *l, TrainCtx *cx, hipStream_t st, float gscale_state, 
 }
 }   // namespace
 
-extern "C" int gnn_loss_grad(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out, const float *sample_weights,
-                             double *loss, float *d_out)
+extern "C" int gnn_loss_grad_ex(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out, const float *sample_weights,
+                                double label_smoothing, double huber_delta, double *loss, float *d_out)
 {
     ARGCHK((n_rows == 0 || (targets && out && sample_weights)) && loss && n_out > 0 && n_rows >= 0, "bad arguments");
-    ARGCHK(loss_kind >= 0 && loss_kind <= 2, "loss_kind: 0 categorical_crossentropy, 1 mean_squared_error, 2 categorical_crossentropy(from_logits=True)");
+    ARGCHK(loss_kind >= 0 && loss_kind < LOSS_KINDS, LOSS_KIND_TEXT);
+    ARGCHK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "label_smoothing must lie in [0, 1]");
+    ARGCHK(std::isfinite(huber_delta) && huber_delta > 0.0, "huber_delta must be finite and > 0");
     std::vector<float> d;
-    loss_host(loss_kind, n_rows, n_out, targets, out, sample_weights, loss, d);
+    loss_host(loss_kind, n_rows, n_out, targets, out, sample_weights, label_smoothing, huber_delta, loss, d);
     if (d_out && n_rows) memcpy(d_out, d.data(), sizeof(float) * d.size());
     return GNN_OK;
 }
 
+extern "C" int gnn_loss_grad(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out, const float *sample_weights,
+                             double *loss, float *d_out)
+{
+    return gnn_loss_grad_ex(loss_kind, n_rows, n_out, targets, out, sample_weights, 0.0, 1.0, loss, d_out);
+}
 
 // Training-mode Loop.  final_sync: wait for the published state / outputs (and out_nodes_host) before returning.
 // owned rows [n_rows, Ds] -> a fresh replica [N_pad, Ds] with the rows of all ranks (all-gather in place); sharded training only
@@ -3283,10 +3298,20 @@ extern "C" int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, co
 namespace {
 // kind 0, SGD: h = {learning rate, momentum}: v <- momentum v - lr g, p <- p + v
 // kind 1, Adam (Keras): h = {lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), b1, b2, epsilon}: m, v updated, p <- p - lr_t m / (sqrt(v) + epsilon)
+//   (h[2] != 0: Nesterov momentum, p <- p + momentum v - lr g with the new v)
+// kind 2, Adam with amsgrad: h as kind 1; m, v as Adam, vhat <- max(vhat, v) (slot c), p <- p - lr_t m / (sqrt(vhat) + epsilon)
+// kind 3, RMSprop: h = {lr, rho, momentum, epsilon}: r <- rho r + (1 - rho) g^2 (slot a); momentum == 0: p <- p - lr g / (sqrt(r) + epsilon);
+//         momentum > 0: q <- momentum q + lr g / sqrt(r + epsilon) (slot b), p <- p - q
+// kind 4, centered RMSprop: also a <- rho a + (1 - rho) g (slot c), and max(r - a^2, 0) in place of r in both branches (r - a^2 cancels
+//         in float32 and may come out below zero: the clamp is part of the rule)
+// kind 5, Adagrad: h = {lr, initial_accumulator_value, epsilon}: s <- s + g^2 (slot a, from zero), p <- p - lr g / (sqrt(initial + s) + epsilon)
+// kind 6, Adamax: h = {lr / (1 - b1^t), b1, b2, epsilon}: m <- b1 m + (1 - b1) g (slot a), u <- max(b2 u, |g|) (slot b), p <- p - h0 m / (u + epsilon)
 // CLIP: the scaled gradient is clipped by value and multiplied by its array's factor (k_clip_factors) first
+enum { OPT_SGD = 0, OPT_ADAM = 1, OPT_AMSGRAD = 2, OPT_RMSPROP = 3, OPT_RMSPROP_CENTERED = 4, OPT_ADAGRAD = 5, OPT_ADAMAX = 6, OPT_KINDS = 7 };
+
 template <bool CLIP>
-__global__ void k_optimizer(ParamMap mp, const float *g, float gscale, float clipvalue, const float *factor, float *sa, float *sb, int kind, float h0,
-                            float h1, float h2, float h3)
+__global__ void k_optimizer(ParamMap mp, const float *g, float gscale, float clipvalue, const float *factor, float *sa, float *sb, float *sc, int kind,
+                            float h0, float h1, float h2, float h3)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= mp.goff[mp.n]) return;
@@ -3295,16 +3320,55 @@ __global__ void k_optimizer(ParamMap mp, const float *g, float gscale, float cli
     float *p = mp.p[a] + (j - mp.goff[a]);
     float gr = g[j] * gscale;
     if (CLIP) gr = clip_value(gr, clipvalue) * factor[a];
-    if (kind == 1) {
+    if (kind == OPT_ADAM || kind == OPT_AMSGRAD) {
         const float m = h1 * sa[j] + (1.0f - h1) * gr;
         const float v = h2 * sb[j] + (1.0f - h2) * gr * gr;
         sa[j] = m; sb[j] = v;
-        *p = *p - h0 * m / (sqrtf(v) + h3);
+        float den = v;
+        if (kind == OPT_AMSGRAD) { den = fmaxf(sc[j], v); sc[j] = den; }
+        *p = *p - h0 * m / (sqrtf(den) + h3);
+    } else if (kind == OPT_RMSPROP || kind == OPT_RMSPROP_CENTERED) {
+        const float r = h1 * sa[j] + (1.0f - h1) * gr * gr;
+        sa[j] = r;
+        float den = r;
+        if (kind == OPT_RMSPROP_CENTERED) {
+            const float mean = h1 * sc[j] + (1.0f - h1) * gr;
+            sc[j] = mean;
+            den = fmaxf(r - mean * mean, 0.0f);
+        }
+        if (h2 > 0.0f) {
+            const float q = h2 * sb[j] + h0 * gr / sqrtf(den + h3);
+            sb[j] = q;
+            *p = *p - q;
+        } else
+            *p = *p - h0 * gr / (sqrtf(den) + h3);
+    } else if (kind == OPT_ADAGRAD) {
+        const float s = sa[j] + gr * gr;
+        sa[j] = s;
+        *p = *p - h0 * gr / (sqrtf(h1 + s) + h2);
+    } else if (kind == OPT_ADAMAX) {
+        const float m = h1 * sa[j] + (1.0f - h1) * gr;
+        const float u = fmaxf(h2 * sb[j], fabsf(gr));
+        sa[j] = m; sb[j] = u;
+        *p = *p - h0 * m / (u + h3);
     } else {
         const float v = h1 * sa[j] - h0 * gr;
         sa[j] = v;
-        *p = *p + v;
+        *p = h2 != 0.0f ? *p + (h1 * v - h0 * gr) : *p + v;
     }
+}
+
+// what optimizer_step / gnn_loop_arm_optimizer accept: a known kind, and a finite value >= 0 wherever a new rule divides by it
+// (kinds 0 and 1 take their hyper-parameters as they always did)
+const char *optimizer_args_error(int kind, const float *h)
+{
+    if (kind < 0 || kind >= OPT_KINDS)
+        return "kind: 0 SGD, 1 Adam, 2 Adam(amsgrad), 3 RMSprop, 4 RMSprop(centered), 5 Adagrad, 6 Adamax";
+    auto ok = [](float v) { return std::isfinite(v) && v >= 0.0f; };
+    if ((kind == OPT_AMSGRAD || kind == OPT_ADAMAX) && !ok(h[3])) return "epsilon must be finite and >= 0";
+    if ((kind == OPT_RMSPROP || kind == OPT_RMSPROP_CENTERED) && !(ok(h[3]) && ok(h[2]))) return "RMSprop: momentum and epsilon must be finite and >= 0";
+    if (kind == OPT_ADAGRAD && !(ok(h[1]) && ok(h[2]))) return "Adagrad: initial_accumulator_value and epsilon must be finite and >= 0";
+    return nullptr;
 }
 
 // moving <- moving * momentum + batch * (1 - momentum), once per BatchNormalization call, in call order
@@ -3330,14 +3394,26 @@ int optimizer_apply(hipStream_t st, gnn_mlp *m, const Net &net, int calls, int k
             return gnn_fail(GNN_ERR_HIP, "hipMalloc of the optimizer slots failed");
         HIPCHK(hipMemsetAsync(m->opt_a, 0, sizeof(float) * total, st));
         HIPCHK(hipMemsetAsync(m->opt_b, 0, sizeof(float) * total, st));
+        m->opt_kind = kind;
+    }
+    const bool third = kind == OPT_AMSGRAD || kind == OPT_RMSPROP_CENTERED;
+    if (m->opt_kind != kind) {                     // another rule wrote these slots: it starts from zero, like a new optimizer
+        HIPCHK(hipMemsetAsync(m->opt_a, 0, sizeof(float) * total, st));
+        HIPCHK(hipMemsetAsync(m->opt_b, 0, sizeof(float) * total, st));
+        if (m->opt_c && third) HIPCHK(hipMemsetAsync(m->opt_c, 0, sizeof(float) * total, st));
+        m->opt_kind = kind;
+    }
+    if (third && !m->opt_c) {
+        if (gnn_dev_malloc((void **)&m->opt_c, sizeof(float) * total) != hipSuccess) return gnn_fail(GNN_ERR_HIP, "hipMalloc of the optimizer slots failed");
+        HIPCHK(hipMemsetAsync(m->opt_c, 0, sizeof(float) * total, st));
     }
     const ParamMap mp = param_map(m, net);
     if (factor)
-        hipLaunchKernelGGL(k_optimizer<true>, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, clipvalue, factor, m->opt_a, m->opt_b, kind, h[0],
-                           h[1], h[2], h[3]);
+        hipLaunchKernelGGL(k_optimizer<true>, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, clipvalue, factor, m->opt_a, m->opt_b, m->opt_c, kind,
+                           h[0], h[1], h[2], h[3]);
     else
-        hipLaunchKernelGGL(k_optimizer<false>, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, 0.0f, nullptr, m->opt_a, m->opt_b, kind, h[0],
-                           h[1], h[2], h[3]);
+        hipLaunchKernelGGL(k_optimizer<false>, cdiv((int64_t)total, 256), 256, 0, st, mp, net.grads, gscale, 0.0f, nullptr, m->opt_a, m->opt_b, m->opt_c, kind,
+                           h[0], h[1], h[2], h[3]);
     HIPCHK(hipGetLastError());
     if (m->has_bn) {
         const int F = m->dims.back();
@@ -3367,7 +3443,8 @@ int update_both(gnn_loop *l, TrainCtx *cx, hipStream_t st, int kind, const float
 
 int optimizer_step(gnn_loop *l, int kind, const float *hyper, float state_grad_scale, float bn_momentum_state, float bn_momentum_output, bool own_global, double extra)
 {
-    ARGCHK(l && hyper && (kind == 0 || kind == 1), "bad arguments (kind: 0 SGD, 1 Adam)");
+    ARGCHK(l && hyper, "bad arguments");
+    if (const char *why = optimizer_args_error(kind, hyper)) return gnn_fail(GNN_ERR_ARG, "%s", why);
     TrainCtx *cx = static_cast<TrainCtx *>(l->train_ctx);
     if (!cx || !cx->backward_done || cx->applied) return gnn_fail(GNN_ERR_STATE, "no fresh gradients: run gnn_loop_train_step (or forward + backward) first");
     ARGCHK(l->st->n_layers <= 16 && l->ou->n_layers <= 16, "too many layers");
@@ -3403,6 +3480,17 @@ extern "C" int gnn_loop_set_clipping(gnn_loop *l, double clipvalue, double clipn
     if (!l->train_arena) l->train_arena = new TrainArena();
     TrainArena *arena = static_cast<TrainArena *>(l->train_arena);
     arena->clip.value = (float)clipvalue; arena->clip.norm = clipnorm; arena->clip.global = global_clipnorm;
+    return GNN_OK;
+}
+
+extern "C" int gnn_loop_set_loss_params(gnn_loop *l, double label_smoothing, double huber_delta)
+{
+    ARGCHK(l, "loop is NULL");
+    ARGCHK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "label_smoothing must lie in [0, 1]");
+    ARGCHK(std::isfinite(huber_delta) && huber_delta > 0.0, "huber_delta must be finite and > 0");
+    if (!l->train_arena) l->train_arena = new TrainArena();
+    TrainArena *arena = static_cast<TrainArena *>(l->train_arena);
+    arena->lossp.smoothing = label_smoothing; arena->lossp.delta = huber_delta;
     return GNN_OK;
 }
 
@@ -3456,7 +3544,8 @@ extern "C" int gnn_loop_update_moving_statistics(gnn_loop *l, float bn_momentum_
 
 extern "C" int gnn_loop_arm_optimizer(gnn_loop *l, int kind, const float *hyper, int mean, float bn_momentum_state, float bn_momentum_output)
 {
-    ARGCHK(l && hyper && (kind == 0 || kind == 1), "bad arguments (kind: 0 SGD, 1 Adam)");
+    ARGCHK(l && hyper, "bad arguments");
+    if (const char *why = optimizer_args_error(kind, hyper)) return gnn_fail(GNN_ERR_ARG, "%s", why);
     ARGCHK(l->st->n_layers <= 16 && l->ou->n_layers <= 16, "too many layers");
     if (!l->train_arena) l->train_arena = new TrainArena();
     TrainArena *arena = static_cast<TrainArena *>(l->train_arena);
@@ -3476,7 +3565,7 @@ extern "C" int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const
 {
     ARGCHK(l && targets && sample_weights && loss_out && k_out && grads_state && grads_output, "bad arguments");
     ARGCHK(l->world == 1, "a training step is single-GPU (only the training-mode forward runs on shards: gnn_loop_train_forward)");
-    ARGCHK(loss_kind >= 0 && loss_kind <= 2, "loss_kind: 0 categorical_crossentropy, 1 mean_squared_error, 2 categorical_crossentropy(from_logits=True)");
+    ARGCHK(loss_kind >= 0 && loss_kind < LOSS_KINDS, LOSS_KIND_TEXT);
     const int64_t M = l->edge_mode ? l->n_edge_masked : l->g->n_masked;
     const int T = l->T;
     ARGCHK(!(l->edge_mode && n_graphs > 0), "an edge-based loop has no graph readout");
@@ -3525,11 +3614,11 @@ extern "C" int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const
         if ((rc = buf.get(&og, (size_t)n_graphs * T)) || (rc = buf.get(&d_dnodes, (size_t)M * T))) return rc;
         HIPCHK(hipMemsetAsync(d_dnodes, 0, sizeof(float) * std::max<size_t>(1, (size_t)M * T), st));
         hipLaunchKernelGGL(k_graph_out, cdiv(n_graphs, 4), 256, 0, st, n_graphs, T, d_ip, d_nd, d_nw, cx->out_nodes, og);
-        hipLaunchKernelGGL(k_loss_rows, lblocks, 256, 0, st, loss_kind, nt, T, d_t, og, d_w, d_o, d_lp);
+        hipLaunchKernelGGL(k_loss_rows, lblocks, 256, 0, st, loss_kind, nt, T, d_t, og, d_w, arena->lossp.smoothing, arena->lossp.delta, d_o, d_lp);
         if (ne) hipLaunchKernelGGL(k_graph_out_bwd, cdiv(ne * T, 256), 256, 0, st, n_graphs, T, d_ip, d_nd, d_nw, d_o, d_dnodes);
         HIPCHK(hipGetLastError());
     } else if (nt) {
-        hipLaunchKernelGGL(k_loss_rows, lblocks, 256, 0, st, loss_kind, nt, T, d_t, cx->out_nodes, d_w, d_o, d_lp);
+        hipLaunchKernelGGL(k_loss_rows, lblocks, 256, 0, st, loss_kind, nt, T, d_t, cx->out_nodes, d_w, arena->lossp.smoothing, arena->lossp.delta, d_o, d_lp);
         HIPCHK(hipGetLastError());
         d_dnodes = d_o;
     }

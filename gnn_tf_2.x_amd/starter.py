@@ -71,6 +71,7 @@ get_state: bool = False
 get_output: bool = True
 path_writer: str = 'writer/'
 optimizer = optimizers.Adam(learning_rate=0.001)
+# optimizer = optimizers.RMSprop(learning_rate=optimizers.schedules.ExponentialDecay(0.001, decay_steps=1000, decay_rate=0.9))   # any optimizer takes a schedule
 lossF = losses.categorical_crossentropy
 lossArguments: Optional[dict] = {'from_logits': False}
 extra_metrics: Optional[dict] = {i: mt.Metrics[i] for i in ['Acc', 'Bacc', 'Tpr', 'Tnr', 'Fpr', 'Fnr', 'Ck', 'Js', 'Prec', 'Rec', 'Fs']}

@@ -159,6 +159,11 @@ int gnn_loop_set_edge_readout(gnn_loop *l, const int32_t *entry_dst, const float
  *                    aggregation of the backward pass; all NULL = derived from the graph's own CSR on first use and kept
  *   targets, sample_weights, n_targets   rows = masked nodes (node-based) or graphs (graph-based); loss_kind 0 =
  *                    categorical_crossentropy(from_logits=False), 1 = mean_squared_error, 2 = categorical_crossentropy(from_logits=True)
+ *                    3 = binary_crossentropy (probabilities p clipped to [1e-7, 1 - 1e-7], L = mean_j -(t log p + (1 - t) log(1 - p)), no
+ *                    gradient where p was clipped, as kind 0), 4 = binary_crossentropy(from_logits=True) (L = mean_j max(z, 0) - z t +
+ *                    log(1 + exp(-|z|)), d = (sigmoid(z) - t) / T), 5 = mean_absolute_error (d = sign(o - t) / T, sign(0) = 0),
+ *                    6 = huber (e = o - t: mean_j of e^2 / 2 where |e| <= delta, delta (|e| - delta / 2) beyond); label smoothing and
+ *                    delta: gnn_loop_set_loss_params
  *   n_graphs, ng_*   NodeGraph^T in CSR form (as gnn_loop_readout) for GNNgraphBased, n_graphs = 0 otherwise
  *   dropout_state / dropout_output   [n_layers + 1] Dropout rate in front of Dense l (0 = none; last entry: in front of
  *                    BatchNormalization), i.e. GNN/MLP.py:54-55 after its position shift; a NEGATIVE value -r is an AlphaDropout
@@ -197,7 +202,8 @@ int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const int32_t *s
  *                    sums of BatchNormalization's backward pass are those of all ranks, and the ranks' shares of the weight
  *                    gradients are added in rank order - every rank returns the same, complete gradients.  gnn_loop_train_step (one
  *                    call with the loss inside) stays single-GPU.
- *   gnn_loss_grad    host helper: *loss = sum_i w_i L(t_i, out_i) and d_out = d loss / d out (may be NULL). */
+ *   gnn_loss_grad    host helper: *loss = sum_i w_i L(t_i, out_i) and d_out = d loss / d out (may be NULL), every loss_kind of
+ *                    gnn_loop_train_step with label_smoothing 0 and huber_delta 1; gnn_loss_grad_ex takes the two as arguments. */
 int gnn_loop_train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w,
                            const float *dropout_state, const float *dropout_output, const uint8_t *masks_state,
                            const uint8_t *masks_output, uint64_t seed, const float *bn_state, const float *bn_output,
@@ -207,8 +213,27 @@ int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, const float *
                             float *d_arc_labels);
 /* Optimizer step on the device (reference GNN_BaseClass.py:243-247, optimizer.apply_gradients on the trainable variables of
  * both nets, and the moving statistics Keras BatchNormalization updates in training mode): weights, optimizer slots (kept with
- * the gnn_mlp) and gradients stay in HBM.  kind 0 = SGD, hyper = {learning_rate, momentum, -, -}; kind 1 = Adam, hyper =
- * {lr_t = lr sqrt(1 - beta_2^t) / (1 - beta_1^t), beta_1, beta_2, epsilon} (the caller counts t).
+ * the gnn_mlp) and gradients stay in HBM.  hyper is always four floats; per entry, in float32, on the gradient g after the
+ * regularizer terms, the division by k and the clipping:
+ *   kind 0 SGD              {learning_rate, momentum, nesterov (0 / 1), -}: v <- momentum v - lr g; p <- p + v, or with nesterov
+ *                           p <- p + momentum v - lr g
+ *   kind 1 Adam             {lr_t = lr sqrt(1 - beta_2^t) / (1 - beta_1^t), beta_1, beta_2, epsilon} (the caller counts t):
+ *                           m <- beta_1 m + (1 - beta_1) g, v <- beta_2 v + (1 - beta_2) g^2, p <- p - lr_t m / (sqrt(v) + epsilon)
+ *   kind 2 Adam, amsgrad    as kind 1, with vhat <- max(vhat, v) in place of v in the denominator
+ *   kind 3 RMSprop          {learning_rate, rho, momentum, epsilon}: r <- rho r + (1 - rho) g^2; momentum == 0:
+ *                           p <- p - lr g / (sqrt(r) + epsilon); momentum > 0: q <- momentum q + lr g / sqrt(r + epsilon), p <- p - q
+ *   kind 4 RMSprop, centered  also a <- rho a + (1 - rho) g, and max(r - a^2, 0) in place of r in both branches (the difference
+ *                           cancels in float32: the clamp is part of the rule)
+ *   kind 5 Adagrad          {learning_rate, initial_accumulator_value, epsilon, -}: s <- s + g^2 (s starts at 0),
+ *                           p <- p - lr g / (sqrt(initial_accumulator_value + s) + epsilon)
+ *   kind 6 Adamax           {learning_rate / (1 - beta_1^t), beta_1, beta_2, epsilon}: m <- beta_1 m + (1 - beta_1) g,
+ *                           u <- max(beta_2 u, |g|), p <- p - hyper[0] m / (u + epsilon)
+ * Any other kind is GNN_ERR_ARG, and so is, for kinds 2 - 6, a negative or non-finite value where the rule divides by it (epsilon,
+ * RMSprop's momentum, Adagrad's initial_accumulator_value).  These rules - the two places of RMSprop's epsilon among them - are
+ * definitions of this library, written down from memory of tf.keras 2.x; they have not been checked against TensorFlow.
+ * Slots: every net has up to three arrays laid out like its gradient vector, the third only once a kind that uses it (2, 4) has
+ * run.  All slots start at zero, and a step whose kind differs from the kind that last wrote a net's slots restarts them from zero
+ * (gnn_mlp_reset_optimizer does the same for a new optimizer object of the same kind).
  *   gnn_loop_arm_optimizer   one-shot: the NEXT gnn_loop_train_step applies the update behind its backward pass, before the
  *                            step's single wait for the device; mean != 0 divides the net_state gradients by the iteration
  *                            count (GNN_BaseClass.py:241).  The gradients returned by that step are the raw ones.
@@ -225,6 +250,13 @@ int gnn_loop_optimizer_step(gnn_loop *l, int kind, const float *hyper, float sta
                             float bn_momentum_output);
 int gnn_loss_grad(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out,
                   const float *sample_weights, double *loss, float *d_out);
+int gnn_loss_grad_ex(int loss_kind, int64_t n_rows, int n_out, const float *targets, const float *out,
+                     const float *sample_weights, double label_smoothing, double huber_delta, double *loss, float *d_out);
+/* Parameters of the loss inside gnn_loop_train_step, sticky per loop like gnn_loop_set_clipping (defaults 0 and 1).
+ * label_smoothing s in [0, 1], applied to the targets before anything else: t <- t (1 - s) + s / T for loss_kind 0 and 2,
+ * t <- t (1 - s) + s / 2 for 3 and 4, ignored by the others.  huber_delta > 0 and finite: the threshold of loss_kind 6.  A value
+ * outside these ranges is GNN_ERR_ARG and leaves the setting as it was. */
+int gnn_loop_set_loss_params(gnn_loop *l, double label_smoothing, double huber_delta);
 /* Kernel / bias regularizers on the device (reference starter.py:55-66 hands them to MLP(), GNN/MLP.py:11-13; their penalties are
  * summed into the taped loss, GNN_BaseClass.py:223-235).  l1 / l2: [2 n_layers] coefficients per array in [W1, b1, W2, b2, ...]
  * order (BatchNormalization's gamma / beta never carry one); both NULL clears them; a negative or non-finite coefficient is
