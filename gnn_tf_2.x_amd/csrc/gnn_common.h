@@ -168,7 +168,7 @@ struct gnn_graph_shared {
     uint8_t *mask = nullptr;
     int max_degree = 0;
     // Adjacency as CSR over SOURCE nodes (destinations ascending): operand of the transposed aggregation of the backward
-    // pass; built on first use by gnn_train.hip when the caller passes no by-source arrays
+    // pass; built on first use by gnn_train.hip (graph_by_source) when the caller passes no by-source arrays
     int32_t *src_indptr = nullptr, *src_dst = nullptr;
     float *src_w = nullptr;
     // arc-side LGNN relabelling (LGNN.py:253-254): arc id of every ArcNode^T entry and the arc labels in ORIGINAL arc order
@@ -225,7 +225,7 @@ struct gnn_mlp {
     float *opt_c = nullptr;             // third slot, only for a kind that has one (Adam amsgrad, centered RMSprop)
     int opt_kind = -1;                  // update rule that last wrote the slots; a step of another kind zeroes them first
     // L1 / L2 coefficients of the kernel / bias regularizers per array, [W1, b1, W2, b2, ...] (gnn_mlp_set_regularizers);
-    // empty = none.  The training step adds their gradient and penalty on the device (gnn_train.hip: k_grad_prepare)
+    // empty = none.  The training step adds their gradient and penalty on the device (gnn_train_update.hip: k_grad_prepare)
     std::vector<double> reg_l1, reg_l2;
     bool has_bn = false;
     float eps = 1e-3f;
@@ -262,6 +262,21 @@ struct gnn_comm {
     int loops = 0;
     bool closed = false;
 };
+
+// The training settings of a loop: they stay from step to step until they are set again.
+struct gnn_train_settings {
+    // optimizer armed for the next gnn_loop_train_step (gnn_loop_arm_optimizer), which consumes `armed`: applied behind the backward pass,
+    // before the step's only wait for the device
+    struct { bool armed = false; int kind = 0; float h[4] = {0, 0, 0, 0}; bool mean = false; float mom_s = 0.99f, mom_o = 0.99f; } opt;
+    // gradient clipping of every optimizer update of this loop (gnn_loop_set_clipping); 0 = off
+    struct { float value = 0.0f; double norm = 0.0, global = 0.0; } clip;
+    // parameters of the loss inside gnn_loop_train_step (gnn_loop_set_loss_params)
+    struct { double smoothing = 0.0, delta = 1.0; } loss;
+    int k_hint = 0;               // bodies the last training forward of this loop ran (the next one enqueues that many + 1 before it looks at the gates)
+};
+#define GNN_INTERNAL __attribute__((visibility("hidden")))      // the library's own: kept out of its dynamic symbol table
+struct GNN_INTERNAL gnn_train_ctx;                // gnn_train.h
+struct GNN_INTERNAL gnn_train_arena;
 
 struct gnn_loop {
     gnn_graph *g = nullptr;
@@ -335,9 +350,9 @@ struct gnn_loop {
     std::vector<hipEvent_t> sl_ev;          // [world]: block t of the aggregation is complete (recorded on `stream`)
     hipEvent_t sl_done = nullptr;           // this rank's transfers of the body are complete (recorded on the second stream)
     float *agg_own = nullptr;               // [shard_rows, Ds]: aggregated states of the owned rows (GNN.py:234), input of the body
-    void *train_ctx = nullptr;              // gnn_train.hip: what train_forward leaves for train_backward
-    void *train_arena = nullptr;            // gnn_train.hip: device scratch slabs kept from step to step
-    int train_k_hint = 0;                   // bodies the last training forward of this loop ran (the next one enqueues that many + 1 before it looks at the gates)
+    gnn_train_ctx *train_ctx = nullptr;     // gnn_train.h: what train_forward leaves for train_backward
+    gnn_train_arena *train_arena = nullptr; // gnn_train.h: device scratch slabs kept from step to step
+    gnn_train_settings train;
 };
 
 // the graph readout of the loop's LAST run was computed inside that run's persistent launch (result in ng_host)
@@ -352,7 +367,7 @@ int gnn_launch_dense(hipStream_t st, int64_t n, int n_in, int n_out, const float
                      int act, float *Y, int64_t ldy);
 int gnn_launch_check(hipStream_t st, int64_t n_rows, int d, const float *s, const float *so, float thr, int *flag_rank_base);
 // all-gather of `count` 4-byte elements per rank on an RCCL communicator (one process per rank; recv: [world][count], in place when
-// send == recv + rank * count), queued on st - for the translation units that do not see the RCCL table (gnn_train.hip)
+// send == recv + rank * count), queued on st - for the translation units that do not see the RCCL table (gnn_train.hip, gnn_train_net.hip)
 int gnn_comm_allgather32(gnn_comm *c, const void *send, void *recv, size_t count, hipStream_t st);
 // GNNedgeBased.apply_filters on `state` (training path): feats [n_edge_masked, 2 (Ds + NLc) + AL]
 int gnn_launch_feats_edge(hipStream_t st, const gnn_loop *l, const float *state, float *feats);

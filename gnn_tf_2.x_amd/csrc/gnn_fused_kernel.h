@@ -640,7 +640,7 @@ __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rs
 #undef GNN_S0_MFMA
 }
 
-// format 3 without the range guard (the training kernels of gnn_train.hip)
+// format 3 without the range guard (the training kernels of gnn_train_wide.hip)
 template <int NO, bool AL16>
 __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rsrc_t wrs, int voff, int soff, int n_chunks, f32x16 (&acc)[NO],
                                              const float *bias_lds, int half)

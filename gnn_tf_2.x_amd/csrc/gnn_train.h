@@ -1,0 +1,256 @@
+// Host-side types and the functions that cross a unit boundary of the training step (gnn_train.hip: the step; gnn_train_net.hip: one
+// Sequential in training mode; gnn_train_wide.hip: the matrix-core products; gnn_train_update.hip: clipping, regularizers, optimizer).
+// Internal, not installed.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <vector>
+
+#include "gnn_common.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Device scratch of the training step: a bump allocator over slabs that stay with the loop from step to step (a step makes
+// a few hundred allocations; hipMalloc / hipFree for each of them dominated the step time).  reset() at the next forward.
+struct GNN_INTERNAL gnn_train_arena {
+    struct Slab { char *p; size_t size; };
+    std::vector<Slab> slabs;
+    size_t cur = 0, off = 0;
+    void reset() { cur = 0; off = 0; }
+    void *alloc(size_t bytes)
+    {
+        bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+        for (; cur < slabs.size(); ++cur, off = 0)
+            if (off + bytes <= slabs[cur].size) {
+                void *r = slabs[cur].p + off;
+                off += bytes;
+                return r;
+            }
+        Slab s{nullptr, std::max<size_t>(bytes, (size_t)32 << 20)};
+        if (gnn_dev_malloc((void **)&s.p, s.size) != hipSuccess) return nullptr;
+        slabs.push_back(s);
+        cur = slabs.size() - 1;
+        off = bytes;
+        return s.p;
+    }
+    struct Pinned {               // grow-only pinned host buffer
+        void *p = nullptr;
+        size_t bytes = 0;
+        void *get(size_t want)
+        {
+            if (want > bytes) {
+                if (p) (void)hipHostFree(p);
+                p = nullptr; bytes = 0;
+                if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return nullptr;
+                bytes = want;
+            }
+            return p;
+        }
+        ~Pinned() { if (p) (void)hipHostFree(p); }
+    };
+    Pinned host;                  // pinned host words for the results the host waits for (iteration gates, loss partials)
+    Pinned stage;                 // pinned staging for the small per-step uploads (targets, sample weights, NodeGraph CSR): packed by the host, one transfer
+    ~gnn_train_arena() { for (Slab &s : slabs) (void)hipFree(s.p); }
+};
+
+namespace gnn_train GNN_INTERNAL {
+
+inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+
+// rows handled by one block of the column reductions / weight-gradient tiles: about 64 blocks along the rows, so that small
+// batches (a few hundred rows) still spread over the chip; a multiple of 16 (k_wgrad's row tile), at most 1024
+inline int64_t rows_per_block(int64_t n)
+{
+    const int64_t r = ((n + 63) / 64 + 15) / 16 * 16;
+    const int64_t capped = std::min<int64_t>(1024, std::max<int64_t>(32, r));
+    // at most 256 row chunks: every chunk leaves a partial result that a second pass adds up in chunk order
+    return std::max<int64_t>(capped, ((n + 255) / 256 + 15) / 16 * 16);
+}
+
+inline unsigned elementwise_grid(int64_t total) { return (unsigned)std::min<int64_t>(std::max<int64_t>(1, (total + 255) / 256), 2048); }
+
+// ---- device code that two units inline ---------------------------------------------------------------------------------
+// mix64, alpha_dropout_coeffs: the Dropout masks of k_dropout_fwd (gnn_train_net.hip) and of k_train_input (gnn_train.hip: the Dropout in
+// front of net_state's first layer rides on the concat) are one generator.  act_grad, dropout_grad: the way back through an activation /
+// a Dropout is the epilogue of k_act_bwd, k_bn_bwd_apply, k_layer_bwd (gnn_train_net.hip) and of k_gemm_f32, k_gemm_split, k_bwd3_split
+// (gnn_train_wide.hip).  All four are forced inline: a kernel's code does not depend on the unit it is compiled in.
+__device__ __forceinline__ uint64_t mix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// AlphaDropout (Keras; reference GNN/MLP.py:59-61 with alphadropout=True) is passed as a NEGATIVE rate: dropped units are set to
+// alpha' = -selu_scale * selu_alpha and the result is mapped by a x + b so that mean and variance of selu activations are kept:
+//   a = ((1 - r)(1 + r alpha'^2))^-1/2,  b = -a alpha' r,  y = a (x keep + alpha' (1 - keep)) + b,  dy/dx = a keep
+__device__ __forceinline__ void alpha_dropout_coeffs(float r, float *a, float *b, float *alpha_p)
+{
+    const float ap = -1.0507009873554805f * 1.6732632423543772f;
+    const float aa = 1.0f / sqrtf((1.0f - r) * (1.0f + r * ap * ap));
+    *a = aa; *b = -aa * ap * r; *alpha_p = ap;
+}
+
+// act'(z) as a function of the OUTPUT a alone (selu: z > 0 <=> a > 0 and scale * alpha * e^z = a + scale * alpha; elu: e^z = a + 1),
+// so z is not kept.  Softmax is not elementwise: k_act_bwd.
+__device__ __forceinline__ float act_grad(float aa, int act)
+{
+    switch (act) {
+    case GNN_ACT_RELU: return aa > 0.0f ? 1.0f : 0.0f;
+    case GNN_ACT_SELU: return aa > 0.0f ? 1.0507009873554805f : aa + 1.0507009873554805f * 1.6732632423543772f;
+    case GNN_ACT_ELU: return aa > 0.0f ? 1.0f : aa + 1.0f;
+    case GNN_ACT_TANH: return 1.0f - aa * aa;
+    case GNN_ACT_SIGMOID: return aa * (1.0f - aa);
+    default: return 1.0f;
+    }
+}
+
+__device__ __forceinline__ float dropout_grad(float d, uint8_t keep, float rate)
+{
+    if (rate < 0.0f) {
+        float a, b, ap;
+        alpha_dropout_coeffs(-rate, &a, &b, &ap);
+        return keep ? d * a : 0.0f;
+    }
+    return keep ? d / (1.0f - rate) : 0.0f;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+struct Buf {                      // typed front end of the arena
+    gnn_train_arena *arena = nullptr;
+    template <typename T>
+    int get(T **p, size_t count)
+    {
+        *p = static_cast<T *>(arena->alloc(count * sizeof(T)));
+        if (!*p) return gnn_fail(GNN_ERR_HIP, "hipMalloc of %zu bytes failed", count * sizeof(T));
+        return GNN_OK;
+    }
+};
+
+struct NetCache {                 // what one training-mode forward of a Sequential leaves for the backward pass
+    std::vector<float *> hin, a;
+    std::vector<uint8_t *> keep;  // per dropout index 0..L (nullptr when no dropout there)
+    float *xhat = nullptr, *stats = nullptr;
+    int64_t n = 0;
+};
+
+struct Net {
+    const gnn_mlp *m = nullptr;
+    std::vector<float *> WT;      // W^T per layer
+    float *gamma = nullptr, *beta = nullptr;
+    std::vector<float> rate;      // [L + 1] dropout rate in front of Dense l (index L: in front of BatchNormalization)
+    float *grads = nullptr;       // flat: dW1, db1, ..., dgamma, dbeta
+    std::vector<size_t> g_off;
+    size_t g_total = 0;
+    float *part = nullptr;        // [chunks of the rows][g_total]: the partial gradients of ONE net_backward call
+    int64_t part_rows = -1;
+    float *stats_all = nullptr;   // [max forward calls][2 F]: batch mean | biased batch variance of every BatchNormalization call, in call order
+    int calls = 0, max_calls = 0;
+    // The form every forward / backward call of this step takes, decided once by net_setup for the `rows` rows of each call:
+    int64_t rows = 0;
+    bool small_fused = false;     // forward: all Dense layers in one launch (k_mlp_fwd) with small_lds bytes of LDS and row stride small_maxpad ...
+    size_t small_lds = 0;
+    int small_maxpad = 0;
+    bool build_input = false;     // ... which also builds the concat rows and evaluates the body's gate (net_state: the caller leaves x unfilled, InputBuild)
+    bool fwd3 = false, bwd3 = false;          // the three-layer chains on the matrix cores (k_fwd3_split / k_bwd3_split)
+    std::vector<uint8_t> wide_fwd, wide_bwd;  // otherwise per layer: the layer's products on the matrix cores (else k_dense_fwd / k_layer_bwd)
+};
+
+// what k_mlp_fwd builds the concat rows of a body from where Net::build_input is set (the build fields of its MlpFwd)
+struct InputBuild {
+    int Ds, c_aggs;
+    const float *tmpl, *state, *own, *own_prev;
+    const int32_t *indptr, *adj_src;
+    const float *adj_w;
+    float thr;
+    int *flag;
+};
+
+// what follows the last layer of net_state's backward pass in the same launch as the sum of the chunk partials (k_state_grad_sum)
+struct StateGradJob {
+    int64_t N;
+    int Ds, in_s, c_aggs;
+    const int32_t *sip, *sdst;
+    const float *sw;
+    float *d_state;               // out: d loss / d state of the body's input
+};
+
+// floats of a net's trainable arrays = of its gradient vector: dW1, db1, ..., dgamma, dbeta
+inline size_t net_grad_floats(const gnn_mlp *m)
+{
+    size_t t = 0;
+    for (int l = 0; l < m->n_layers; ++l) t += (size_t)m->dims[l] * m->dims[l + 1] + (size_t)m->dims[l + 1];
+    return t + (m->has_bn ? (size_t)2 * m->dims.back() : 0);
+}
+
+// floats of zero-initialised memory a Net needs: the gradient vector and the BatchNormalization statistics of every call
+inline size_t net_zero_floats(const gnn_mlp *m, int max_calls)
+{
+    const size_t t = net_grad_floats(m) + (m->has_bn ? (size_t)std::max(1, max_calls) * 2 * m->dims.back() : 0);
+    return (t + 63) & ~(size_t)63;
+}
+
+// gnn_train_wide.hip: the matrix-core products.  The predicates say what the launchers cover (and hold the GNN_DIAG switches).
+bool tg_many_rows(int64_t n);
+bool tg_wide(int n_in, int n_out);
+bool tg_wgrad_covers(int n_in, int n_out);
+bool fwd3_covers(const gnn_mlp *m);
+bool bwd3_covers(const gnn_mlp *m);
+int launch_gemm_f32(hipStream_t st, Buf &buf, int64_t n, int K, int n_cols, const float *X, const float *M, const float *bias, int act, int mode,
+                    const uint8_t *keep, float rate, const float *a_prev, float *Y);
+int launch_fwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, int64_t n, const float *x, float *a0, float *a1, float *a2);
+int launch_bwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, float *const *WT, int64_t n, const float *dz2, const float *a1, const float *a0, float *dz1,
+                float *dz0, float *dinp, float *dsg = nullptr, int Ds = 0, int c_aggs = 0);
+int launch_wgrad_f32(hipStream_t st, int64_t n, int64_t rpb, int parts, int64_t pstride, int n_in, int n_out, const float *H, const float *DZ, float *part);
+
+// the gather / scatter between the state and the concat with 16 lanes per state row (k_train_input_rows; the dsg rows of k_bwd3_split,
+// k_state_grad_rows): state rows of whole 16-byte pieces, at most 16 of them, on many rows
+inline bool state_rows16(int Ds, int64_t n) { return (Ds & 3) == 0 && Ds <= 64 && tg_many_rows(n); }
+
+// gnn_train_net.hip: one Sequential in training mode
+int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
+              int64_t rows, bool producer_dropout);
+int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, uint64_t seed, NetCache &c, float **y_out,
+                gnn_comm *comm = nullptr, const InputBuild *build = nullptr);
+int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job = nullptr,
+                 gnn_comm *comm = nullptr, int64_t n_global = 0);
+// out[t] += part[0][t] + ... + part[parts - 1][t], t < count (k_sum_parts)
+int net_sum_parts(hipStream_t st, int parts, int64_t count, const float *part, float *out);
+
+}   // namespace gnn_train
+
+// What gnn_loop_train_forward leaves for gnn_loop_train_backward (owned by the loop; replaced by the next forward)
+struct GNN_INTERNAL gnn_train_ctx {
+    gnn_train::Buf buf;
+    gnn_train::Net ns, no_;
+    std::vector<gnn_train::NetCache> caches;
+    gnn_train::NetCache co;
+    int32_t *d_sip = nullptr, *d_sdst = nullptr;
+    float *d_sw = nullptr;
+    float *state = nullptr, *out_nodes = nullptr;
+    int k = 0;
+    int64_t N = 0, M = 0;
+    int64_t N_global = 0, M_global = 0;   // sharded forward: the rows / masked rows of all ranks
+    bool backward_done = false;   // the gradients are complete (and the activations spent)
+    bool applied = false;         // gnn_loop_optimizer_step has consumed them
+    // regularizer penalty, per-block partials of k_grad_prepare: net_state's blocks, then net_output's (0 blocks: no regularizer there)
+    double *pen_part = nullptr;
+    unsigned pen_blocks[2] = {0, 0};
+    // gradient clipping (clip_prepare): per-block partial sums of squares of both nets, their sums per array [2][CLIP_SLOTS] and
+    // over all arrays [1], and the factor of every array [2][CLIP_SLOTS]
+    double *sq_part[2] = {nullptr, nullptr}, *sq = nullptr;
+    float *factor = nullptr;
+};
+
+namespace gnn_train GNN_INTERNAL {
+
+// both nets of the loop with what differs between them: BatchNormalization calls of this step's forward (their statistics rows in
+// Net::stats_all), index 0 net_state, 1 net_output
+struct LoopNet { gnn_mlp *m; Net *net; int calls; };
+inline std::array<LoopNet, 2> loop_nets(gnn_loop *l, gnn_train_ctx *cx) { return {{{l->st, &cx->ns, cx->k}, {l->ou, &cx->no_, cx->M > 0 ? 1 : 0}}}; }
+
+// gnn_train_update.hip: between the backward pass and the update
+int grad_prepare(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st);
+int update_both(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, int kind, const float *h, float gscale_state, float mom_s, float mom_o, bool own_global, double extra);
+
+}   // namespace gnn_train

@@ -1,0 +1,1048 @@
+// One Sequential in training mode: Dropout, activations, BatchNormalization, the per-layer and small fused Dense kernels, the state
+// gradient behind net_state's backward pass; net_setup / net_forward / net_backward (see gnn_train.hip for the step).
+#include <stdlib.h>
+
+#include "gnn_train.h"
+#include "gnn_fused.h"            // GNN_FUSED_MAXL: k_mlp_fwd takes a Sequential of up to one layer more
+
+using namespace gnn_train;
+
+namespace {
+
+// Dropout forward: keep[i] = injected mask or own RNG; y = x * keep / (1 - rate); keep bytes are stored for the backward pass
+__global__ void k_dropout_fwd(int64_t n, const float *x, const uint8_t *mask_in, float rate, uint64_t seed, uint8_t *keep, float *y)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float r = fabsf(rate);
+    uint8_t kp;
+    if (mask_in) kp = mask_in[i] != 0;
+    else kp = ((mix64(seed ^ mix64((uint64_t)i)) >> 40) * (1.0f / 16777216.0f)) >= r;
+    keep[i] = kp;
+    if (rate < 0.0f) {
+        float a, b, ap;
+        alpha_dropout_coeffs(r, &a, &b, &ap);
+        y[i] = a * (kp ? x[i] : ap) + b;
+    } else
+        y[i] = kp ? x[i] / (1.0f - rate) : 0.0f;
+}
+
+__global__ void k_dropout_bwd(int64_t n, const uint8_t *keep, float rate, float *d)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (rate < 0.0f) {
+        float a, b, ap;
+        alpha_dropout_coeffs(-rate, &a, &b, &ap);
+        d[i] = keep[i] ? d[i] * a : 0.0f;
+    } else
+        d[i] = keep[i] ? d[i] / (1.0f - rate) : 0.0f;
+}
+
+__global__ void k_act_fwd(int64_t n, int F, const float *z, int act, float *a)
+{
+    if (act == GNN_ACT_SOFTMAX) {
+        const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (r >= n) return;
+        const float *zr = z + r * F;
+        float *ar = a + r * F;
+        float m = zr[0];
+        for (int j = 1; j < F; ++j) m = zr[j] > m ? zr[j] : m;
+        float s = 0.0f;
+        for (int j = 0; j < F; ++j) { const float e = gnn_expf(zr[j] - m); ar[j] = e; s = s + e; }
+        for (int j = 0; j < F; ++j) ar[j] = __fdiv_rn(ar[j], s);
+    } else {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n * F) a[i] = gnn_act(z[i], act);
+    }
+}
+
+// dz = da * act'(z) (softmax: a * (da - sum da a) per row); in place on d
+__global__ void k_act_bwd(int64_t n, int F, float *d, const float *a, int act)
+{
+    if (act == GNN_ACT_SOFTMAX) {
+        const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (r >= n) return;
+        float s = 0.0f;
+        for (int j = 0; j < F; ++j) s += d[r * F + j] * a[r * F + j];
+        for (int j = 0; j < F; ++j) d[r * F + j] = a[r * F + j] * (d[r * F + j] - s);
+        return;
+    }
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * F) return;
+    d[i] = d[i] * act_grad(a[i], act);
+}
+
+// Row chunks.  Every reduction over the rows of a matrix (BatchNormalization statistics, bias / weight / gamma / beta gradients)
+// is done per chunk of rows_per_block(n) rows; a chunk leaves a partial result and the partials are added in a fixed order
+// (k_sum_parts, or by the consumer itself): run-to-run identical sums without float atomics.
+// Thread layout of the column reductions: 256 threads = CW columns x (256 / CW) row lanes, CW = 2^cw_shift >= min(F, 32), so that
+// narrow matrices (F = 14, 16) still use the whole block; rows are read four at a time (independent loads in flight).
+inline int column_shift(int F) { int s = 0; while ((1 << s) < F && s < 5) ++s; return s; }
+
+// partial sums of x * y and x over the rows of chunk blockIdx.y: out0 / out1 [chunk * ostride + j]
+__global__ void __launch_bounds__(256) k_colreduce2(int64_t n, int F, int cw_shift, const float *__restrict__ x, const float *__restrict__ y, float *out0,
+                                                    float *out1, int64_t ostride, int64_t rows_per_block)
+{
+    __shared__ float s0[256], s1[256];
+    const int CW = 1 << cw_shift, RL = 256 >> cw_shift;
+    const int c = threadIdx.x & (CW - 1), ry = threadIdx.x >> cw_shift;
+    const int j = blockIdx.x * CW + c;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+    float a0 = 0.0f, a1 = 0.0f;
+    if (j < F) {
+        int64_t r = r0 + ry;
+        for (; r + 3 * RL < r1; r += 4 * RL) {
+            float xv[4], yv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { xv[q] = x[(r + q * RL) * F + j]; yv[q] = y[(r + q * RL) * F + j]; }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { a0 += xv[q] * yv[q]; a1 += xv[q]; }
+        }
+        for (; r < r1; r += RL) { const float v = x[r * F + j]; a0 += v * y[r * F + j]; a1 += v; }
+    }
+    s0[threadIdx.x] = a0; s1[threadIdx.x] = a1;
+    __syncthreads();
+    if (ry == 0 && j < F) {
+        for (int t = 1; t < RL; ++t) { a0 += s0[t * CW + c]; a1 += s1[t * CW + c]; }
+        out0[(size_t)blockIdx.y * ostride + j] = a0;
+        out1[(size_t)blockIdx.y * ostride + j] = a1;
+    }
+}
+
+// out[t] += part[0][t] + part[1][t] + ... for the 64 columns of block `bid`: four lanes per column take every fourth chunk, their
+// sums are added in lane order
+__device__ __forceinline__ void sum_parts_block(int bid, int parts, int64_t count, const float *__restrict__ part, float *out, float *sp /* [256] */)
+{
+    const int c = threadIdx.x & 63, zl = threadIdx.x >> 6;
+    const int64_t t = (int64_t)bid * 64 + c;
+    float acc = 0.0f;
+    if (t < count) {
+#pragma unroll 8
+        for (int z = zl; z < parts; z += 4) acc += part[(size_t)z * count + t];
+    }
+    sp[threadIdx.x] = acc;
+    __syncthreads();
+    if (zl == 0 && t < count) out[t] += ((acc + sp[64 + c]) + sp[128 + c]) + sp[192 + c];
+}
+
+__global__ void __launch_bounds__(256) k_sum_parts(int parts, int64_t count, const float *part, float *out)
+{
+    __shared__ float sp[256];
+    sum_parts_block(blockIdx.x, parts, count, part, out, sp);
+}
+
+// out[j] = sum over the chunks z (ascending) of base[z * stride + j], j < count: a rank's own share of sums that the sharded backward
+// pass exchanges (BatchNormalization: sum d y xhat | sum d y)
+__global__ void __launch_bounds__(256) k_sum_strided(int parts, int64_t stride, const float *__restrict__ base, int count, float *out)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    float acc = 0.0f;
+    for (int z = 0; z < parts; ++z) acc += base[(size_t)z * stride + j];
+    out[j] = acc;
+}
+
+// BatchNormalization, training mode, forward statistics of one row chunk: part[chunk][j] = chunk mean, part[chunk][F + j] =
+// sum over the chunk of (x - chunk mean)^2 (two passes over the chunk's rows)
+__global__ void __launch_bounds__(256) k_bn_stats(int64_t n, int F, int cw_shift, const float *__restrict__ h, float *part, int64_t rows_per_block)
+{
+    __shared__ float s0[256];
+    __shared__ float mu[32];
+    const int CW = 1 << cw_shift, RL = 256 >> cw_shift;
+    const int c = threadIdx.x & (CW - 1), ry = threadIdx.x >> cw_shift;
+    const int j = blockIdx.x * CW + c;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+    float a0 = 0.0f;
+    if (j < F) {
+        int64_t r = r0 + ry;
+        for (; r + 3 * RL < r1; r += 4 * RL) {
+            float v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = h[(r + q * RL) * F + j];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a0 += v[q];
+        }
+        for (; r < r1; r += RL) a0 += h[r * F + j];
+    }
+    s0[threadIdx.x] = a0;
+    __syncthreads();
+    if (ry == 0) {
+        for (int t = 1; t < RL; ++t) a0 += s0[t * CW + c];
+        mu[c] = a0 / (float)(r1 - r0);
+    }
+    __syncthreads();
+    const float m = mu[c];
+    a0 = 0.0f;
+    if (j < F) {
+        int64_t r = r0 + ry;
+        for (; r + 3 * RL < r1; r += 4 * RL) {
+            float v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = h[(r + q * RL) * F + j] - m;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a0 += v[q] * v[q];
+        }
+        for (; r < r1; r += RL) { const float dv = h[r * F + j] - m; a0 += dv * dv; }
+    }
+    __syncthreads();
+    s0[threadIdx.x] = a0;
+    __syncthreads();
+    if (ry == 0 && j < F) {
+        for (int t = 1; t < RL; ++t) a0 += s0[t * CW + c];
+        part[(size_t)blockIdx.y * 2 * F + j] = m;
+        part[(size_t)blockIdx.y * 2 * F + F + j] = a0;
+    }
+}
+
+// (count, mean, M2) of two disjoint sets of rows -> of their union (exact in real arithmetic; the order of the calls is fixed)
+__device__ __forceinline__ void stats_merge(float &cnt, float &mean, float &m2, float cb, float mb, float qb)
+{
+    if (cb == 0.0f) return;
+    const float delta = mb - mean, tot = cnt + cb;
+    mean = mean + delta * (cb / tot);
+    m2 = m2 + qb + delta * delta * (cnt * cb / tot);
+    cnt = tot;
+}
+
+// batch mean / biased batch variance from the chunk statistics, then xhat = (h - mean) / sqrt(var + eps), y = gamma xhat + beta.
+// Every block combines the chunks itself (256 / CW lanes per column take every (256 / CW)-th chunk, the lanes are merged in order);
+// block 0 leaves [mean | var] in stats for the backward pass and the moving statistics.  Dynamic LDS: 2 F floats.
+__global__ void __launch_bounds__(256) k_bn_apply(int64_t n, int F, int cw_shift, const float *__restrict__ h, const float *__restrict__ part, int parts,
+                                                  int64_t rows_per_block, float eps, const float *gamma, const float *beta, float *xhat, float *y, float *stats)
+{
+    extern __shared__ float bsh[];
+    __shared__ float sc[3][256];
+    float *sm = bsh, *sinv = bsh + F;
+    const int CW = 1 << cw_shift, ZL = 256 >> cw_shift;
+    const int c = threadIdx.x & (CW - 1), zl = threadIdx.x >> cw_shift;
+    for (int jb = 0; jb < F; jb += CW) {
+        const int j = jb + c;
+        float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
+        if (j < F) {
+#pragma unroll 4
+            for (int z = zl; z < parts; z += ZL) {
+                const int64_t r0 = (int64_t)z * rows_per_block;
+                const float nz = (float)((r0 + rows_per_block < n ? r0 + rows_per_block : n) - r0);
+                stats_merge(cnt, mean, m2, nz, part[(size_t)z * 2 * F + j], part[(size_t)z * 2 * F + F + j]);
+            }
+        }
+        sc[0][threadIdx.x] = cnt; sc[1][threadIdx.x] = mean; sc[2][threadIdx.x] = m2;
+        __syncthreads();
+        if (zl == 0 && j < F) {
+            for (int t = 1; t < ZL; ++t) stats_merge(cnt, mean, m2, sc[0][t * CW + c], sc[1][t * CW + c], sc[2][t * CW + c]);
+            const float var = m2 / (float)n;
+            sm[j] = mean;
+            sinv[j] = 1.0f / sqrtf(var + eps);
+            if (blockIdx.x == 0) { stats[j] = mean; stats[F + j] = var; }
+        }
+        __syncthreads();
+    }
+    const int64_t total = n * F, step = (int64_t)gridDim.x * blockDim.x;
+    const bool small = total < ((int64_t)1 << 31);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int j = small ? (int)((unsigned)i % (unsigned)F) : (int)(i % F);
+        const float xh = (h[i] - sm[j]) * sinv[j];
+        xhat[i] = xh;
+        y[i] = gamma[j] * xh + beta[j];
+    }
+}
+
+// (Round 3 tried BatchNormalization of a small batch as ONE single-block launch per direction - statistics + apply, column sums + apply,
+//  matrices staged in LDS, tree-reduced column sums - to save two launches per call: SLOWER than the two multi-block kernels at MUTAG size,
+//  0.85 against 0.76 ms per 10-body step and 3.0 against 2.6 ms per 50-body step: one workgroup's latency chain against a few microseconds
+//  of launch.  Removed.)
+// ---- BatchNormalization statistics over the rows of ALL ranks (sharded training forward) ----------------------------------------------
+// k_bn_local: the rank's chunk statistics merged in chunk order into ONE triple per feature, tri = [count | mean | M2] (3 F floats);
+// the triples of all ranks are all-gathered (3 F floats per rank and call - the review's "2 H floats" plus the count) and
+// k_bn_apply_ext merges them in RANK order - every rank the same numbers - before it normalises its own rows.
+__global__ void __launch_bounds__(256) k_bn_local(int64_t n, int F, const float *__restrict__ part, int parts, int64_t rows_per_block, float *tri)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= F) return;
+    float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
+    for (int z = 0; z < parts; ++z) {
+        const int64_t r0 = (int64_t)z * rows_per_block;
+        const float nz = (float)((r0 + rows_per_block < n ? r0 + rows_per_block : n) - r0);
+        stats_merge(cnt, mean, m2, nz, part[(size_t)z * 2 * F + j], part[(size_t)z * 2 * F + F + j]);
+    }
+    tri[j] = cnt; tri[F + j] = mean; tri[2 * F + j] = m2;
+}
+
+__global__ void __launch_bounds__(256) k_bn_apply_ext(int64_t n, int F, const float *__restrict__ h, const float *__restrict__ tri_all, int world, float eps,
+                                                      const float *gamma, const float *beta, float *xhat, float *y, float *stats)
+{
+    extern __shared__ float bsh[];
+    float *sm = bsh, *sinv = bsh + F;
+    for (int j = threadIdx.x; j < F; j += blockDim.x) {
+        float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
+        for (int p = 0; p < world; ++p) stats_merge(cnt, mean, m2, tri_all[(size_t)p * 3 * F + j], tri_all[(size_t)p * 3 * F + F + j], tri_all[(size_t)p * 3 * F + 2 * F + j]);
+        const float var = cnt > 0.0f ? m2 / cnt : 0.0f;
+        sm[j] = mean;
+        sinv[j] = 1.0f / sqrtf(var + eps);
+        if (blockIdx.x == 0) { stats[j] = mean; stats[F + j] = var; }
+    }
+    __syncthreads();
+    const int64_t total = n * F, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int j = (int)(i % F);
+        const float xh = (h[i] - sm[j]) * sinv[j];
+        xhat[i] = xh;
+        y[i] = gamma[j] * xh + beta[j];
+    }
+}
+
+// d x = inv / n * (n * dxh - sum dxh - xhat * sum(dxh * xhat)), dxh = d y * gamma, with sum d y * xhat / sum d y added up from the
+// chunk partials p_dyx / p_dy [chunk * pstride + j] (the same numbers k_sum_parts adds into the gamma / beta gradients);
+// then, fused, the derivative of the layer's activation: d <- d x * act'(a) (act < 0: none).  Dynamic LDS: 2 F floats.
+__global__ void __launch_bounds__(256) k_bn_bwd_apply(int64_t n, int F, int cw_shift, float *d, const float *__restrict__ xhat, const float *gamma,
+                                                      const float *stats, float eps, const float *__restrict__ p_dyx, const float *__restrict__ p_dy,
+                                                      int64_t pstride, int parts, const float *__restrict__ a, int act, int64_t n_stat = 0)
+{
+    // n_stat: rows the batch statistics were taken over (sharded backward: the rows of ALL ranks, the partial sums are then one pair per rank); 0: n
+    extern __shared__ float bsh[];
+    __shared__ float sc[2][256];
+    float *s_dyx = bsh, *s_dy = bsh + F;
+    const int CW = 1 << cw_shift, ZL = 256 >> cw_shift;
+    const int c = threadIdx.x & (CW - 1), zl = threadIdx.x >> cw_shift;
+    for (int jb = 0; jb < F; jb += CW) {
+        const int j = jb + c;
+        float a0 = 0.0f, a1 = 0.0f;
+        if (j < F) {
+#pragma unroll 4
+            for (int z = zl; z < parts; z += ZL) { a0 += p_dyx[(size_t)z * pstride + j]; a1 += p_dy[(size_t)z * pstride + j]; }
+        }
+        sc[0][threadIdx.x] = a0; sc[1][threadIdx.x] = a1;
+        __syncthreads();
+        if (zl == 0 && j < F) {
+            for (int t = 1; t < ZL; ++t) { a0 += sc[0][t * CW + c]; a1 += sc[1][t * CW + c]; }
+            s_dyx[j] = a0; s_dy[j] = a1;
+        }
+        __syncthreads();
+    }
+    const int64_t total = n * F, step = (int64_t)gridDim.x * blockDim.x;
+    const float m = (float)(n_stat > 0 ? n_stat : n);
+    const bool small = total < ((int64_t)1 << 31);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int j = small ? (int)((unsigned)i % (unsigned)F) : (int)(i % F);
+        const float inv = 1.0f / sqrtf(stats[F + j] + eps), g = gamma[j];
+        float v = inv / m * (m * d[i] * g - g * s_dy[j] - xhat[i] * g * s_dyx[j]);
+        if (act >= 0) v = v * act_grad(a[i], act);
+        d[i] = v;
+    }
+}
+
+// Weight and bias gradient of one Dense layer over one row chunk: part[chunk * pstride + i * n_out + j] = sum_r H'[r, i] DZ[r, j]
+// with H' = [H | 1] (row i = n_in is the bias gradient: dW and db are adjacent in the gradient vector).  32 x 32 outputs per
+// block, 2 x 2 per thread (one 8-byte LDS read of each operand per four products), 64 rows staged per step, the next step's
+// rows fetched into registers while this step's products run.  lds: 2 x 64 x 34 floats.
+#define GNN_WG_TILE 32
+#define GNN_WG_LD 34
+__device__ __forceinline__ void wgrad_block(int bx, int by, int bz, int64_t n, int n_in, int n_out, const float *__restrict__ H,
+                                            const float *__restrict__ DZ, float *part, int64_t pstride, int64_t rows_per_block, float *lds)
+{
+    float *sh = lds, *sz = lds + 64 * GNN_WG_LD;
+    const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;            // outputs (i0 + 2 ti + {0, 1}, j0 + 2 tj + {0, 1})
+    const int lr = threadIdx.x >> 5, lc = threadIdx.x & 31;            // loader: rows lr + 8 q, column lc
+    const int i0 = bx * GNN_WG_TILE, j0 = by * GNN_WG_TILE;
+    const int64_t r0 = (int64_t)bz * rows_per_block, r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+    float a00 = 0.0f, a01 = 0.0f, a10 = 0.0f, a11 = 0.0f;
+    float hv[8], zv[8];
+    auto fetch = [&](int64_t r) {                  // this thread's share of the 64-row step at r, into registers
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int64_t row = r + lr + 8 * q;
+            const bool in = row < r1;
+            hv[q] = !in ? 0.0f : (i0 + lc < n_in ? H[row * n_in + i0 + lc] : (i0 + lc == n_in ? 1.0f : 0.0f));
+            zv[q] = (in && j0 + lc < n_out) ? DZ[row * n_out + j0 + lc] : 0.0f;
+        }
+    };
+    if (r0 < r1) fetch(r0);
+    for (int64_t r = r0; r < r1; r += 64) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { sh[(lr + 8 * q) * GNN_WG_LD + lc] = hv[q]; sz[(lr + 8 * q) * GNN_WG_LD + lc] = zv[q]; }
+        __syncthreads();
+        if (r + 64 < r1) fetch(r + 64);            // the next step's loads fly during this step's products
+#pragma unroll 16
+        for (int q = 0; q < 64; ++q) {
+            const float2 hq = *reinterpret_cast<const float2 *>(sh + q * GNN_WG_LD + 2 * ti);
+            const float2 zq = *reinterpret_cast<const float2 *>(sz + q * GNN_WG_LD + 2 * tj);
+            a00 = __builtin_fmaf(hq.x, zq.x, a00); a01 = __builtin_fmaf(hq.x, zq.y, a01);
+            a10 = __builtin_fmaf(hq.y, zq.x, a10); a11 = __builtin_fmaf(hq.y, zq.y, a11);
+        }
+        __syncthreads();
+    }
+    float *out = part + (size_t)bz * pstride;
+    const int i = i0 + 2 * ti, j = j0 + 2 * tj;
+    if (i <= n_in) {
+        if (j < n_out) out[(size_t)i * n_out + j] = a00;
+        if (j + 1 < n_out) out[(size_t)i * n_out + j + 1] = a01;
+    }
+    if (i + 1 <= n_in) {
+        if (j < n_out) out[(size_t)(i + 1) * n_out + j] = a10;
+        if (j + 1 < n_out) out[(size_t)(i + 1) * n_out + j + 1] = a11;
+    }
+}
+
+// Dense products of the training step, Y[r, j] = sum_k X[r, k] M[k, j] on R rows per block: 256 threads = CW output columns x KG
+// slices of the k range (CW = 2^cshift >= min(columns, 64)); every thread runs the fmaf chain of its slice (one to a few iterations
+// even for narrow layers: the loop over k is a chain of L2 round trips), the KG partial sums of an output are added in slice order
+// through LDS.  xs: R rows of X, padded to a multiple of 4 (zeros); ps: [KG][R][CW] partials.  fin(r, j, value) stores an output.
+template <int R, class Fin>
+__device__ __forceinline__ void dense_rows(int n_k, int n_k_pad, int n_cols, int cshift, const float *__restrict__ M, const float *xs, float *ps, Fin fin)
+{
+    const int CW = 1 << cshift, KG = 256 >> cshift;
+    const int c = threadIdx.x & (CW - 1), kg = threadIdx.x >> cshift;
+    const int slice = ((n_k + KG - 1) / KG + 3) & ~3;
+    const int k0 = kg * slice, k1 = k0 + slice < n_k ? k0 + slice : n_k;
+    for (int jb = 0; jb < n_cols; jb += CW) {
+        const int j = jb + c;
+        float acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = 0.0f;
+        if (j < n_cols) {
+            int k = k0;
+            for (; k + 4 <= k1; k += 4) {
+                const float w0 = M[(size_t)(k + 0) * n_cols + j], w1 = M[(size_t)(k + 1) * n_cols + j];
+                const float w2 = M[(size_t)(k + 2) * n_cols + j], w3 = M[(size_t)(k + 3) * n_cols + j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float4 x = *reinterpret_cast<const float4 *>(&xs[r * n_k_pad + k]);
+                    acc[r] = __builtin_fmaf(x.x, w0, acc[r]);
+                    acc[r] = __builtin_fmaf(x.y, w1, acc[r]);
+                    acc[r] = __builtin_fmaf(x.z, w2, acc[r]);
+                    acc[r] = __builtin_fmaf(x.w, w3, acc[r]);
+                }
+            }
+            for (; k < k1; ++k) {
+                const float wk = M[(size_t)k * n_cols + j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[r] = __builtin_fmaf(xs[r * n_k_pad + k], wk, acc[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) ps[(kg * R + r) * CW + c] = acc[r];
+        __syncthreads();
+        if (j < n_cols)
+            for (int r = kg; r < R; r += KG) {
+                float v = ps[r * CW + c];
+                for (int g = 1; g < KG; ++g) v += ps[(g * R + r) * CW + c];
+                fin(r, j, v);
+            }
+        __syncthreads();
+    }
+}
+
+inline int dense_cshift(int cols) { int s = 2; while ((1 << s) < cols && s < 6) ++s; return s; }     // CW = 4 .. 64
+inline size_t dense_lds_bytes(int R, int k_pad) { return sizeof(float) * ((size_t)R * k_pad + (size_t)256 * R); }
+
+// d h_in = d z . W^T, then (fused) the way back through what produced h_in: Dropout (keep != NULL) and the previous layer's
+// activation (act >= 0: d <- d * act'(a_prev))
+template <int R>
+__device__ __forceinline__ void dense_bwd_block(int64_t bid, int64_t n, int n_out, int n_out_pad, int n_in, int cshift, const float *__restrict__ DZ,
+                                                const float *__restrict__ WT, const uint8_t *__restrict__ keep, float rate,
+                                                const float *__restrict__ a_prev, int act, float *__restrict__ dprev, float *xs)
+{
+    const int64_t i0 = bid * R;
+    for (int t = threadIdx.x; t < R * n_out_pad; t += blockDim.x) {
+        const int r = t / n_out_pad, k = t - r * n_out_pad;
+        xs[t] = (k < n_out && i0 + r < n) ? DZ[(i0 + r) * n_out + k] : 0.0f;
+    }
+    __syncthreads();
+    dense_rows<R>(n_out, n_out_pad, n_in, cshift, WT, xs, xs + R * n_out_pad, [&](int r, int j, float v) {
+        if (i0 + r >= n) return;
+        const int64_t o = (i0 + r) * n_in + j;
+        if (keep) v = dropout_grad(v, keep[o], rate);
+        if (act >= 0) v = v * act_grad(a_prev[o], act);
+        dprev[o] = v;
+    });
+}
+
+// a = act(h . W + b), training-mode forward of one Dense layer (softmax is applied by the caller)
+template <int R>
+__global__ void __launch_bounds__(256) k_dense_fwd(int64_t n, int n_in, int n_in_pad, int n_out, int cshift, const float *__restrict__ X,
+                                                   const float *__restrict__ W, const float *__restrict__ b, int act, float *__restrict__ Y)
+{
+    extern __shared__ __attribute__((aligned(16))) float xs[];
+    const int64_t i0 = (int64_t)blockIdx.x * R;
+    for (int t = threadIdx.x; t < R * n_in_pad; t += blockDim.x) {
+        const int r = t / n_in_pad, k = t - r * n_in_pad;
+        xs[t] = (k < n_in && i0 + r < n) ? X[(i0 + r) * n_in + k] : 0.0f;
+    }
+    __syncthreads();
+    dense_rows<R>(n_in, n_in_pad, n_out, cshift, W, xs, xs + R * n_in_pad, [&](int r, int j, float v) {
+        if (i0 + r >= n) return;
+        v = v + b[j];
+        if (act != GNN_ACT_SOFTMAX) v = gnn_act(v, act);
+        Y[(i0 + r) * n_out + j] = v;
+    });
+}
+
+// ALL Dense layers of a Sequential on a row tile in one launch (few rows: a MUTAG-sized step is bound by the number of launches): the
+// tile's activations go from layer to layer through LDS, every layer's output is also written out (the backward pass reads it); the
+// arithmetic per layer is that of k_dense_fwd (same dense_rows chains: identical bits).  No Dropout between the layers, softmax only as
+// the last activation (applied by the caller).  LDS: 2 R maxpad + 256 R floats.
+struct MlpFwd {
+    int64_t n;
+    int L, maxpad;
+    int dims[GNN_FUSED_MAXL + 2], pad[GNN_FUSED_MAXL + 2], cshift[GNN_FUSED_MAXL + 1], act[GNN_FUSED_MAXL + 1];
+    const float *W[GNN_FUSED_MAXL + 1], *b[GNN_FUSED_MAXL + 1];
+    const float *X;
+    float *Y[GNN_FUSED_MAXL + 1];
+    // build != 0 (net_state of a loop body, no Dropout in front of the first layer): the input rows are not read from X but BUILT here -
+    // the concat of k_train_input (GNN.py:223-239: own state | template columns | aggregated neighbour states, the fmaf chain over the
+    // arcs in stored order) - written to X_out for the backward pass, and the body's gate (GNN.py:202-220) is evaluated per row
+    int build, Ds, c_aggs;
+    const float *tmpl, *state, *own, *own_prev;
+    const int32_t *indptr, *adj_src;
+    const float *adj_w;
+    float *X_out;
+    float thr;
+    int *flag;
+};
+template <int R>
+__global__ void __launch_bounds__(256) k_mlp_fwd(const MlpFwd p)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *in = lds, *out = lds + (size_t)R * p.maxpad, *ps = lds + (size_t)2 * R * p.maxpad;
+    const int64_t i0 = (int64_t)blockIdx.x * R;
+    if (p.build) {
+        const int in_s = p.dims[0], Ds = p.Ds, c_aggs = p.c_aggs;
+        int moved = 0;
+        for (int t = threadIdx.x; t < R * p.pad[0]; t += blockDim.x) {
+            const int r = t / p.pad[0], c = t - r * p.pad[0];
+            const int64_t row = i0 + r;
+            float v = 0.0f;
+            if (c < in_s && row < p.n) {
+                if (c < Ds) v = p.own[row * Ds + c];
+                else if (c >= c_aggs && c < c_aggs + Ds) {
+                    const int cc = c - c_aggs;
+                    const int32_t e1 = p.indptr[row + 1];
+                    for (int32_t e = p.indptr[row]; e < e1; e += 4) {          // four arcs per step: their loads are in flight together
+                        float w[4], x[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const bool in_ = e + u < e1;
+                            w[u] = in_ ? p.adj_w[e + u] : 0.0f;
+                            x[u] = in_ ? p.state[(int64_t)p.adj_src[e + u] * Ds + cc] : 0.0f;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) if (e + u < e1) v = __builtin_fmaf(w[u], x[u], v);
+                    }
+                } else
+                    v = p.tmpl[row * in_s + c];
+                p.X_out[row * in_s + c] = v;
+                if (c == 0) {                              // the while-condition of this body for the row (k_train_input's chain)
+                    float dist = 0.0f, nrm = 0.0f;
+                    for (int q = 0; q < Ds; ++q) {
+                        const float o = p.own_prev ? p.own_prev[row * Ds + q] : 1.0f;
+                        const float df = p.own[row * Ds + q] - o;
+                        dist = dist + df * df;
+                        nrm = nrm + o * o;
+                    }
+                    moved |= sqrtf(dist) > p.thr * sqrtf(nrm) ? 1 : 0;
+                }
+            }
+            in[t] = v;
+        }
+        if (__any(moved) && (threadIdx.x & 63) == 0) gnn_flag_raise(p.flag);
+    } else {
+        for (int t = threadIdx.x; t < R * p.pad[0]; t += blockDim.x) {
+            const int r = t / p.pad[0], k = t - r * p.pad[0];
+            in[t] = (k < p.dims[0] && i0 + r < p.n) ? p.X[(i0 + r) * p.dims[0] + k] : 0.0f;
+        }
+    }
+    for (int l = 0; l < p.L; ++l) {
+        const int no = p.dims[l + 1], npad = p.pad[l + 1], act = p.act[l];
+        for (int t = threadIdx.x; t < R * npad; t += blockDim.x) out[t] = 0.0f;          // (the padding columns of the next input)
+        __syncthreads();
+        const float *bl = p.b[l];
+        float *Yl = p.Y[l];
+        dense_rows<R>(p.dims[l], p.pad[l], no, p.cshift[l], p.W[l], in, ps, [&](int r, int j, float v) {
+            v = v + bl[j];
+            if (act != GNN_ACT_SOFTMAX) v = gnn_act(v, act);
+            out[r * npad + j] = v;
+            if (i0 + r < p.n) Yl[(i0 + r) * no + j] = v;
+        });
+        float *t_ = in; in = out; out = t_;          // (dense_rows ends with a barrier)
+    }
+}
+
+// One Dense layer of the backward pass in one launch: the blocks of the weight / bias gradient (first wg_blocks ids: the heavier
+// ones) and the blocks of d h_in run side by side; both read d z, neither reads the other's result.
+struct LayerBwd {
+    int64_t n, rows_per_block, pstride;
+    int n_in, n_out, n_out_pad, act, wg_bx, wg_by, wg_blocks, cshift;
+    float rate;
+    const float *H, *DZ, *WT, *a_prev;
+    const uint8_t *keep;
+    float *part, *dprev;
+};
+
+template <int R>
+__global__ void __launch_bounds__(256) k_layer_bwd(const LayerBwd p)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if ((int)blockIdx.x < p.wg_blocks) {
+        const int id = blockIdx.x, bx = id % p.wg_bx, by = (id / p.wg_bx) % p.wg_by, bz = id / (p.wg_bx * p.wg_by);
+        wgrad_block(bx, by, bz, p.n, p.n_in, p.n_out, p.H, p.DZ, p.part, p.pstride, p.rows_per_block, lds);
+    } else
+        dense_bwd_block<R>((int64_t)blockIdx.x - p.wg_blocks, p.n, p.n_out, p.n_out_pad, p.n_in, p.cshift, p.DZ, p.WT, p.keep, p.rate, p.a_prev, p.act, p.dprev, lds);
+}
+
+// End of one body of the backward pass in one launch.  Blocks < sg_blocks: aggregated_states = Adjacency^T . state  =>
+// d state[r] = d inp[r, :Ds] + sum over arcs (r -> dst) of w * d inp[dst, c_aggs:] (own-state columns of the concat + the transposed
+// aggregation over the by-source CSR).  The other blocks: the net's gradient vector += this call's chunk partials (sum_parts_block).
+__global__ void __launch_bounds__(256) k_state_grad_sum(int sg_blocks, int64_t n, int Ds, int in_s, int c_aggs, const float *__restrict__ d_inp,
+                                                        const int32_t *__restrict__ sip, const int32_t *__restrict__ sdst, const float *__restrict__ sw,
+                                                        float *__restrict__ d_state, int parts, int64_t count, const float *part, float *out)
+{
+    __shared__ float sp[256];
+    if ((int)blockIdx.x >= sg_blocks) {
+        sum_parts_block(blockIdx.x - sg_blocks, parts, count, part, out, sp);
+        return;
+    }
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * Ds) return;
+    const int64_t r = n * Ds < ((int64_t)1 << 31) ? (int64_t)((unsigned)t / (unsigned)Ds) : t / Ds;
+    const int c = (int)(t - r * Ds);
+    float acc = 0.0f;
+    const int32_t e1 = sip[r + 1];
+    for (int32_t e = sip[r]; e < e1; e += 4) {                  // four arcs per step: their loads are in flight together
+        float w[4], x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool in = e + u < e1;
+            w[u] = in ? sw[e + u] : 0.0f;
+            x[u] = in ? d_inp[(int64_t)sdst[e + u] * in_s + c_aggs + c] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if (e + u < e1) acc = __builtin_fmaf(w[u], x[u], acc);
+    }
+    d_state[t] = d_inp[r * in_s + c] + acc;
+}
+
+
+// The transposed aggregation of k_state_grad_sum for many rows (state width a multiple of 4, <= 64): 16 lanes per source row, four columns
+// per lane, four arcs in flight per lane (sixteen dependent-free loads), same fmaf chain per element; the sum of the chunk partials runs as
+// its own launch then.  (One thread per element: 1.14 ms per body at 1 M rows x 64, profiles/r03_train_c3.txt.)
+__global__ void __launch_bounds__(256) k_state_grad_rows(int64_t n, int Ds, int in_s, int c_aggs, const float *__restrict__ d_inp, const int32_t *__restrict__ sip,
+                                                         const int32_t *__restrict__ sdst, const float *__restrict__ sw, float *__restrict__ d_state)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = t >> 4;
+    const int cc = 4 * (int)(t & 15);
+    if (r >= n || cc >= Ds) return;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int32_t e1 = sip[r + 1];
+    for (int32_t e = sip[r]; e < e1; e += 4) {
+        float w[4], x[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool in = e + u < e1;
+            w[u] = in ? sw[e + u] : 0.0f;
+            const float *q = d_inp + (int64_t)(in ? sdst[e + u] : 0) * in_s + c_aggs + cc;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) x[u][v] = in ? q[v] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (e + u < e1) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[v] = __builtin_fmaf(w[u], x[u][v], acc[v]);
+            }
+    }
+    const float *own = d_inp + r * in_s + cc;
+    *reinterpret_cast<float4 *>(d_state + r * Ds + cc) = float4{own[0] + acc[0], own[1] + acc[1], own[2] + acc[2], own[3] + acc[3]};
+}
+
+// The same from the aligned copy k_bwd3_split leaves (dsg [n, 2 Ds] = [d inp[:, :Ds] | d inp[:, c_aggs : c_aggs + Ds]]): 16-byte loads, eight arcs in
+// flight per lane, same fmaf chain per element.
+__global__ void __launch_bounds__(256) k_state_grad_rows_al(int64_t n, int Ds, const float *__restrict__ dsg, const int32_t *__restrict__ sip,
+                                                            const int32_t *__restrict__ sdst, const float *__restrict__ sw, float *__restrict__ d_state)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = t >> 4;
+    const int cc = 4 * (int)(t & 15);
+    if (r >= n || cc >= Ds) return;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int32_t e1 = sip[r + 1];
+    for (int32_t e = sip[r]; e < e1; e += 8) {
+        float w[8];
+        float4 x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int32_t ee = e + u < e1 ? e + u : e;                   // clamp: a real entry, result unused
+            w[u] = sw[ee];
+            x[u] = *reinterpret_cast<const float4 *>(dsg + (int64_t)sdst[ee] * 2 * Ds + Ds + cc);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (e + u < e1) {
+                acc[0] = __builtin_fmaf(w[u], x[u].x, acc[0]); acc[1] = __builtin_fmaf(w[u], x[u].y, acc[1]);
+                acc[2] = __builtin_fmaf(w[u], x[u].z, acc[2]); acc[3] = __builtin_fmaf(w[u], x[u].w, acc[3]);
+            }
+    }
+    const float4 own = *reinterpret_cast<const float4 *>(dsg + r * 2 * Ds + cc);
+    *reinterpret_cast<float4 *>(d_state + r * Ds + cc) = float4{own.x + acc[0], own.y + acc[1], own.z + acc[2], own.w + acc[3]};
+}
+
+__global__ void k_transpose(int ni, int no, const float *W, float *WT)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ni * no) return;
+    const int i = t / no, j = t - i * no;
+    WT[(size_t)j * ni + i] = W[t];
+}
+
+}   // namespace
+
+namespace gnn_train {
+
+// The form of this step's forward and backward calls on n rows each (Net::small_fused .. wide_bwd).  producer_dropout: the producer of
+// the input rows applies the Dropout in front of the first Dense layer (net_state: k_train_input hands its mask over as keep0) and,
+// where there is none and the rows are few, leaves the rows themselves to k_mlp_fwd.
+static void net_decide_form(Net &net, int64_t n, bool producer_dropout)
+{
+    const gnn_mlp *m = net.m;
+    const int L = m->n_layers;
+    const bool many = n > 0 && tg_many_rows(n);
+    net.rows = n;
+    // few rows, no Dropout between the layers, softmax at most as the last activation: all Dense layers in one launch (k_mlp_fwd)
+    net.small_fused = L >= 2 && L <= GNN_FUSED_MAXL + 1 && n > 0 && !tg_many_rows(n);
+    int maxpad = (m->dims[0] + 3) & ~3;
+    for (int q = 1; q <= L; ++q) {
+        if (q < L && (net.rate[q] != 0.0f || m->acts[q - 1] == GNN_ACT_SOFTMAX)) net.small_fused = false;
+        maxpad = std::max(maxpad, (m->dims[q] + 3) & ~3);
+    }
+    net.small_maxpad = maxpad;
+    net.small_lds = sizeof(float) * ((size_t)2 * 8 * maxpad + (size_t)256 * 8);
+    if (net.small_lds > 64 * 1024) net.small_fused = false;
+    // a 3-layer net without Dropout behind its first layer, on many rows: the three Dense layers in one pass (k_fwd3_split)
+    net.fwd3 = many && fwd3_covers(m) && net.rate[1] == 0.0f && net.rate[2] == 0.0f && (net.rate[0] == 0.0f || producer_dropout);
+    // ... and without any Dropout, every weight gradient on the matrix cores: the whole backward chain in one pass (k_bwd3_split)
+    net.bwd3 = many && L == 3 && bwd3_covers(m) && net.rate[0] == 0.0f && net.rate[1] == 0.0f && net.rate[2] == 0.0f;
+    for (int l = 0; l < 3 && net.bwd3; ++l) net.bwd3 = tg_wide(m->dims[l + 1], m->dims[l]) && tg_wgrad_covers(m->dims[l], m->dims[l + 1]);
+#ifdef GNN_DIAG
+    static const bool small_off = getenv("GNN_TRAIN_MLP_FUSED") && atoi(getenv("GNN_TRAIN_MLP_FUSED")) == 0;
+    static const bool fuse_off = getenv("GNN_TRAIN_FWD3") && atoi(getenv("GNN_TRAIN_FWD3")) == 0;
+    static const bool chain_off = getenv("GNN_TRAIN_BWD3") && atoi(getenv("GNN_TRAIN_BWD3")) == 0;
+    if (small_off) net.small_fused = false;
+    if (fuse_off) net.fwd3 = false;
+    if (chain_off) net.bwd3 = false;
+#endif
+    net.build_input = net.small_fused && producer_dropout && net.rate[0] == 0.0f;
+    // otherwise layer by layer; a wide layer on many rows: matrix cores (softmax needs the whole row: not as an epilogue)
+    net.wide_fwd.assign(L, 0); net.wide_bwd.assign(L, 0);
+    for (int l = 0; l < L; ++l) {
+        const int ni = m->dims[l], no = m->dims[l + 1];
+        net.wide_fwd[l] = many && tg_wide(ni, no) && m->acts[l] != GNN_ACT_SOFTMAX;
+        net.wide_bwd[l] = many && tg_wide(no, ni) && tg_wgrad_covers(ni, no) && !(l > 0 && m->acts[l - 1] == GNN_ACT_SOFTMAX);
+    }
+}
+
+// zero_mem: net_zero_floats() floats the caller has zeroed (one memset for everything a step needs zeroed); rows, producer_dropout: net_decide_form
+int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
+              int64_t rows, bool producer_dropout)
+{
+    net.m = m;
+    net.max_calls = max_calls;
+    const int L = m->n_layers;
+    net.rate.assign(rates, rates + L + 1);
+    net_decide_form(net, rows, producer_dropout);
+    net.WT.assign(L, nullptr);
+    size_t off = 0;
+    int rc;
+    for (int l = 0; l < L; ++l) {
+        const int ni = m->dims[l], no = m->dims[l + 1];
+        if ((rc = buf.get(&net.WT[l], (size_t)ni * no))) return rc;
+        hipLaunchKernelGGL(k_transpose, cdiv((int64_t)ni * no, 256), 256, 0, st, ni, no, m->W[l], net.WT[l]);
+        HIPCHK(hipGetLastError());
+        net.g_off.push_back(off); off += (size_t)ni * no;
+        net.g_off.push_back(off); off += (size_t)no;
+    }
+    if (m->has_bn) {
+        const int F = m->dims.back();
+        // gamma | beta: the caller's arrays, or (NULL) the MLP's own device copy (the one the device-side optimizer updates)
+        if (bn_gamma_beta_host) {
+            if ((rc = buf.get(&net.gamma, (size_t)2 * F))) return rc;
+            net.beta = net.gamma + F;
+            HIPCHK(hipMemcpyAsync(net.gamma, bn_gamma_beta_host, sizeof(float) * 2 * F, hipMemcpyHostToDevice, st));
+        } else { net.gamma = m->bn_raw; net.beta = m->bn_raw + F; }
+        net.g_off.push_back(off); off += F;
+        net.g_off.push_back(off); off += F;
+        net.stats_all = zero_mem + off;
+    }
+    net.g_total = off;
+    net.grads = zero_mem;
+    return GNN_OK;
+}
+
+// training-mode forward of one Sequential on its net.rows rows (x: [rows, dims[0]]); *y_out: [rows, dims.back()].  keep0 != NULL: the Dropout
+// in front of the first Dense layer has been applied by the producer of x (k_train_input), its mask is keep0.
+// comm != NULL (sharded forward, one process per rank): the BatchNormalization statistics are those of the rows of ALL ranks.
+// net.build_input: x has NOT been filled - k_mlp_fwd builds the concat rows itself (and writes them to x for the backward pass) from *build.
+int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, uint64_t seed, NetCache &c, float **y_out,
+                gnn_comm *comm, const InputBuild *build)
+{
+    const gnn_mlp *m = net.m;
+    const int L = m->n_layers;
+    const int64_t n = net.rows;
+    c.n = n;
+    c.hin.assign(L, nullptr); c.a.assign(L, nullptr); c.keep.assign(L + 1, nullptr);
+    float *h = x;
+    size_t mask_off = 0;
+    int rc;
+    int l_start = 0;
+    if (net.fwd3) {                                // the three Dense layers in one pass (k_fwd3_split)
+        if (net.rate[0] != 0.0f) { c.keep[0] = keep0; mask_off += (size_t)n * m->dims[0]; }
+        for (int l = 0; l < 3; ++l)
+            if ((rc = buf.get(&c.a[l], (size_t)n * m->dims[l + 1]))) return rc;
+        c.hin[0] = x; c.hin[1] = c.a[0]; c.hin[2] = c.a[1];
+        if ((rc = launch_fwd3(st, buf, m, n, x, c.a[0], c.a[1], c.a[2]))) return rc;
+        h = c.a[2];
+        l_start = L;
+    }
+    for (int l = l_start; l <= L; ++l) {
+        const int width = m->dims[l];
+        if (net.rate[l] != 0.0f) {
+            if (l == 0 && keep0) c.keep[0] = keep0;
+            else {
+                float *hd = nullptr;
+                if ((rc = buf.get(&hd, (size_t)n * width)) || (rc = buf.get(&c.keep[l], (size_t)n * width))) return rc;
+                if (n > 0) {
+                    hipLaunchKernelGGL(k_dropout_fwd, cdiv(n * width, 256), 256, 0, st, n * width, h, masks ? masks + mask_off : nullptr, net.rate[l],
+                                       seed + 0x9E37ull * (uint64_t)(l + 1), c.keep[l], hd);
+                    HIPCHK(hipGetLastError());
+                }
+                h = hd;
+            }
+            mask_off += (size_t)n * width;
+        }
+        if (l == L) break;
+        // few rows, no Dropout between the layers: every Dense layer of the net in one launch (k_mlp_fwd)
+        if (l == 0 && net.small_fused) {
+            constexpr int R = 8;
+            MlpFwd p{};
+            if (net.build_input) {
+                p.build = 1; p.X_out = h;
+                p.Ds = build->Ds; p.c_aggs = build->c_aggs; p.tmpl = build->tmpl; p.state = build->state; p.own = build->own; p.own_prev = build->own_prev;
+                p.indptr = build->indptr; p.adj_src = build->adj_src; p.adj_w = build->adj_w; p.thr = build->thr; p.flag = build->flag;
+            }
+            p.n = n; p.L = L; p.maxpad = net.small_maxpad; p.X = h;
+            for (int q = 0; q <= L; ++q) { p.dims[q] = m->dims[q]; p.pad[q] = (m->dims[q] + 3) & ~3; }
+            for (int q = 0; q < L; ++q) {
+                if ((rc = buf.get(&c.a[q], (size_t)n * m->dims[q + 1]))) return rc;
+                p.cshift[q] = dense_cshift(m->dims[q + 1]); p.act[q] = m->acts[q]; p.W[q] = m->W[q]; p.b[q] = m->b[q]; p.Y[q] = c.a[q];
+                c.hin[q] = q == 0 ? h : c.a[q - 1];
+            }
+            hipLaunchKernelGGL((k_mlp_fwd<R>), cdiv(n, R), 256, net.small_lds, st, p);
+            HIPCHK(hipGetLastError());
+            if (m->acts[L - 1] == GNN_ACT_SOFTMAX) {
+                hipLaunchKernelGGL(k_act_fwd, cdiv(n, 256), 256, 0, st, n, m->dims[L], c.a[L - 1], m->acts[L - 1], c.a[L - 1]);
+                HIPCHK(hipGetLastError());
+            }
+            h = c.a[L - 1];
+            l = L - 1;               // (the loop goes on with index L: the Dropout in front of BatchNormalization, if any)
+            continue;
+        }
+        const int no = m->dims[l + 1];
+        c.hin[l] = h;
+        if ((rc = buf.get(&c.a[l], (size_t)n * no))) return rc;
+        const bool sm = m->acts[l] == GNN_ACT_SOFTMAX;          // softmax needs the whole row: separate pass, in place
+        if (net.wide_fwd[l]) {                     // wide layer on many rows: matrix cores
+            if ((rc = launch_gemm_f32(st, buf, n, width, no, h, m->W[l], m->b[l], m->acts[l], 0, nullptr, 0.0f, nullptr, c.a[l]))) return rc;
+        } else if (n > 0) {
+            constexpr int R = 8;
+            const int ni_pad = (width + 3) & ~3;
+            const size_t lds = dense_lds_bytes(R, ni_pad);
+            if (lds > 64 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "layer input width %d too large", width);
+            hipLaunchKernelGGL((k_dense_fwd<R>), cdiv(n, R), 256, lds, st, n, width, ni_pad, no, dense_cshift(no), h, m->W[l], m->b[l],
+                               sm ? GNN_ACT_LINEAR : m->acts[l], c.a[l]);
+            HIPCHK(hipGetLastError());
+        }
+        if (n > 0 && sm) {
+            hipLaunchKernelGGL(k_act_fwd, cdiv(n, 256), 256, 0, st, n, no, c.a[l], m->acts[l], c.a[l]);
+            HIPCHK(hipGetLastError());
+        }
+        h = c.a[l];
+    }
+    if (m->has_bn) {
+        const int F = m->dims.back();
+        float *y = nullptr;
+        if ((rc = buf.get(&c.xhat, (size_t)n * F)) || (rc = buf.get(&y, (size_t)n * F))) return rc;
+        if (net.calls >= std::max(1, net.max_calls)) return gnn_fail(GNN_ERR_STATE, "more BatchNormalization calls than announced");
+        c.stats = net.stats_all + (size_t)net.calls++ * 2 * F;
+        if (comm) {
+            // every rank takes part in the exchange, also one without rows (count 0)
+            float *tri = nullptr, *tri_all = nullptr;
+            if ((rc = buf.get(&tri, (size_t)3 * F)) || (rc = buf.get(&tri_all, (size_t)3 * F * comm->world))) return rc;
+            const int64_t rpb = n > 0 ? rows_per_block(n) : 1;
+            const int parts = n > 0 ? (int)cdiv(n, rpb) : 0;
+            float *part = nullptr;
+            if ((rc = buf.get(&part, (size_t)std::max(parts, 1) * 2 * F))) return rc;
+            if (n > 0) {
+                const int cs = column_shift(F);
+                hipLaunchKernelGGL(k_bn_stats, dim3(cdiv(F, 1 << cs), parts), 256, 0, st, n, F, cs, h, part, rpb);
+            }
+            hipLaunchKernelGGL(k_bn_local, cdiv(F, 256), 256, 0, st, n, F, part, parts, rpb, tri);
+            HIPCHK(hipGetLastError());
+            if ((rc = gnn_comm_allgather32(comm, tri, tri_all, (size_t)3 * F, st))) return rc;
+            hipLaunchKernelGGL(k_bn_apply_ext, n > 0 ? elementwise_grid(n * F) : 1, 256, sizeof(float) * 2 * F, st, n, F, h, tri_all, comm->world, m->eps, net.gamma,
+                               net.beta, c.xhat, y, c.stats);
+            HIPCHK(hipGetLastError());
+        } else if (n > 0) {
+            const int64_t rpb = rows_per_block(n);
+            const int parts = (int)cdiv(n, rpb);
+            float *part = nullptr;
+            if ((rc = buf.get(&part, (size_t)parts * 2 * F))) return rc;
+            const int cs = column_shift(F);
+            hipLaunchKernelGGL(k_bn_stats, dim3(cdiv(F, 1 << cs), parts), 256, 0, st, n, F, cs, h, part, rpb);
+            hipLaunchKernelGGL(k_bn_apply, elementwise_grid(n * F), 256, sizeof(float) * 2 * F, st, n, F, cs, h, part, parts, rpb, m->eps, net.gamma,
+                               net.beta, c.xhat, y, c.stats);
+            HIPCHK(hipGetLastError());
+        }
+        h = y;
+    }
+    *y_out = h;
+    return GNN_OK;
+}
+
+// back-propagation through one Sequential: d is d loss / d y on entry ([n, dims.back()], overwritten); on return *dx_out is
+// d loss / d x ([n, dims[0]]); weight gradients are ADDED into net.grads (one sum over the call's chunk partials)
+// comm != NULL (sharded backward, one process per rank): the sums of BatchNormalization's backward pass are those of the rows of ALL
+// ranks (n_global of them); the weight gradients stay this rank's share (train_backward adds the shares up at the end).
+int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job,
+                 gnn_comm *comm, int64_t n_global)
+{
+    const gnn_mlp *m = net.m;
+    const int L = m->n_layers;
+    const int64_t n = c.n;
+    int rc;
+    if (n <= 0) {                              // no rows: no gradient; d x is empty
+        if (comm && m->has_bn) {               // ... but the other ranks wait for this one's (zero) share of the sums
+            const int F = m->dims.back();
+            float *loc = nullptr, *all = nullptr;
+            if ((rc = buf.get(&loc, (size_t)2 * F)) || (rc = buf.get(&all, (size_t)2 * F * comm->world))) return rc;
+            HIPCHK(hipMemsetAsync(loc, 0, sizeof(float) * 2 * F, st));
+            if ((rc = gnn_comm_allgather32(comm, loc, all, (size_t)2 * F, st))) return rc;
+        }
+        *dx_out = d;
+        return GNN_OK;
+    }
+    const int64_t rpb = rows_per_block(n);
+    const int parts = (int)cdiv(n, rpb);
+    if (net.part_rows != n) {
+        if ((rc = buf.get(&net.part, (size_t)parts * net.g_total))) return rc;
+        net.part_rows = n;
+    }
+    const int64_t ps = (int64_t)net.g_total;
+    const int act_last = m->acts[L - 1];
+    // the derivative of the last activation rides on the BatchNormalization pass when nothing sits between them
+    bool last_act_done = false;
+    if (m->has_bn) {
+        const int F = m->dims.back(), cs = column_shift(F);
+        float *p_dyx = net.part + net.g_off[2 * L], *p_dy = net.part + net.g_off[2 * L + 1];
+        const bool fuse = net.rate[L] == 0.0f && act_last != GNN_ACT_SOFTMAX;
+        hipLaunchKernelGGL(k_colreduce2, dim3(cdiv(F, 1 << cs), parts), 256, 0, st, n, F, cs, d, c.xhat, p_dyx, p_dy, ps, rpb);
+        if (comm) {
+            // this rank's sums [sum d y xhat | sum d y] (adjacent in the gradient vector: they ARE the gamma / beta gradients), those of
+            // all ranks all-gathered, added in rank order by every block of the apply kernel
+            float *loc = nullptr, *all = nullptr;
+            if ((rc = buf.get(&loc, (size_t)2 * F)) || (rc = buf.get(&all, (size_t)2 * F * comm->world))) return rc;
+            hipLaunchKernelGGL(k_sum_strided, cdiv(2 * F, 256), 256, 0, st, parts, ps, p_dyx, 2 * F, loc);
+            HIPCHK(hipGetLastError());
+            if ((rc = gnn_comm_allgather32(comm, loc, all, (size_t)2 * F, st))) return rc;
+            hipLaunchKernelGGL(k_bn_bwd_apply, elementwise_grid(n * F), 256, sizeof(float) * 2 * F, st, n, F, cs, d, c.xhat, net.gamma, c.stats, m->eps,
+                               all, all + F, (int64_t)2 * F, comm->world, c.a[L - 1], fuse ? act_last : -1, n_global);
+        } else
+            hipLaunchKernelGGL(k_bn_bwd_apply, elementwise_grid(n * F), 256, sizeof(float) * 2 * F, st, n, F, cs, d, c.xhat, net.gamma, c.stats, m->eps,
+                               p_dyx, p_dy, ps, parts, c.a[L - 1], fuse ? act_last : -1, (int64_t)0);
+        HIPCHK(hipGetLastError());
+        last_act_done = fuse;
+    }
+    if (net.rate[L] != 0.0f) {
+        const int F = m->dims.back();
+        hipLaunchKernelGGL(k_dropout_bwd, cdiv(n * F, 256), 256, 0, st, n * F, c.keep[L], net.rate[L], d);
+        HIPCHK(hipGetLastError());
+    }
+    if (!last_act_done) {
+        const int no = m->dims[L];
+        const bool sm = act_last == GNN_ACT_SOFTMAX;
+        if (sm || act_last != GNN_ACT_LINEAR) {
+            hipLaunchKernelGGL(k_act_bwd, cdiv(sm ? n : n * no, 256), 256, 0, st, n, no, d, c.a[L - 1], act_last);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    // d is d loss / d z of layer l at the top of every pass
+    // a 3-layer net without Dropout on many rows: the whole chain d z2 -> d z1 -> d z0 -> d inp in one pass (k_bwd3_split), then the three weight gradients
+    float *dsg = nullptr;
+    const bool chain3 = net.bwd3;
+    if (chain3) {
+        float *dz1 = nullptr, *dz0 = nullptr, *dinp = nullptr;
+        if ((rc = buf.get(&dz1, (size_t)n * m->dims[2])) || (rc = buf.get(&dz0, (size_t)n * m->dims[1])) || (rc = buf.get(&dinp, (size_t)n * m->dims[0]))) return rc;
+        // the state gradient of this body reads two column blocks of d inp: the chain leaves them once more as aligned rows
+        if (job && job->N == n && state_rows16(job->Ds, job->N) && job->in_s == m->dims[0] && (rc = buf.get(&dsg, (size_t)n * 2 * job->Ds))) return rc;
+        if ((rc = launch_bwd3(st, buf, m, net.WT.data(), n, d, c.a[1], c.a[0], dz1, dz0, dinp, dsg, job ? job->Ds : 0, job ? job->c_aggs : 0))) return rc;
+        const float *dzs[3] = {dz0, dz1, d};
+        for (int l = 2; l >= 0; --l)
+            if ((rc = launch_wgrad_f32(st, n, rpb, parts, ps, m->dims[l], m->dims[l + 1], c.hin[l], dzs[l], net.part + net.g_off[2 * l]))) return rc;
+        d = dinp;
+    }
+    for (int l = chain3 ? -1 : L - 1; l >= 0; --l) {
+        const int ni = m->dims[l], no = m->dims[l + 1];
+        float *dprev = nullptr;
+        if ((rc = buf.get(&dprev, (size_t)n * ni))) return rc;
+        // weight + bias gradient tiles and d h_in = d z . W^T (back through Dropout l and, l > 0, the activation of layer l - 1) in one launch
+        const int act_prev = l > 0 ? m->acts[l - 1] : -1;
+        const bool prev_sm = act_prev == GNN_ACT_SOFTMAX;
+        if (net.wide_bwd[l]) {                     // both products of a wide layer on the matrix cores
+            if ((rc = launch_wgrad_f32(st, n, rpb, parts, ps, ni, no, c.hin[l], d, net.part + net.g_off[2 * l]))) return rc;
+            if ((rc = launch_gemm_f32(st, buf, n, no, ni, d, net.WT[l], nullptr, act_prev, 1, net.rate[l] != 0.0f ? c.keep[l] : nullptr, net.rate[l],
+                                      l > 0 ? c.a[l - 1] : nullptr, dprev))) return rc;
+            d = dprev;
+            continue;
+        }
+        constexpr int R = 8;
+        LayerBwd p;
+        p.n = n; p.rows_per_block = rpb; p.pstride = ps;
+        p.n_in = ni; p.n_out = no; p.n_out_pad = (no + 3) & ~3; p.act = prev_sm ? -1 : act_prev;
+        p.wg_bx = (int)cdiv(ni + 1, GNN_WG_TILE); p.wg_by = (int)cdiv(no, GNN_WG_TILE); p.wg_blocks = p.wg_bx * p.wg_by * parts;
+        p.rate = net.rate[l];
+        p.H = c.hin[l]; p.DZ = d; p.WT = net.WT[l]; p.a_prev = l > 0 ? c.a[l - 1] : nullptr;
+        p.keep = net.rate[l] != 0.0f ? c.keep[l] : nullptr;
+        p.part = net.part + net.g_off[2 * l]; p.dprev = dprev;
+        p.cshift = dense_cshift(ni);
+        const size_t lds = std::max(dense_lds_bytes(R, p.n_out_pad), sizeof(float) * 2 * 64 * GNN_WG_LD);
+        if (lds > 64 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "layer width %d too large", no);
+        hipLaunchKernelGGL((k_layer_bwd<R>), (unsigned)(p.wg_blocks + cdiv(n, R)), 256, lds, st, p);
+        if (prev_sm) hipLaunchKernelGGL(k_act_bwd, cdiv(n, 256), 256, 0, st, n, ni, dprev, c.a[l - 1], act_prev);
+        HIPCHK(hipGetLastError());
+        d = dprev;
+    }
+    const unsigned sum_blocks = cdiv((int64_t)net.g_total, 64);
+    if (job && dsg) {
+        hipLaunchKernelGGL(k_state_grad_rows_al, cdiv(job->N * 16, 256), 256, 0, st, job->N, job->Ds, dsg, job->sip, job->sdst, job->sw, job->d_state);
+        hipLaunchKernelGGL(k_sum_parts, sum_blocks, 256, 0, st, parts, (int64_t)net.g_total, net.part, net.grads);
+    } else if (job && state_rows16(job->Ds, job->N)) {
+        hipLaunchKernelGGL(k_state_grad_rows, cdiv(job->N * 16, 256), 256, 0, st, job->N, job->Ds, job->in_s, job->c_aggs, d, job->sip, job->sdst, job->sw, job->d_state);
+        hipLaunchKernelGGL(k_sum_parts, sum_blocks, 256, 0, st, parts, (int64_t)net.g_total, net.part, net.grads);
+    } else if (job && job->N > 0) {
+        const int sg = (int)cdiv(job->N * job->Ds, 256);
+        hipLaunchKernelGGL(k_state_grad_sum, sg + sum_blocks, 256, 0, st, sg, job->N, job->Ds, job->in_s, job->c_aggs, d, job->sip, job->sdst, job->sw,
+                           job->d_state, parts, (int64_t)net.g_total, net.part, net.grads);
+    } else
+        hipLaunchKernelGGL(k_sum_parts, sum_blocks, 256, 0, st, parts, (int64_t)net.g_total, net.part, net.grads);
+    HIPCHK(hipGetLastError());
+    *dx_out = d;
+    return GNN_OK;
+}
+
+int net_sum_parts(hipStream_t st, int parts, int64_t count, const float *part, float *out)
+{
+    hipLaunchKernelGGL(k_sum_parts, cdiv(count, 64), 256, 0, st, parts, count, part, out);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
+}   // namespace gnn_train

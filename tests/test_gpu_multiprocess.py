@@ -134,7 +134,7 @@ def test_ranks_as_processes_match_oracle(world):
         assert np.max(np.abs(state - ctx['state'])) < 2e-5 * scale and np.max(np.abs(outp - ctx['out_nodes'])) < 2e-5, \
             (tag, float(np.max(np.abs(state - ctx['state']))), float(np.max(np.abs(outp - ctx['out_nodes']))))
         # one GPU: the order in which the chunk statistics of BatchNormalization are merged differs, and with few rows per rank the dense
-        # products run on the FP32 ALUs instead of the matrix cores (gnn_train.hip, tg_many_rows): float32-level differences
+        # products run on the FP32 ALUs instead of the matrix cores (gnn_train_wide.hip, tg_many_rows): float32-level differences
         ipt, srct, wt, awt, alt = S._csr_parts(gt)
         maskt = np.logical_and(gt['set_mask'], gt['output_mask'])
         mst, mou = e.Mlp(stt['weights'], stt['activations'], True), e.Mlp(out_['weights'], out_['activations'], True)

@@ -651,7 +651,7 @@ def test_lgnn_device_optimizer_matches_host_optimizer(mode):
 @pytest.mark.parametrize('n,with_dropout,d,hidden', [(6000, False, 64, (128, 128)), (4500, True, 64, (128, 128)), (4200, False, 64, (100, 96)), (4131, False, 64, (72, 128)), (4300, False, 48, (100, 96))])
 def test_wide_layers_on_the_matrix_cores_match_oracle(n, with_dropout, d, hidden):
     """BASELINE configs[2] net shape (state_dim 64, 135 -> 128 -> 128 -> 64) on enough rows for the matrix-core products of the training
-    step (gnn_train.hip: k_gemm_f32 forward / d h_in, k_wgrad_f32 weight gradients, k_train_input_rows): loss, k and every gradient array
+    step (gnn_train_wide.hip: k_gemm_f32 forward / d h_in, k_wgrad_f32 weight gradients; gnn_train.hip: k_train_input_rows): loss, k and every gradient array
     against the float64 oracle to 2e-4 of the array's largest entry (1e-3, the bar of the small-shape tests above, with Dropout in the
     net).  Measured on this step (tools/dbg/train_acc.py, profiles/r03_train_c3.txt): split-bf16 products 1.1e-4, f32-MFMA chain 3.1e-4,
     per-op FP32-ALU kernels 2.6e-4 - the bias gradients are the least accurate arrays in all three.  A repeated step gives the same bits
