@@ -22,7 +22,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
            'gnn_loss_grad_ex', 'gnn_loop_set_loss_params',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
-           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
+           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
 
@@ -112,6 +112,21 @@ def shard_range(n_nodes: int, rank: int, world: int) -> tuple[int, int]:
     b, n = C.c_int64(0), C.c_int64(0)
     _check(lib().gnn_shard_range(C.c_int64(n_nodes), C.c_int(rank), C.c_int(world), C.byref(b), C.byref(n)))
     return b.value, n.value
+
+
+def gather_program(indptr, adj_src, adj_w):
+    """gnn_gather_program_build (host code): (hdr [tiles, 2] int32, ent [batches, 64, 2] uint32) of the full 32-row tiles of a CSR graph;
+    ent[..., 0] is the source word, ent[..., 1] the weight's bits."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+    adj_src = np.ascontiguousarray(adj_src, dtype=np.int32)
+    adj_w = _f32(adj_w)
+    n_rows = indptr.size - 1
+    hdr = np.zeros((n_rows // 32, 2), np.int32)
+    nb = C.c_int64(0)
+    _check(lib().gnn_gather_program_build(C.c_int64(n_rows), _ip(indptr), _ip(adj_src), _fp(adj_w), _ip(hdr), None, C.byref(nb)))
+    ent = np.zeros((nb.value, 64, 2), np.int32)
+    _check(lib().gnn_gather_program_build(C.c_int64(n_rows), _ip(indptr), _ip(adj_src), _fp(adj_w), None, _ip(ent), C.byref(nb)))
+    return hdr, ent.view(np.uint32)
 
 
 def halo_plan(n_nodes: int, world: int, indptr, adj_src):
@@ -243,6 +258,12 @@ class Graph:
         d = Graph(None, None, None, None, None, None, None, None, _handle=h)
         d._base = self
         return d
+
+    def gather_program_info(self) -> dict:
+        """gnn_graph_gather_program_info: size and host build time of the graph's gather program (all zero while it has none)."""
+        t, b, n, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
+        _check(lib().gnn_graph_gather_program_info(self._h, C.byref(t), C.byref(b), C.byref(n), C.byref(ms)))
+        return dict(tiles=t.value, batches=b.value, bytes=n.value, build_ms=ms.value)
 
     def set_arc_order(self, arc_id, arc_labels_orig) -> None:
         arc_id = np.ascontiguousarray(arc_id, dtype=np.int32)
@@ -652,6 +673,14 @@ class Loop:
         next run takes (0: the fused path does not cover this loop)."""
         used = C.c_int(0)
         _check(lib().gnn_loop_set_tile_form(self._h, C.c_int(int(form)), C.byref(used)))
+        return used.value
+
+    def set_gather_form(self, form: int) -> int:
+        """gnn_loop_set_gather_form: how the full-tile kernel finds a tile's neighbour rows - 1 = it walks the CSR, 2 = it reads the graph's
+        gather program (built on first demand), 0 = the library's choice; returns the form the next run takes (0: the fused path does not
+        cover this loop).  Results are identical bit for bit."""
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_gather_form(self._h, C.c_int(int(form)), C.byref(used)))
         return used.value
 
     def counters(self) -> dict:

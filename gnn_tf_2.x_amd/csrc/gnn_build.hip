@@ -13,9 +13,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
+#include <new>
 #include <vector>
 
 #include "gnn_common.h"
+#include "gnn_fused.h"
 
 namespace {
 
@@ -196,4 +199,147 @@ extern "C" int gnn_graph_create_from_arcs(int64_t n_nodes, int64_t n_arcs, const
     *out = g;
     return GNN_OK;
 #undef HIPCHK_G
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Gather program of the full-tile fused kernel (gather form 2; gnn_fused_kernel.h: load_tile_prog64).  Host code.
+//
+// A lane group of the kernel consumes one entry per slot; a row takes as many slots as it has entries, an empty row one (a zero-weight
+// entry without a source, so that its aggregate is written as an exact +0).  The 32 rows of a tile go to the four lane groups as
+// contiguous ranges that minimise the largest group's slot count (a group may get no row at all); all four streams are padded to that
+// count, rounded up to whole batches of 16.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// rows [start[g], start[g + 1]) of the tile to lane group g: the smallest possible largest slot count, groups filled front to back
+void gather_program_split(const int (&slots)[32], int (&start)[5], int &longest)
+{
+    int lo = 0, hi = 0;
+    for (int r = 0; r < 32; ++r) { lo = std::max(lo, slots[r]); hi += slots[r]; }
+    auto groups_needed = [&](int cap) {
+        int n = 1, fill = 0;
+        for (int r = 0; r < 32; ++r) {
+            if (fill + slots[r] > cap) { ++n; fill = 0; }
+            fill += slots[r];
+        }
+        return n;
+    };
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (groups_needed(mid) <= 4) hi = mid; else lo = mid + 1;
+    }
+    int g = 0, fill = 0;
+    start[0] = 0;
+    for (int r = 0; r < 32; ++r) {
+        if (fill + slots[r] > lo) { start[++g] = r; fill = 0; }
+        fill += slots[r];
+    }
+    while (g < 4) start[++g] = 32;
+    longest = lo;
+}
+
+}   // namespace
+
+extern "C" int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, const int32_t *adj_src, const float *adj_w, int32_t *hdr,
+                                        int32_t *ent, int64_t *n_batches)
+{
+    ARGCHK(n_rows >= 0 && indptr && n_batches, "n_rows / indptr / n_batches are required");
+    const int64_t tiles = n_rows / 32;
+    ARGCHK(indptr[tiles * 32] == 0 || (adj_src && adj_w), "arc arrays are required");
+    int64_t batch = 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int32_t *ip = indptr + t * 32;
+        int slots[32], start[5], longest = 0;
+        for (int r = 0; r < 32; ++r) {
+            ARGCHK(ip[r + 1] >= ip[r], "indptr not monotone at row %lld", (long long)(t * 32 + r));
+            slots[r] = std::max(1, ip[r + 1] - ip[r]);
+        }
+        gather_program_split(slots, start, longest);
+        const int nb = (longest + 15) / 16;
+        ARGCHK(batch + nb < ((int64_t)1 << 31) / 64, "gather program too large");
+        if (hdr) { hdr[2 * t] = (int32_t)batch; hdr[2 * t + 1] = nb; }
+        if (ent) {
+            for (int g = 0; g < 4; ++g) {
+                int s = 0;
+                auto put = [&](uint32_t word, float w) {
+                    int32_t *e = ent + (((batch + s / 16) * 64 + 16 * g + s % 16) * 2);
+                    memcpy(e, &word, 4);
+                    memcpy(e + 1, &w, 4);
+                    ++s;
+                };
+                for (int r = start[g]; r < start[g + 1]; ++r) {
+                    if (ip[r + 1] == ip[r]) put(GNN_GP_NOROW | GNN_GP_ROW_END | (uint32_t)r, 0.0f);
+                    for (int32_t e = ip[r]; e < ip[r + 1]; ++e) {
+                        if (adj_src[e] < 0 || adj_src[e] >= (1 << 23))
+                            return gnn_fail(GNN_ERR_UNSUPPORTED, "adj_src[%d]=%d does not fit a gather-program source word", e, adj_src[e]);
+                        put((uint32_t)adj_src[e] << 8 | (e + 1 == ip[r + 1] ? GNN_GP_ROW_END : 0u) | (uint32_t)r, adj_w[e]);
+                    }
+                }
+                while (s < 16 * nb) put(GNN_GP_NOROW, 0.0f);      // behind the group's last row end: whatever it accumulates is never written
+            }
+        }
+        batch += nb;
+    }
+    *n_batches = batch;
+    return GNN_OK;
+}
+
+// The program of g's graph on g's device, built once (with the first fused Loop, or the first gnn_loop_set_gather_form, that takes gather
+// form 2).  Never an error: a graph whose program cannot be built or kept keeps walking the CSR (sh->gp_ent stays nullptr).  The attempt is
+// made ONCE per graph (gp_tried): a graph that failed for want of memory is not tried again when memory has become free.
+int gnn_gather_program_ensure(const gnn_graph *g)
+{
+    gnn_graph_shared *sh = g->sh;
+    if (sh->gp_tried) return GNN_OK;
+    sh->gp_tried = true;
+    const int64_t tiles = g->n_rows / 32;
+    if (tiles == 0) return GNN_OK;
+    // the caller may be a setter outside any run: the copies and allocations below belong on the graph's device, whatever device is current
+    int dev_before = -1;
+    if (hipGetDevice(&dev_before) != hipSuccess || hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return GNN_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    int32_t *d_hdr = nullptr, *d_ent = nullptr;
+    int64_t batches = 0;
+    bool ok = false;
+    try {
+        std::vector<int32_t> indptr((size_t)tiles * 32 + 1), hdr((size_t)tiles * 2), src, ent;
+        std::vector<float> w;
+        ok = hipMemcpy(indptr.data(), sh->indptr, sizeof(int32_t) * indptr.size(), hipMemcpyDeviceToHost) == hipSuccess;
+        const size_t E = ok ? (size_t)indptr.back() : 0;
+        src.resize(E); w.resize(E);
+        ok = ok && (E == 0 || (hipMemcpy(src.data(), sh->adj_src, sizeof(int32_t) * E, hipMemcpyDeviceToHost) == hipSuccess &&
+                               hipMemcpy(w.data(), sh->adj_w, sizeof(float) * E, hipMemcpyDeviceToHost) == hipSuccess));
+        // what the builder would refuse is looked for here, so that a graph without a program leaves no error text behind a Loop that succeeds
+        for (size_t e = 0; ok && e < E; ++e) ok = src[e] >= 0 && src[e] < (1 << 23);
+        ok = ok && gnn_gather_program_build(tiles * 32, indptr.data(), src.data(), w.data(), hdr.data(), nullptr, &batches) == GNN_OK;
+        if (ok) {
+            ent.resize((size_t)batches * 128);
+            ok = gnn_gather_program_build(tiles * 32, indptr.data(), src.data(), w.data(), nullptr, ent.data(), &batches) == GNN_OK;
+        }
+        ok = ok && gnn_dev_malloc((void **)&d_hdr, sizeof(int32_t) * hdr.size()) == hipSuccess &&
+             gnn_dev_malloc((void **)&d_ent, sizeof(int32_t) * ent.size()) == hipSuccess &&
+             hipMemcpy(d_hdr, hdr.data(), sizeof(int32_t) * hdr.size(), hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(d_ent, ent.data(), sizeof(int32_t) * ent.size(), hipMemcpyHostToDevice) == hipSuccess;
+    } catch (const std::bad_alloc &) { ok = false; }
+    if (ok) {
+        sh->gp_hdr = d_hdr; sh->gp_ent = d_ent; sh->gp_tiles = tiles; sh->gp_batches = batches;
+        sh->gp_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    } else {
+        (void)hipFree(d_hdr); (void)hipFree(d_ent);
+        (void)hipGetLastError();                                   // (an allocation failure is not this Loop's error)
+    }
+    (void)hipSetDevice(dev_before);
+    return GNN_OK;
+}
+
+extern "C" int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *batches, int64_t *bytes, float *build_ms)
+{
+    ARGCHK(g, "graph is NULL");
+    const gnn_graph_shared *sh = g->sh;
+    const bool have = sh->gp_ent != nullptr;
+    if (tiles) *tiles = have ? sh->gp_tiles : 0;
+    if (batches) *batches = have ? sh->gp_batches : 0;
+    if (bytes) *bytes = have ? sh->gp_tiles * 8 + sh->gp_batches * 512 : 0;
+    if (build_ms) *build_ms = have ? sh->gp_build_ms : 0.0f;
+    return GNN_OK;
 }

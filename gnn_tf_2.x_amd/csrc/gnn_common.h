@@ -181,6 +181,15 @@ struct gnn_graph_shared {
     int32_t *full_indptr = nullptr, *full_src = nullptr;
     float *full_w = nullptr;
     int64_t full_rows = 0;
+    // Gather program of the full-tile fused kernel (gather form 2; gnn_gather_program_build, GnnFusedArgs::gp_*): the CSR above, walked once
+    // and laid out per 32-row tile and lane group in the order the kernel consumes it.  Built with the first fused Loop that asks for it
+    // (gnn_gather_program_ensure), shared with the graphs derived from this one, freed with the last owner.  gp_tried without gp_ent: the
+    // graph has no program (no full tile, sources beyond the source word's range, or no memory) and keeps walking the CSR - for its
+    // lifetime: the attempt is made once, also when what failed was an allocation that might succeed later.
+    int32_t *gp_hdr = nullptr, *gp_ent = nullptr;
+    int64_t gp_tiles = 0, gp_batches = 0;
+    bool gp_tried = false;
+    float gp_build_ms = 0.0f;               // host time of the build, copies included
 };
 
 struct gnn_graph {
@@ -313,6 +322,8 @@ struct gnn_loop {
     bool graph_ready_seen = false;          // this loop's stream has waited for the graph's creation-time fills
     int impl_req = 1, impl_used = 0;
     int tile_form = 0;                      // gnn_loop_set_tile_form: 0 library's choice, 1 one wave per tile, 2 wave pair per tile
+    int gather_form = 0;                    // gnn_loop_set_gather_form: 0 library's choice, 1 walk the CSR, 2 the graph's gather program
+    bool gather_program = false;            // this run's launches read the program: decided once per run by gnn_fused_prepare
     int32_t *ng_ip = nullptr, *ng_node = nullptr;   // cached NodeGraph^T (graph readout)
     float *ng_w = nullptr, *ng_out = nullptr, *ng_part = nullptr;   // ng_part [world, G, T]: per-rank partial readouts
     std::vector<int32_t> ng_key;
@@ -382,6 +393,9 @@ void gnn_train_arena_free(gnn_loop *l);
 // gnn_fused.hip
 bool gnn_fused_supported(const gnn_loop *l);
 bool gnn_fused_pair_selected(const gnn_loop *l);   // the default path's bodies run as k_fused_pair (wave pair per tile) rather than k_fused
+bool gnn_fused_program_selected(const gnn_loop *l);   // the bodies run as the full-tile k_fused and gather from the graph's program (built on demand)
+// gnn_build.hip
+int gnn_gather_program_ensure(const gnn_graph *g);
 int gnn_fused_prepare(gnn_loop *l);
 int gnn_fused_pack(gnn_mlp *m, int nlc);
 int gnn_fused_iteration(gnn_loop *l, int k);

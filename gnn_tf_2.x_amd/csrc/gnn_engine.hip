@@ -744,6 +744,7 @@ static void graph_release_shared(gnn_graph_shared *sh)
     (void)hipFree(sh->src_indptr); (void)hipFree(sh->src_dst); (void)hipFree(sh->src_w);
     (void)hipFree(sh->arc_id); (void)hipFree(sh->arc_labels_orig);
     (void)hipFree(sh->full_indptr); (void)hipFree(sh->full_src); (void)hipFree(sh->full_w);
+    (void)hipFree(sh->gp_hdr); (void)hipFree(sh->gp_ent);
     delete sh;
 }
 
@@ -1446,6 +1447,14 @@ extern "C" int gnn_loop_set_tile_form(gnn_loop *l, int form, int *used)
     ARGCHK(l && form >= 0 && form <= 2, "form must be 0 (library's choice), 1 (one wave per tile) or 2 (wave pair per tile)");
     l->tile_form = form;
     if (used) *used = (l->impl_req >= 1 && gnn_fused_supported(l)) ? (gnn_fused_pair_selected(l) ? 2 : 1) : 0;
+    return GNN_OK;
+}
+
+extern "C" int gnn_loop_set_gather_form(gnn_loop *l, int form, int *used)
+{
+    ARGCHK(l && form >= 0 && form <= 2, "form must be 0 (library's choice), 1 (walk the CSR) or 2 (the graph's gather program)");
+    l->gather_form = form;
+    if (used) *used = (l->impl_req >= 1 && gnn_fused_supported(l)) ? (gnn_fused_program_selected(l) ? 2 : 1) : 0;
     return GNN_OK;
 }
 

@@ -10,6 +10,14 @@ constexpr int GNN_FUSED_THREADS = 64 * GNN_FUSED_WAVES;
 // of magnitude >= GNN_F16_LIMIT (the largest finite fp16) sends the Loop back to the bf16-piece format
 #define GNN_F16_EX 4
 #define GNN_F16_LIMIT 65504.0f
+// Source word of a gather-program entry: the byte offset of the neighbour's 256-byte state row (source id << 8; the replica is < 2 GiB by the
+// fused path's precondition, gnn_fused_supported), in the low byte the tile-local row the entry belongs to and "this entry ends its row".
+// GNN_GP_NOROW is an offset no replica reaches (any offset >= 2^31 would do; this one keeps the 16-byte access of the last lane, 0xfffffef0
+// .. 0xfffffeff, clear of the 2^32 wrap): a raw buffer load past the descriptor's range returns zeros (padding, and the single entry of an
+// empty row).  That such a load costs no memory fetch is the ISA's description of the range check, not something a counter run has shown.
+#define GNN_GP_ROW_MASK 31u
+#define GNN_GP_ROW_END 32u
+#define GNN_GP_NOROW 0xfffffe00u
 
 struct GnnFusedArgs {
     // graph
@@ -54,6 +62,11 @@ struct GnnFusedArgs {
     int variant;             // tuning switches (bit 0: raised wave priority during the gather); fixed in the shipped build
     // feature-sliced exchange: aggregated states of the owned rows [n_rows, Ds], computed outside the kernel (no gather), else nullptr
     const float *agg_in;
+    // gather program of the graph (gnn_gather_program_build; gather form 2 of the full-tile kernel), or gp_tiles == 0: walk the CSR.
+    // gp_hdr [gp_tiles][2] = {first batch, batches} of every full 32-row tile; gp_ent [batches][64][2] = {source word, weight} of lane
+    // 16 g + j: entry j of lane group g in that batch, in the order the group consumes them
+    const int32_t *gp_hdr, *gp_ent;
+    int gp_tiles;
     int threads;             // threads per workgroup of the launch (0: GNN_FUSED_THREADS)
     int single_ticket;       // 1: the launch has no more tiles than waves - a wave draws ONE ticket at start (no look-ahead tile)
     // diagnostics only (GNN_FUSED_STAMPS=<file>): s_memtime stamps per wave at the phase boundaries, else nullptr

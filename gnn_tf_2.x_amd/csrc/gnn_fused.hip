@@ -38,6 +38,12 @@ constexpr int GNN_FUSED_VARIANT_DEFAULT = 1;      // bit 0: raised wave priority
 // tiles, no atomics at start; profiles/r04_midsize.txt): 8 and 6.
 constexpr int GNN_FUSED_SPREAD_DEFAULT = 8;
 constexpr int GNN_FUSED_SPREAD_SMALL_DEFAULT = 6;
+// gather form of the full-tile kernel when the loop leaves the choice to the library (gnn_loop_set_gather_form(l, 0)): 1 walks the CSR, 2 reads
+// the graph's gather program.  A macro so that an A/B build (tools/ab_build.sh) can turn it; the measurement behind the shipped value:
+// docs/DESIGN_appendix.md A.1, profiles/r10_gather_program.txt
+#ifndef GNN_GATHER_FORM_DEFAULT
+#define GNN_GATHER_FORM_DEFAULT 2
+#endif
 constexpr int S_SLACK = 2;      // zero chunks after the layer-0 block of the split image (layer0_split looks two chunks ahead)
 
 int round_tiles(int width) { return width <= 32 ? 1 : (width <= 64 ? 2 : 4); }
@@ -140,6 +146,19 @@ bool gnn_fused_pair_selected(const gnn_loop *l)
     if (!pair_covers(p, l->Ds) || pair_lds_bytes(p) > 160 * 1024) return false;
     if (l->tile_form) return l->tile_form == 2;
     return (l->g->n_rows + 31) / 32 <= (int64_t)4 * device_cus(l->device);
+}
+
+// Whether the loop's bodies gather from the graph's program (gnn_loop_set_gather_form): the launch must be the full-tile form of k_fused that
+// gathers (state width 64, a net with a 64-wide last layer, no feature-sliced exchange, not the wave pair), and the graph must have a program
+// - it is built here, on first demand.
+bool gnn_fused_program_selected(const gnn_loop *l)
+{
+    FusedPlan p;
+    if (l->impl_req < 1 || l->slice_mode || l->Ds != 64 || !make_plan(l->st, l->NLc, p) || p.NTL != 2) return false;
+    if ((l->gather_form ? l->gather_form : GNN_GATHER_FORM_DEFAULT) != 2) return false;
+    if (l->impl_req == 2 && gnn_fused_pair_selected(l)) return false;
+    if (gnn_gather_program_ensure(l->g) != GNN_OK) return false;
+    return l->g->sh->gp_ent != nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -291,6 +310,7 @@ bool gnn_fused_supported(const gnn_loop *l)
 int gnn_fused_prepare(gnn_loop *l)
 {
     const gnn_graph *g = l->g;
+    l->gather_program = gnn_fused_program_selected(l);      // once per run (the first one builds the graph's program), not per launch
     const int IW = 2 * l->NLc + g->AL;
     if (!l->inv) {
         // (rows padded to whole 32-node tiles and zeroed: the full-tile kernel reads the label columns of a partial last tile unguarded)
@@ -452,6 +472,7 @@ int gnn_fused_iteration(gnn_loop *l, int k)
         // branch with masked row stores / condition votes (the row buffers are padded to whole tiles, rows past n_rows have no arcs)
         GnnFusedArgs af = a;
         af.full_tiles = 1; af.tile_base = 0;
+        if (l->gather_program) { af.gp_hdr = g->sh->gp_hdr; af.gp_ent = g->sh->gp_ent; af.gp_tiles = (int)g->sh->gp_tiles; }
         ok = go(af, (unsigned)std::min<size_t>((size_t)n_cu, (size_t)n_tiles64));
     } else
         ok = go(a, grid);

@@ -937,26 +937,57 @@ __device__ __forceinline__ void gather_batch(int my_src, float my_w, __amdgpu_bu
 // PADDED: the zero padding of the tile (columns behind the concat, alignment hole) is already in place: nothing in a tile's life
 // writes those columns, so the full-tile kernel zeroes them once per wave instead of once per tile
 // (Two batches of GB rows in flight per lane group were measured in round 2: 4 % slower, DESIGN.md appendix.)
+// Own state rows and label columns of a full Ds == 64 tile: 8 x 16 B + 4 floats per lane requested in front of the gather, written to
+// LDS behind it (their latency hides behind the gather)
+template <bool AL16>
+struct TileOwn64 {
+    v4f own[8];
+    float lab[4];
+    __device__ __forceinline__ void request(const GnnFusedArgs &a, int64_t i0, int lane)
+    {
+        const float *src = a.state_cur + (a.row_begin + i0) * 64 + lane * 4;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) own[u] = gload4(src + u * 256);      // (as non-temporal loads: +2.5 %, round 5 - these rows are other tiles' neighbour rows too)
+        const int IW = a.IW, nlab = 32 * IW;
+        const float *lsrc = a.inv + i0 * IW;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) lab[u] = (lane + 64 * u < nlab) ? gload1(lsrc + lane + 64 * u) : 0.0f;
+    }
+    __device__ __forceinline__ void write(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs) const
+    {
+        constexpr int Ds = 64;
+        const int IW = a.IW, nlab = 32 * IW;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float *x = X + (4 * u + (lane >> 4)) * KP + (lane & 15) * 4;         // flat element 256 u + 4 lane = row 4u + lane/16
+            if constexpr (AL16) *reinterpret_cast<v4f *>(x) = own[u];
+            else { x[0] = own[u].x; x[1] = own[u].y; x[2] = own[u].z; x[3] = own[u].w; }
+        }
+        const float inv_iw = 1.0f / (float)(IW > 0 ? IW : 1);                    // t / IW without an integer division: exact for t < 2^16
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = lane + 64 * u;
+            if (t < nlab) {
+                const int i = (int)(((float)t + 0.5f) * inv_iw), c = t - i * IW;
+                X[i * KP + label_col(c, Ds, a.NLc, c_aggs)] = lab[u];
+            }
+        }
+        if (nlab > 256)                                                          // wide label blocks: the rest, plainly
+            for (int t = 256 + lane; t < nlab; t += 64) {
+                const int i = t / IW, c = t - i * IW;
+                X[i * KP + label_col(c, Ds, a.NLc, c_aggs)] = gload1(a.inv + i0 * IW + t);
+            }
+    }
+};
+
 template <bool AL16, bool PADDED = false>
 __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X, const int *ipt, int64_t i0, int lane,
                                                  int KP, int c_aggs, int my_src, float my_w)
 {
-    constexpr int GB = 16, Ds = 64;
+    constexpr int GB = 16;
     const int gl = lane & 15, grp = lane >> 4;
-    // own state rows: 8 x 16 B per lane requested now, written to LDS after the gather (their latency hides behind it)
-    v4f own[8];
-    {
-        const float *src = a.state_cur + (a.row_begin + i0) * Ds + lane * 4;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) own[u] = gload4(src + u * 256);      // (as non-temporal loads: +2.5 %, round 5 - these rows are other tiles' neighbour rows too)
-    }
-    float lab[4];
-    const int IW = a.IW, nlab = 32 * IW;
-    {
-        const float *src = a.inv + i0 * IW;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) lab[u] = (lane + 64 * u < nlab) ? gload1(src + lane + 64 * u) : 0.0f;
-    }
+    TileOwn64<AL16> own;
+    own.request(a, i0, lane);
     if constexpr (!PADDED) zero_pad_columns(a, X, lane, KP);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                   // ipt visible to the whole wave
 
@@ -966,7 +997,7 @@ __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X
     int next_end = ipt[node + 1];
     v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
     // neighbour rows through a buffer descriptor: 32-bit byte offsets (src * 256 + 16 * lane-in-row) instead of 64-bit
-    // pointer arithmetic per row; the state replica is < 4 GiB by the fused path's precondition
+    // pointer arithmetic per row; the state replica is < 2 GiB by the fused path's precondition (gnn_fused_supported)
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
     const int voff0 = gl * 16;
     float *xo = X + c_aggs + gl * 4;
@@ -1016,27 +1047,76 @@ __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X
         else { xr[0] = acc01.x; xr[1] = acc01.y; xr[2] = acc23.x; xr[3] = acc23.y; }
         acc01 = v2f{0.f, 0.f}; acc23 = v2f{0.f, 0.f};
     }
-    // own state and label columns into the tile
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        float *x = X + (4 * u + (lane >> 4)) * KP + (lane & 15) * 4;         // flat element 256 u + 4 lane = row 4u + lane/16
-        if constexpr (AL16) *reinterpret_cast<v4f *>(x) = own[u];
-        else { x[0] = own[u].x; x[1] = own[u].y; x[2] = own[u].z; x[3] = own[u].w; }
+    own.write(a, X, i0, lane, KP, c_aggs);                                   // own state and label columns into the tile
+}
+
+// ---- the same tile from the graph's gather program (gather form 2; gnn_gather_program_build) ----
+// The CSR structure never changes after the graph is created, so it is walked once, on the host: per tile and lane group the program holds
+// the (source word, weight) entries in the order the group consumes them, all four streams padded to the same number of 16-entry batches.
+// The tile's 32 rows are split into four contiguous ranges of near-equal entry count (rows whole, entries in CSR order: every row's fmaf
+// chain is the one load_tile_fast64 evaluates), the trip count is wave-uniform, and a row end is a bit of the entry: no row pointers, no
+// tail batch, no loop inside the batch.
+// one entry: the fmaf chain, and at a row end the aggregate to the tile and a fresh accumulator
+template <bool AL16, int J>
+__device__ __forceinline__ void prog_consume(int words, float w, v4f x, v2f &acc01, v2f &acc23, float *xo, int KP)
+{
+    gather_fma(acc01, acc23, w, x);
+    const unsigned t = (unsigned)row_bcast_i<J>(words);                      // entry J's word again (one DPP move; not kept across the batch)
+    if (t & GNN_GP_ROW_END) {                                                // uniform per lane group
+        float *xr = xo + __umul24(t & GNN_GP_ROW_MASK, (unsigned)KP);
+        if constexpr (AL16) *reinterpret_cast<v4f *>(xr) = v4f{acc01.x, acc01.y, acc23.x, acc23.y};
+        else { xr[0] = acc01.x; xr[1] = acc01.y; xr[2] = acc23.x; xr[3] = acc23.y; }
+        acc01 = v2f{0.f, 0.f}; acc23 = v2f{0.f, 0.f};
     }
-    const float inv_iw = 1.0f / (float)(IW > 0 ? IW : 1);                    // t / IW without an integer division: exact for t < 2^16
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int t = lane + 64 * u;
-        if (t < nlab) {
-            const int i = (int)(((float)t + 0.5f) * inv_iw), c = t - i * IW;
-            X[i * KP + label_col(c, Ds, a.NLc, c_aggs)] = lab[u];
-        }
+}
+template <bool AL16, int GB, int... J>
+__device__ __forceinline__ void prog_batch(int words, float my_w, __amdgpu_buffer_rsrc_t rsrc, int voff0, float (&w)[GB], v4f (&x)[GB],
+                                           std::integer_sequence<int, J...>)
+{
+    ((w[J] = row_bcast_f<J>(my_w),
+      x[J] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (row_bcast_i<J>(words) & ~0xff) | voff0, 0, 0))), ...);
+}
+template <bool AL16, int GB, int... J>
+__device__ __forceinline__ void prog_consume_all(int words, const float (&w)[GB], const v4f (&x)[GB], v2f &acc01, v2f &acc23, float *xo, int KP,
+                                                 std::integer_sequence<int, J...>)
+{
+    (prog_consume<AL16, J>(words, w[J], x[J], acc01, acc23, xo, KP), ...);
+}
+typedef int v2i __attribute__((ext_vector_type(2)));
+// header {first batch, batches} of a tile's program, {0, 0} for a tile without one (the partial last tile, a ticket past the end): the same
+// 8 bytes for every lane
+__device__ __forceinline__ v2i prog_header_request(const GnnFusedArgs &a, int tile)
+{
+    v2i h = {0, 0};
+    if (tile < a.gp_tiles) h = *reinterpret_cast<const GNN_GLOBAL v2i *>(gptr(a.gp_hdr) + 2 * (int64_t)tile);
+    return h;
+}
+// this lane's entry of batch b of the program
+__device__ __forceinline__ v2i prog_entry(const GnnFusedArgs &a, int b, int lane)
+{
+    return *reinterpret_cast<const GNN_GLOBAL v2i *>(gptr(a.gp_ent) + ((int64_t)b * 64 + lane) * 2);
+}
+// first / nb: the tile's header; ent: this lane's entry of the first batch, requested during the previous tile
+template <bool AL16>
+__device__ __forceinline__ void load_tile_prog64(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs, int first, int nb, v2i ent)
+{
+    constexpr int GB = 16;
+    const int gl = lane & 15;
+    TileOwn64<AL16> own;
+    own.request(a, i0, lane);
+    v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
+    const int voff0 = gl * 16;
+    float *xo = X + c_aggs + gl * 4;
+    for (int b = 0; b < nb; ++b) {
+        float w[GB];
+        v4f x[GB];
+        const int words = ent.x;
+        prog_batch<AL16, GB>(words, __int_as_float(ent.y), rsrc, voff0, w, x, std::make_integer_sequence<int, GB>{});
+        if (b + 1 < nb) ent = prog_entry(a, first + b + 1, lane);           // (wave-uniform)
+        prog_consume_all<AL16, GB>(words, w, x, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
     }
-    if (nlab > 256)                                                          // wide label blocks: the rest, plainly
-        for (int t = 256 + lane; t < nlab; t += 64) {
-            const int i = t / IW, c = t - i * IW;
-            X[i * KP + label_col(c, Ds, a.NLc, c_aggs)] = gload1(a.inv + i0 * IW + t);
-        }
+    own.write(a, X, i0, lane, KP, c_aggs);
 }
 
 // Ds == 64, full tile, aggregate GIVEN (a.agg_in: rows of the aggregated state computed by another kernel): three coalesced row
@@ -1309,7 +1389,9 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N])
 // GIVEN (with FULL): the aggregated states come from a.agg_in (feature-sliced exchange) - row copies instead of the gather.  A
 // template parameter, not a branch: a wave-uniform branch in the tile loop of the full-tile kernel cost 3 % (0.700 -> 0.721 ms).
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3>
+// PROG (with FULL, not GIVEN): the full tiles are gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the
+// partial last tile of the range walks the CSR as before.  A template parameter for the same reason as GIVEN.
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3, bool PROG = false>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedArgs a0)
 {
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
@@ -1339,7 +1421,10 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     const int w_launch = wave * (int)gridDim.x + (int)blockIdx.x;
     const bool third_round = (int64_t)2 * W_launch * 32 < a.n_rows;          // wave-uniform: tickets are only drawn when tiles beyond 2 W exist
     int tile = w_launch + a.tile_base, next_tile = w_launch + W_launch + a.tile_base;
-    const int ip_first_raw = tile_rowptr_request(a, tile, lane);      // on its way while the workgroup stages its vectors below
+    int ip_first_raw = 0;
+    v2i hdr_first_raw = {0, 0};
+    if constexpr (PROG) hdr_first_raw = prog_header_request(a, tile);
+    else ip_first_raw = tile_rowptr_request(a, tile, lane);           // on its way while the workgroup stages its vectors below
     // last-layer bias and BatchNormalization scale / shift: staged once per workgroup behind the row-pointer slots
     float *ep = lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32 + GNN_FUSED_WAVES * 36;
     for (int t = threadIdx.x; t < 3 * 32 * NTL; t += blockDim.x) {
@@ -1361,10 +1446,18 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         else rounds = (int)((((unsigned)blockIdx.x * GNN_FUSED_WAVES + (unsigned)wave) * 0x9E3779B1u) >> 16) % (unsigned)(a.stagger + 1);
         for (int i = 0; i < rounds; ++i) __builtin_amdgcn_s_sleep(127);
     }
-    int ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
-    int src_cur = 0;
+    int ip_cur = 0, src_cur = 0;
     float w_cur = 0.0f;
-    if (FULL || Ds == 64) tile_first_ids(a, ip_cur, lane, src_cur, w_cur);
+    // PROG: header of the current tile (wave-uniform) and this lane's entry of its first batch
+    int hdr_first = 0, hdr_nb = 0;
+    v2i ent_cur = {0, 0};
+    if constexpr (PROG) {
+        hdr_first = __builtin_amdgcn_readfirstlane(hdr_first_raw.x); hdr_nb = __builtin_amdgcn_readfirstlane(hdr_first_raw.y);
+        if (hdr_nb > 0) ent_cur = prog_entry(a, hdr_first, lane);
+    } else {
+        ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
+        if (FULL || Ds == 64) tile_first_ids(a, ip_cur, lane, src_cur, w_cur);
+    }
     if constexpr (FULL) zero_pad_columns(a, X, lane, KP);             // once: no tile ever writes the padding columns
   for (;;) {
     const int64_t i0 = (int64_t)tile * 32;
@@ -1394,13 +1487,27 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     // the tile's 33 row pointers go through LDS: the gather re-reads them inside divergent code, where a cross-lane
     // broadcast from lanes of another group would not be safe
     int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
-    if (lane <= 32) ipt[lane] = ip_cur;               // requested during the previous tile
-    const int ip_next_raw = tile_rowptr_request(a, next_tile, lane);      // row pointers of the NEXT tile: on their way during the gather
+    int ip_next_raw = 0;
+    v2i hdr_next_raw = {0, 0};
+    if constexpr (PROG) hdr_next_raw = prog_header_request(a, next_tile);     // program header of the NEXT tile: on its way during the gather
+    else {
+        if (lane <= 32) ipt[lane] = ip_cur;           // requested during the previous tile
+        ip_next_raw = tile_rowptr_request(a, next_tile, lane);            // row pointers of the NEXT tile: on their way during the gather
+    }
     const bool fast64 = FULL || ((Ds == 64) && (nvalid == 32) && !a.agg_in);     // wave-uniform: the BASELINE shape takes the unguarded paths
     // the gather is a chain of few instructions and long memory waits: with a raised priority its loads are issued ahead of the
     // SIMD partner's dense VALU / MFMA stream instead of behind it
     if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
     if constexpr (FULL && GIVEN) load_tile_given64<SPLIT>(a, X, i0, lane, KP, c_aggs);      // feature-sliced exchange: no gather (a.agg_in)
+    else if constexpr (PROG) {
+        if (hdr_nb > 0) load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur);      // (wave-uniform)
+        else {                                        // the partial last tile: its row pointers and first ids are asked for here, once per launch
+            const int ip = tile_rowptr_clamp(a, tile, lane, tile_rowptr_request(a, tile, lane));
+            if (lane <= 32) ipt[lane] = ip;
+            tile_first_ids(a, ip, lane, src_cur, w_cur);
+            load_tile_fast64<SPLIT, true>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
+        }
+    }
     else if constexpr (FULL) load_tile_fast64<SPLIT, true>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
     else {
         if (fast64) load_tile_fast64<SPLIT>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
@@ -1471,10 +1578,17 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     if (third_round) {
         if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr, 1) + 2 * W_launch;
     }
-    const int ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
-    int src_next = 0;
+    int ip_next = 0, src_next = 0;
     float w_next = 0.0f;
-    if (FULL || Ds == 64) tile_first_ids(a, ip_next, lane, src_next, w_next);
+    int hdr_first_next = 0, hdr_nb_next = 0;
+    v2i ent_next = {0, 0};
+    if constexpr (PROG) {
+        hdr_first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); hdr_nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
+        if (hdr_nb_next > 0) ent_next = prog_entry(a, hdr_first_next, lane);
+    } else {
+        ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
+        if (FULL || Ds == 64) tile_first_ids(a, ip_next, lane, src_next, w_next);
+    }
     if constexpr (SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
     GnnFlagPeek peek = {0, 0, 0};                             // the gate words of this wave's slot: on their way across the epilogue arithmetic
     if (SPLIT && NTL == 2 && lane == 0) peek = gnn_flag_peek(a.flag_out);
@@ -1521,21 +1635,26 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     tile = next_tile;
     next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + a0.tile_base;
     ip_cur = ip_next; src_cur = src_next; w_cur = w_next;
+    hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; ent_cur = ent_next;
   }
 }
 
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false, int PC = 3>
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false, int PC = 3, bool PROG = false>
 inline void launch_one_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
+    // the full-tile gathering kernel exists in both gather forms; the launch carries a program (gp_tiles > 0) when form 2 was chosen for it
+    if constexpr (FULL && !GIVEN && !PROG) {
+        if (a.gp_tiles > 0) { launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, true>(a, grid, lds_bytes, st); return; }
+    }
     static bool raised[64] = {false};   // dynamic LDS above 64 KiB has to be requested once per kernel AND device
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !raised[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (dev >= 0 && dev < 64) raised[dev] = true;
     }
-    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
+    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
 }
 // the split arithmetic in the piece format of the launch (a.pieces); the exact path has one
 template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false>

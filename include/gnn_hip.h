@@ -334,6 +334,26 @@ int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used);
  * The two forms evaluate the same arithmetic per node: states, outputs and k are identical bit for bit.  *used (may be NULL) = the form
  * the next run will take (1 or 2; 0 when the fused path does not cover the loop at all). */
 int gnn_loop_set_tile_form(gnn_loop *l, int form, int *used);
+/* How the full-tile form-1 kernel (state width 64, impl 1 or 2, no feature-sliced exchange) finds a tile's neighbour rows:
+ *   form 1  it walks the CSR: row pointers, then ids / weights in batches of 16 per lane group of 8 rows, row ends found by comparison;
+ *   form 2  it reads the graph's gather program: the CSR walked once per graph and stored per tile and lane group in the order of
+ *           consumption, the tile's rows split into four contiguous ranges of near-equal entry count (gnn_gather_program_build).  The
+ *           program is built with the first Loop that takes this form, shared by the graphs derived from the same graph, and costs
+ *           about 9.2 bytes per arc of device memory; a graph for which it cannot be built (no memory, no full tile) runs form 1;
+ *   form 0  the library's choice (default).
+ * Every row's fmaf chain is the same in both forms: states, outputs and k are identical bit for bit.  *used (may be NULL) = the form the
+ * next run will take (0 when the fused path does not cover the loop at all); asking for the form builds the program if it is needed. */
+int gnn_loop_set_gather_form(gnn_loop *l, int form, int *used);
+/* ---- Test and diagnostic entry points of gather form 2: not part of the supported interface, they may change with the program's layout. ----
+ * The gather program of rows [0, n_rows) of a CSR graph (host code; tests/test_gather_program.py).  Per full 32-row tile t: hdr[2 t] = first
+ * 64-entry batch, hdr[2 t + 1] = batches; ent[(64 b + 16 g + j) 2 + {0, 1}] = {source word, weight bits} of entry j of lane group g in
+ * batch b.  Source word: adj_src << 8 | row-end bit 32 | tile-local row (low 5 bits); 0xfffffe00 | ... for an entry without a source (the
+ * one entry of an empty row, weight 0; padding behind a group's last row end, no row-end bit).  hdr ([2 (n_rows / 32)]) and ent may be
+ * NULL: *n_batches is always set, so a first call sizes ent.  Returns GNN_ERR_UNSUPPORTED when a source id does not fit (>= 2^23). */
+int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, const int32_t *adj_src, const float *adj_w, int32_t *hdr, int32_t *ent,
+                             int64_t *n_batches);
+/* Size and host build time of the program of g's graph: 0 tiles when it has none (yet).  Any pointer may be NULL. */
+int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *batches, int64_t *bytes, float *build_ms);
 /* per-kernel HIP-event timing of the last gnn_loop_run when profiling was enabled:
  * avg_iter_ms = mean duration of the per-iteration kernel(s), total_ms = whole loop on the stream. */
 int gnn_loop_set_profiling(gnn_loop *l, int enable);
