@@ -20,7 +20,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_mlp_create', 'gnn_mlp_set_weights', 'gnn_mlp_get_weights', 'gnn_mlp_reset_optimizer', 'gnn_mlp_forward', 'gnn_mlp_destroy', 'gnn_loop_create',
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
-           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params',
+           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -57,6 +57,28 @@ def loss_grad(loss_kind: int, targets, out, sample_weights, label_smoothing: flo
     _check(lib().gnn_loss_grad_ex(C.c_int(loss_kind), C.c_int64(o.shape[0]), C.c_int(o.shape[1]), _fp(t), _fp(o), _fp(w), C.c_double(label_smoothing),
                                   C.c_double(huber_delta), C.byref(loss), _fp(d)))
     return float(loss.value), d
+
+
+FORM_NAMES = {0: 'per_op', 1: 'mlp_fwd', 2: 'wide', 3: 'chain3', 4: 'wgrad_bf', 5: 'wgrad_f32'}      # GNN_FORM_* of include/gnn_hip.h
+
+
+def _forms_dict(out):
+    names = [FORM_NAMES[int(v)] for v in out[3:]]
+    return dict(forward=names[0::3], backward=names[1::3], wgrad=names[2::3], build_input=bool(out[1]), sweep_rows=int(out[2]))
+
+
+def train_forms(dims, activations, rates=None, n_rows=0, producer_dropout=True) -> dict:
+    """gnn_train_forms (host code, no device): the kernels a net of this description takes in a training step on n_rows rows -
+    dict(forward, backward, wgrad: one name of FORM_NAMES per Dense layer; build_input; sweep_rows).  rates: Dropout rate in front of every
+    Dense layer and of BatchNormalization (default: none); producer_dropout: net_state (True) or net_output."""
+    L = len(dims) - 1
+    if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
+    d = np.ascontiguousarray(dims, np.int32)
+    a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
+    r = _f32(rates if rates is not None else np.zeros(L + 1), (L + 1,))
+    out = np.zeros(3 + 3 * L, np.int32)
+    _check(lib().gnn_train_forms(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int64(int(n_rows)), C.c_int(bool(producer_dropout)), _ip(out)))
+    return _forms_dict(out)
 
 
 def split_f16(values, exponent=None):
@@ -635,6 +657,12 @@ class Loop:
             return out
 
         return dict(grads_state=split(gs, shp_s), grads_output=split(go, shp_o), bn_batch_state=bns[:kk], bn_batch_output=bno, d_nodes=dn, d_arcs=da)
+
+    def train_forms(self, net: int = 0) -> dict:
+        """gnn_loop_train_forms: what the last train_forward() / train_step() decided for net_state (0) or net_output (1), as train_forms()."""
+        out = np.zeros(3 + 3 * self._keep[1 + net].n, np.int32)
+        _check(lib().gnn_loop_train_forms(self._h, C.c_int(net), _ip(out)))
+        return _forms_dict(out)
 
     def set_impl(self, impl: int) -> int:
         used = C.c_int(0)

@@ -194,6 +194,8 @@ inline size_t net_zero_floats(const gnn_mlp *m, int max_calls)
 bool tg_many_rows(int64_t n);
 bool tg_wide(int n_in, int n_out);
 bool tg_wgrad_covers(int n_in, int n_out);
+bool tg_wgrad_bf(int n_out);      // which of the two weight-gradient kernels launch_wgrad_f32 takes
+int64_t tg_sweep_rows();
 bool fwd3_covers(const gnn_mlp *m);
 bool bwd3_covers(const gnn_mlp *m);
 int launch_gemm_f32(hipStream_t st, Buf &buf, int64_t n, int K, int n_cols, const float *X, const float *M, const float *bias, int act, int mode,
@@ -214,6 +216,8 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
                 gnn_comm *comm = nullptr, const InputBuild *build = nullptr);
 int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job = nullptr,
                  gnn_comm *comm = nullptr, int64_t n_global = 0);
+// the form net_setup decided, as the ints of gnn_train_forms (include/gnn_hip.h): out[3 + 3 n_layers]
+void net_forms(const Net &net, int *out);
 // out[t] += part[0][t] + ... + part[parts - 1][t], t < count (k_sum_parts)
 int net_sum_parts(hipStream_t st, int parts, int64_t count, const float *part, float *out);
 

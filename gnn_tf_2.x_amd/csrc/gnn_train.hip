@@ -923,6 +923,16 @@ extern "C" int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, co
     return train_backward(l, nullptr, d_out_nodes, d_state_extra, grads_state, grads_output, bn_batch_state, bn_batch_output, d_nodes_host, d_arcs_host, true);
 }
 
+// what the last training forward decided for one of the loop's nets (the context outlives the backward pass: until the next forward)
+extern "C" int gnn_loop_train_forms(const gnn_loop *l, int net, int *out)
+{
+    ARGCHK(l && out && (net == 0 || net == 1), "bad arguments");
+    const gnn_train_ctx *cx = l->train_ctx;
+    if (!cx) return gnn_fail(GNN_ERR_STATE, "gnn_loop_train_forward has not been called");
+    gnn_train::net_forms(net == 0 ? cx->ns : cx->no_, out);
+    return GNN_OK;
+}
+
 extern "C" int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w,
                                    const float *targets, const float *sample_weights, int64_t n_targets, int loss_kind,
                                    int n_graphs, const int32_t *ng_indptr, const int32_t *ng_node, const float *ng_w,

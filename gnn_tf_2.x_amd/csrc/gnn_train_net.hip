@@ -741,6 +741,26 @@ static void net_decide_form(Net &net, int64_t n, bool producer_dropout)
     }
 }
 
+// What net_forward / net_backward launch for a decided form, layer by layer (read-only: the tests' view of the decision)
+void net_forms(const Net &net, int *out)
+{
+    const gnn_mlp *m = net.m;
+    const int L = m->n_layers;
+    out[0] = L; out[1] = net.build_input ? 1 : 0; out[2] = (int)tg_sweep_rows();
+    for (int l = 0; l < L; ++l) {
+        int *o = out + 3 + 3 * l;
+        o[0] = o[1] = o[2] = GNN_FORM_PER_OP;
+        if (net.rows <= 0) continue;                                     // no rows: nothing is launched
+        if (net.fwd3) o[0] = GNN_FORM_CHAIN3;
+        else if (net.small_fused) o[0] = GNN_FORM_MLP_FWD;
+        else if (net.wide_fwd[l]) o[0] = GNN_FORM_WIDE;
+        if (net.bwd3 || net.wide_bwd[l]) {
+            o[1] = net.bwd3 ? GNN_FORM_CHAIN3 : GNN_FORM_WIDE;
+            o[2] = tg_wgrad_bf(m->dims[l + 1]) ? GNN_FORM_WGRAD_BF : GNN_FORM_WGRAD_F32;
+        }
+    }
+}
+
 // zero_mem: net_zero_floats() floats the caller has zeroed (one memset for everything a step needs zeroed); rows, producer_dropout: net_decide_form
 int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
               int64_t rows, bool producer_dropout)
@@ -1046,3 +1066,21 @@ int net_sum_parts(hipStream_t st, int parts, int64_t count, const float *part, f
 }
 
 }   // namespace gnn_train
+
+// The form a net of this description would take on n_rows rows (include/gnn_hip.h): host code, no device
+extern "C" int gnn_train_forms(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int producer_dropout, int *out)
+{
+    ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && rates && n_rows >= 0 && out, "bad arguments");
+    gnn_mlp m;
+    m.n_layers = n_layers;
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.acts.assign(acts, acts + n_layers);
+    for (int l = 0; l <= n_layers; ++l) ARGCHK(m.dims[l] >= 1, "bad layer width");
+    for (int l = 0; l < n_layers; ++l) ARGCHK(m.acts[l] >= GNN_ACT_LINEAR && m.acts[l] <= GNN_ACT_SOFTMAX, "bad activation code");
+    gnn_train::Net net;
+    net.m = &m;
+    net.rate.assign(rates, rates + n_layers + 1);
+    gnn_train::net_decide_form(net, n_rows, producer_dropout != 0);
+    gnn_train::net_forms(net, out);
+    return GNN_OK;
+}

@@ -20,6 +20,7 @@ namespace {
 // ALUs before (profiles/r03_train_c3.txt).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int TG_WAVES = 8;
+constexpr int TG_MAX_GRID = 256;                       // blocks of the persistent kernels (k_gemm_*, k_fwd3_split, k_bwd3_split): a wave takes tile after tile beyond that
 constexpr int64_t GNN_TRAIN_MFMA_MIN_ROWS = 4096;      // below that a step is launch-bound (MUTAG batches: 570 rows) and the per-op kernels are as fast
 
 // packed A operand of layer_from_lds for output columns [col0, col0 + 32 NO) of M [K, n_cols]: wp[(kk 64 + lane) NO + j] =
@@ -479,7 +480,7 @@ int launch_gemm_f32(hipStream_t st, Buf &buf, int64_t n, int K, int n_cols, cons
     const size_t lds = sizeof(float) * ((size_t)TG_WAVES * 32 * p.KP + 32 + 128) + 16;
     if (lds > 160 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "layer input width %d too large for the matrix-core path", K);
     const int64_t n_tiles = (n + 31) / 32;
-    const unsigned grid = (unsigned)std::min<int64_t>(256, (n_tiles + TG_WAVES - 1) / TG_WAVES);
+    const unsigned grid = (unsigned)std::min<int64_t>(TG_MAX_GRID, (n_tiles + TG_WAVES - 1) / TG_WAVES);
     for (int col0 = 0; col0 < n_cols;) {
         const int left = (n_cols - col0 + 31) / 32, NO = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
         int rc;
@@ -548,7 +549,7 @@ int launch_fwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, int64_t n, const flo
     const size_t lds = sizeof(float) * ((size_t)TG_WAVES * 32 * p.KP + 32 + 320) + 16;
     if (lds > 160 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "fused forward: LDS");
     const int64_t n_tiles = (n + 31) / 32;
-    const unsigned grid = (unsigned)std::min<int64_t>(256, (n_tiles + TG_WAVES - 1) / TG_WAVES);
+    const unsigned grid = (unsigned)std::min<int64_t>(TG_MAX_GRID, (n_tiles + TG_WAVES - 1) / TG_WAVES);
     switch (p.act) {
     case GNN_ACT_LINEAR: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_LINEAR>), grid, 64 * TG_WAVES, lds, st, p); break;
     case GNN_ACT_RELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_RELU>), grid, 64 * TG_WAVES, lds, st, p); break;
@@ -778,7 +779,7 @@ int launch_bwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, float *const *WT, in
     const size_t lds = sizeof(float) * ((size_t)TG_WAVES * 32 * p.KP + 32 + 128) + 16;
     if (lds > 160 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "fused backward: LDS");
     const int64_t n_tiles = (n + 31) / 32;
-    const unsigned grid = (unsigned)std::min<int64_t>(256, (n_tiles + TG_WAVES - 1) / TG_WAVES);
+    const unsigned grid = (unsigned)std::min<int64_t>(TG_MAX_GRID, (n_tiles + TG_WAVES - 1) / TG_WAVES);
     hipLaunchKernelGGL(k_bwd3_split, grid, 64 * TG_WAVES, lds, st, p);
     HIPCHK(hipGetLastError());
     return GNN_OK;
@@ -1046,17 +1047,10 @@ int launch_wgrad_f32(hipStream_t st, int64_t n, int64_t rpb, int parts, int64_t 
     WgradArgs p{n, rpb, pstride, n_in, n_out, H, DZ, part};
     const int mt = (n_in + 1 + 31) / 32, nt = (n_out + 31) / 32;
     const int nt2 = nt >= 2 ? 2 : 1;
-    {   // split-bf16 form (k_wgrad_bf) when the d z tiles divide the eight waves of a block; the f32-MFMA form (k_wgrad_f32) otherwise
-        bool bf = nt == 1 || nt == 2 || nt == 4;
-#ifdef GNN_DIAG
-        static const bool bf_off = getenv("GNN_TRAIN_WGRAD_BF") && atoi(getenv("GNN_TRAIN_WGRAD_BF")) == 0;
-        if (bf_off) bf = false;
-#endif
-        if (bf) {
+    if (tg_wgrad_bf(n_out)) {
 #define GNN_WGB_CASE(M_, N_) if (mt == M_ && nt == N_) { hipLaunchKernelGGL((k_wgrad_bf<M_, N_>), dim3((unsigned)parts), 512, 0, st, p); HIPCHK(hipGetLastError()); return GNN_OK; }
-            GNN_WGB_CASE(3, 1) GNN_WGB_CASE(3, 2) GNN_WGB_CASE(3, 4) GNN_WGB_CASE(4, 1) GNN_WGB_CASE(4, 2) GNN_WGB_CASE(4, 4) GNN_WGB_CASE(5, 1) GNN_WGB_CASE(5, 2) GNN_WGB_CASE(5, 4)
+        GNN_WGB_CASE(3, 1) GNN_WGB_CASE(3, 2) GNN_WGB_CASE(3, 4) GNN_WGB_CASE(4, 1) GNN_WGB_CASE(4, 2) GNN_WGB_CASE(4, 4) GNN_WGB_CASE(5, 1) GNN_WGB_CASE(5, 2) GNN_WGB_CASE(5, 4)
 #undef GNN_WGB_CASE
-        }
     }
     const dim3 grid((unsigned)parts, (unsigned)((nt + nt2 - 1) / nt2));
 #ifdef GNN_DIAG
@@ -1077,5 +1071,17 @@ int launch_wgrad_f32(hipStream_t st, int64_t n, int64_t rpb, int parts, int64_t 
     return gnn_fail(GNN_ERR_UNSUPPORTED, "no matrix-core weight-gradient instantiation for %d x %d tiles", mt, nt2);
 }
 bool tg_wgrad_covers(int n_in, int n_out) { const int mt = (n_in + 1 + 31) / 32; return mt >= 3 && mt <= 5 && n_out >= 32; }
+// split-bf16 form (k_wgrad_bf) when the d z tiles divide the eight waves of a block; the f32-MFMA form (k_wgrad_f32) otherwise
+bool tg_wgrad_bf(int n_out)
+{
+    const int nt = (n_out + 31) / 32;
+#ifdef GNN_DIAG
+    static const bool bf_off = getenv("GNN_TRAIN_WGRAD_BF") && atoi(getenv("GNN_TRAIN_WGRAD_BF")) == 0;
+    if (bf_off) return false;
+#endif
+    return nt == 1 || nt == 2 || nt == 4;
+}
+// rows the persistent kernels cover before a wave takes its second tile
+int64_t tg_sweep_rows() { return (int64_t)32 * TG_WAVES * TG_MAX_GRID; }
 
 }   // namespace gnn_train

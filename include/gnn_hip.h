@@ -354,6 +354,23 @@ int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, const int32_
                              int64_t *n_batches);
 /* Size and host build time of the program of g's graph: 0 tiles when it has none (yet).  Any pointer may be NULL. */
 int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *batches, int64_t *bytes, float *build_ms);
+/* ---- Test entry points of the training step: read-only, not part of the supported interface. ----
+ * Which kernels the Dense layers of a net take in a training-mode forward / backward pass on n_rows rows per call (the decision of
+ * gnn_loop_train_forward; few rows: the per-op kernels or one launch for all layers, 4,096 rows and more: wide layers on the matrix cores).
+ * out receives 3 + 3 n_layers ints:
+ *   out[0] = n_layers; out[1] = 1 when the first forward kernel also builds the concat rows of a body; out[2] = rows the persistent
+ *   matrix-core kernels cover before a wave takes a second 32-row tile;
+ *   out[3 + 3 l] = forward form of Dense layer l: GNN_FORM_PER_OP (k_dense_fwd), GNN_FORM_MLP_FWD (all layers in k_mlp_fwd), GNN_FORM_WIDE (its
+ *   own matrix-core product, k_gemm_split) or GNN_FORM_CHAIN3 (inside k_fwd3_split);
+ *   out[4 + 3 l] = backward form: GNN_FORM_PER_OP (k_layer_bwd), GNN_FORM_WIDE (k_gemm_split on W^T) or GNN_FORM_CHAIN3 (inside k_bwd3_split);
+ *   out[5 + 3 l] = weight-gradient kernel: GNN_FORM_PER_OP (the tiles of k_layer_bwd), GNN_FORM_WGRAD_BF (k_wgrad_bf) or GNN_FORM_WGRAD_F32.
+ * gnn_train_forms (host code, no device): a net described by dims [n_layers + 1], acts [n_layers] (gnn_activation codes) and the Dropout
+ * rates [n_layers + 1] in front of every Dense layer and of BatchNormalization; producer_dropout != 0: net_state (the concat kernel applies
+ * the Dropout in front of the first layer), 0: net_output.  gnn_loop_train_forms: what the last gnn_loop_train_forward / gnn_loop_train_step
+ * of this loop decided for net 0 (net_state) or 1 (net_output); GNN_ERR_STATE before the first one. */
+enum { GNN_FORM_PER_OP = 0, GNN_FORM_MLP_FWD = 1, GNN_FORM_WIDE = 2, GNN_FORM_CHAIN3 = 3, GNN_FORM_WGRAD_BF = 4, GNN_FORM_WGRAD_F32 = 5 };
+int gnn_train_forms(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int producer_dropout, int *out);
+int gnn_loop_train_forms(const gnn_loop *l, int net, int *out);
 /* per-kernel HIP-event timing of the last gnn_loop_run when profiling was enabled:
  * avg_iter_ms = mean duration of the per-iteration kernel(s), total_ms = whole loop on the stream. */
 int gnn_loop_set_profiling(gnn_loop *l, int enable);

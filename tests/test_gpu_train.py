@@ -656,7 +656,9 @@ def test_wide_layers_on_the_matrix_cores_match_oracle(n, with_dropout, d, hidden
     net).  Measured on this step (tools/dbg/train_acc.py, profiles/r03_train_c3.txt): split-bf16 products 1.1e-4, f32-MFMA chain 3.1e-4,
     per-op FP32-ALU kernels 2.6e-4 - the bias gradients are the least accurate arrays in all three.  A repeated step gives the same bits
     (per-chunk partials are added in a fixed order).  Without Dropout the backward chain of the three layers runs in ONE pass (k_bwd3_split,
-    round 5): also with hidden widths below 128 / a state narrower than 64 (zero-padded feature tiles) and a partial last 32-row tile."""
+    round 5): also with hidden widths below 128 / a state narrower than 64 (zero-padded feature tiles) and a partial last 32-row tile.
+    Whole steps of three bodies at the tolerances of the small-shape tests; the kernels one by one - every instantiation, second tiles, single
+    rows, at the float32 noise of the oracle - are in tests/test_gpu_train_forms.py."""
     from GNN import _engine as e
     rng = np.random.default_rng(n)
     nl, al, max_it = 3, 1, 3
@@ -705,8 +707,9 @@ def test_wide_layers_on_the_matrix_cores_match_oracle(n, with_dropout, d, hidden
 def test_train_step_random_shapes():
     """gnn_loop_train_step on 14 seeded random shapes (state width 0 / 1 .. 64, 0 - 2 hidden layers of 1 .. 128 units, smooth activations -
     the kinks of relu / selu make single gradient entries jump between float32 and float64, DESIGN.md section 7 - with and without
-    BatchNormalization, 40 .. 9,000 nodes so that both the per-op and the matrix-core kernels take part): k, loss and every gradient array
-    against the float64 oracle, and identical bits on a repeated step."""
+    BatchNormalization, 40 .. 9,000 nodes): k, loss and every gradient array against the float64 oracle, and identical bits on a repeated
+    step.  With this seed every case has fewer than 4,096 rows or no wide layer: the per-op kernels and k_mlp_fwd run here, no matrix-core
+    form does (those: test_wide_layers_on_the_matrix_cores_match_oracle and tests/test_gpu_train_forms.py)."""
     from GNN import _engine as e
     rng = np.random.default_rng(20261006)
     for case in range(14):
