@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "gnn_hip.h"
+#include "gnn_fused.h"
 
 int gnn_fail(int code, const char *fmt, ...);
 
@@ -16,6 +17,21 @@ int gnn_fail(int code, const char *fmt, ...);
 // allocation before their first tile.
 hipError_t gnn_dev_malloc(void **p, size_t bytes);
 bool gnn_poison_enabled();
+
+// Dynamic LDS above 64 KiB is an attribute of a kernel ON A DEVICE: raised before the first launch of the launcher's `n` kernels on the current
+// device, noted in the launcher's table.  A device index outside the table gets the attribute with every launch.
+inline hipError_t gnn_raise_dynamic_lds(const void *const *kernels, int n, size_t bytes, bool (&raised)[64])
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool listed = dev >= 0 && dev < 64;
+    if (listed && raised[dev]) return hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i) e = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (listed && e == hipSuccess) raised[dev] = true;
+    return e;
+}
+inline hipError_t gnn_raise_dynamic_lds(const void *kernel, size_t bytes, bool (&raised)[64]) { return gnn_raise_dynamic_lds(&kernel, 1, bytes, raised); }
 
 #define HIPCHK(expr)                                                                             \
     do {                                                                                         \
@@ -301,6 +317,7 @@ struct gnn_loop {
     float *inp = nullptr;                   // unfused: materialised concat [n_rows, in_s]
     float *inv = nullptr;                   // fused: loop-invariant label block [n_rows, inv_w]
     uint64_t inv_version = 0;               // label_version of the graph the block was built from
+    bool inv_zeroed = false;                // the block's zero fill has been queued (by the first fused run, on the loop's stream)
     float *tmp[2] = {nullptr, nullptr};     // unfused: layer activations
     float *feats = nullptr, *out = nullptr, *otmp[2] = {nullptr, nullptr};
     int *flags = nullptr;                   // [(max_iter+2), world, GNN_FLAG_WORDS]
@@ -320,10 +337,10 @@ struct gnn_loop {
     int kfinal = -1;
     bool have_state0 = false, ran = false;
     bool graph_ready_seen = false;          // this loop's stream has waited for the graph's creation-time fills
-    int impl_req = 1, impl_used = 0;
+    int impl_req = 1;
     int tile_form = 0;                      // gnn_loop_set_tile_form: 0 library's choice, 1 one wave per tile, 2 wave pair per tile
     int gather_form = 0;                    // gnn_loop_set_gather_form: 0 library's choice, 1 walk the CSR, 2 the graph's gather program
-    bool gather_program = false;            // this run's launches read the program: decided once per run by gnn_fused_prepare
+    LoopForm form;                          // launch form of the current run (gnn_fused.h): decided afresh by every loop_prepare, nothing of it outlives a run
     int32_t *ng_ip = nullptr, *ng_node = nullptr;   // cached NodeGraph^T (graph readout)
     float *ng_w = nullptr, *ng_out = nullptr, *ng_part = nullptr;   // ng_part [world, G, T]: per-rank partial readouts
     std::vector<int32_t> ng_key;
@@ -369,36 +386,35 @@ struct gnn_loop {
 // the graph readout of the loop's LAST run was computed inside that run's persistent launch (result in ng_host)
 inline bool gnn_loop_ng_folded(const gnn_loop *l) { return l->ng_inlaunch && l->ng_inlaunch_run == l->out_runs; }
 
-// gnn_engine.hip
+// gnn_graph.hip
 int gnn_graph_wait_ready(const gnn_graph *g, hipStream_t st);
+// gnn_engine.hip
 int gnn_launch_spmm(hipStream_t st, int64_t n_rows, const int32_t *indptr, const int32_t *idx, const float *w, const float *X,
                     int width, int64_t ldx, float *out, int64_t ldo, const int *gate, int world);
-
 int gnn_launch_dense(hipStream_t st, int64_t n, int n_in, int n_out, const float *X, int64_t ldx, const float *W, const float *b,
                      int act, float *Y, int64_t ldy);
 int gnn_launch_check(hipStream_t st, int64_t n_rows, int d, const float *s, const float *so, float thr, int *flag_rank_base);
-// all-gather of `count` 4-byte elements per rank on an RCCL communicator (one process per rank; recv: [world][count], in place when
+// gnn_comm.hip: all-gather of `count` 4-byte elements per rank on an RCCL communicator (one process per rank; recv: [world][count], in place when
 // send == recv + rank * count), queued on st - for the translation units that do not see the RCCL table (gnn_train.hip, gnn_train_net.hip)
 int gnn_comm_allgather32(gnn_comm *c, const void *send, void *recv, size_t count, hipStream_t st);
-// GNNedgeBased.apply_filters on `state` (training path): feats [n_edge_masked, 2 (Ds + NLc) + AL]
+// gnn_loop.hip: GNNedgeBased.apply_filters on `state` (training path): feats [n_edge_masked, 2 (Ds + NLc) + AL]
 int gnn_launch_feats_edge(hipStream_t st, const gnn_loop *l, const float *state, float *feats);
-
+// gnn_engine.hip
 int gnn_launch_copy_cols(hipStream_t st, int64_t n_rows, int w, const float *src, int64_t lds_, float *dst, int64_t ldd, const int *gate, int world);
-
 int gnn_mlp_refresh_bn(gnn_mlp *m, hipStream_t st);
 // gnn_train.hip
 void gnn_train_ctx_free(gnn_loop *l);
 void gnn_train_arena_free(gnn_loop *l);
 
 // gnn_fused.hip
-bool gnn_fused_supported(const gnn_loop *l);
-bool gnn_fused_pair_selected(const gnn_loop *l);   // the default path's bodies run as k_fused_pair (wave pair per tile) rather than k_fused
-bool gnn_fused_program_selected(const gnn_loop *l);   // the bodies run as the full-tile k_fused and gather from the graph's program (built on demand)
+// the launch form of the loop's next run into l->form (gnn_fused.h); packs the weight images, builds the graph's gather program and
+// allocates the label block where the form needs them
+int gnn_loop_decide_form(gnn_loop *l);
+inline int gnn_loop_impl_used(const gnn_loop *l) { return l->form.path == GNN_PATH_UNFUSED ? 0 : (l->form.split ? 2 : 1); }
 // gnn_build.hip
 int gnn_gather_program_ensure(const gnn_graph *g);
 int gnn_fused_prepare(gnn_loop *l);
 int gnn_fused_pack(gnn_mlp *m, int nlc);
 int gnn_fused_iteration(gnn_loop *l, int k);
-bool gnn_small_supported(const gnn_loop *l);   // persistent small-graph loop (gnn_small.hip): all bodies in one launch
-int gnn_small_run(gnn_loop *l, bool *output_done);
+int gnn_small_run(gnn_loop *l);                // persistent small-graph loop (gnn_small.hip): all bodies in one launch
 void gnn_fused_release(gnn_mlp *m);

@@ -11,7 +11,7 @@ constexpr int GNN_FUSED_THREADS = 64 * GNN_FUSED_WAVES;
 #define GNN_F16_EX 4
 #define GNN_F16_LIMIT 65504.0f
 // Source word of a gather-program entry: the byte offset of the neighbour's 256-byte state row (source id << 8; the replica is < 2 GiB by the
-// fused path's precondition, gnn_fused_supported), in the low byte the tile-local row the entry belongs to and "this entry ends its row".
+// fused path's precondition, gnn_loop_decide_form), in the low byte the tile-local row the entry belongs to and "this entry ends its row".
 // GNN_GP_NOROW is an offset no replica reaches (any offset >= 2^31 would do; this one keeps the 16-byte access of the last lane, 0xfffffef0
 // .. 0xfffffeff, clear of the 2^32 wrap): a raw buffer load past the descriptor's range returns zeros (padding, and the single entry of an
 // empty row).  That such a load costs no memory fetch is the ISA's description of the range check, not something a counter run has shown.
@@ -109,6 +109,50 @@ struct GnnSmallCtl {
     float *ng_host;
     int G, ro_word;
     int ecache;              // arcs of a tile whose ids / weights may be kept in LDS (GNN_SMALL_ECACHE; 0: none)
+};
+
+// Layout of a net_state's packed weight images and of the kernels' LDS tile (gnn_fused.hip, make_plan): a function of the net's widths and
+// activations and of the loop's node-label columns alone.
+struct FusedPlan {
+    int layers = 0, NT = 0, NTL = 0, KP = 0, kk0 = 0, act = 0;
+    // split arithmetic, state width 64 (the tuned shape): the LDS tile is laid out for 16-byte accesses - rows 16-byte aligned
+    // (KPs a multiple of 4 with KPs / 4 odd: ds_read_b128 down a column stays bank-conflict free) and the aggregated-state block
+    // starting on a multiple of 4 columns, i.e. after a hole of `pad` zero columns behind [state | nodes]
+    int pad = 0, KPs = 0;
+    int nt[GNN_FUSED_MAXL] = {0, 0, 0};       // tiles of each layer's output
+    int kk[GNN_FUSED_MAXL] = {0, 0, 0};       // K-steps of each layer
+    size_t w_off[GNN_FUSED_MAXL] = {0, 0, 0}, b_off[GNN_FUSED_MAXL] = {0, 0, 0}, bn_off = 0, total = 0;
+    // split arithmetic (impl 2): K = 16 chunks per layer and the dword offsets of the piece images, bf16 x 3 (s_off) and fp16 x 2 (h_off),
+    // one after the other in one buffer
+    int chunks[GNN_FUSED_MAXL] = {0, 0, 0};
+    size_t s_off[GNN_FUSED_MAXL] = {0, 0, 0}, h_off[GNN_FUSED_MAXL] = {0, 0, 0}, s_total = 0;
+};
+
+// The launch form of one run of a Loop: everything about its launches that cannot change between the first body and the last.  Decided by
+// gnn_loop_decide_form (gnn_fused.hip) in every loop_prepare - its inputs (the requested impl / pieces / tile form / gather form, the
+// exchange layout, profiling, "the persistent loop gave up", the weights, the graph's labels) may all have changed since the last run, so
+// nothing of it is kept from run to run - and by the setters, which answer `used` from it.
+enum GnnLoopPath { GNN_PATH_UNFUSED = 0, GNN_PATH_BODIES = 1, GNN_PATH_PERSISTENT = 2 };      // one kernel per TF op / one launch per body / all bodies in one launch
+enum GnnBodyKernel { GNN_BODY_GENERIC = 0, GNN_BODY_FULL_TILE = 1, GNN_BODY_PAIR = 2 };       // k_fused / its full-tile specialisation / k_fused_pair
+struct LoopForm {
+    int path = GNN_PATH_UNFUSED;
+    // the per-body kernel of a fused loop (on the persistent path: what a run with one launch per body would take; the setters report it)
+    int kernel = GNN_BODY_GENERIC;
+    bool split = false;              // split arithmetic (impl 2) rather than the exact f32 MFMA (impl 1)
+    int pieces = 3;                  // piece format of the split arithmetic
+    bool program = false;            // the full-tile kernel gathers from the graph's program
+    // launch constants of the path's launches
+    FusedPlan plan;
+    unsigned grid = 0;
+    size_t lds = 0;                  // dynamic LDS bytes
+    // every field that is constant for the run; a body sets state_cur, state_nxt, gate, flag_out and tile_ctr (the start-up spread and
+    // single_ticket are in it).  Persistent path: the arguments of that launch (exact arithmetic, unpadded tile, no gates)
+    GnnFusedArgs args;
+    // persistent path: 16- or 32-node tiles, the instantiated layer-0 K-step count (kk_small of k_small_loop / s0 of k_small16), and
+    // whether the output stage and the graph readout run inside the launch; ctl holds everything but the run-parity gate words
+    int small_tile = 0, kk_small = 0, s0 = 0;
+    bool fold_output = false, fold_readout = false;
+    GnnSmallCtl ctl;
 };
 
 // LDS layout of the persistent small-graph loop (gnn_small_common.h), in 4-byte words, for ROWS = 32 (k_small_loop) or 16 (k_small16) rows

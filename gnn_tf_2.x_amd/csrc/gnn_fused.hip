@@ -1,5 +1,5 @@
 // Host side of the fused iteration kernel (device code: gnn_fused_kernel.h): which nets it covers, the packed weight
-// image, the loop-invariant label block, and the per-iteration launch.
+// image, the loop-invariant label block, the launch form of a run (gnn_loop_decide_form) and the per-iteration launch.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,21 +16,6 @@ namespace {
 constexpr int MAXL = GNN_FUSED_MAXL;
 constexpr int K_GROUP = 12;     // layer-0 K-steps are consumed in pipelined groups of 3 x 4 (layer_from_lds)
 constexpr int K_SLACK = 8;      // zero K-steps after the layer-0 block: the pipeline prefetches two groups past the end
-
-struct FusedPlan {
-    int layers = 0, NT = 0, NTL = 0, KP = 0, kk0 = 0, act = 0;
-    // split arithmetic, state width 64 (the tuned shape): the LDS tile is laid out for 16-byte accesses - rows 16-byte aligned
-    // (KPs a multiple of 4 with KPs / 4 odd: ds_read_b128 down a column stays bank-conflict free) and the aggregated-state block
-    // starting on a multiple of 4 columns, i.e. after a hole of `pad` zero columns behind [state | nodes]
-    int pad = 0, KPs = 0;
-    int nt[MAXL] = {0, 0, 0};       // tiles of each layer's output
-    int kk[MAXL] = {0, 0, 0};       // K-steps of each layer
-    size_t w_off[MAXL] = {0, 0, 0}, b_off[MAXL] = {0, 0, 0}, bn_off = 0, total = 0;
-    // split arithmetic (impl 2): K = 16 chunks per layer and the dword offsets of the piece images, bf16 x 3 (s_off) and fp16 x 2 (h_off),
-    // one after the other in one buffer
-    int chunks[MAXL] = {0, 0, 0};
-    size_t s_off[MAXL] = {0, 0, 0}, h_off[MAXL] = {0, 0, 0}, s_total = 0;
-};
 
 constexpr int GNN_FUSED_VARIANT_DEFAULT = 1;      // bit 0: raised wave priority during the gather (measured: -1 %)
 // start-up spread: every wave waits 0 .. n x 8k cycles before its first tile.  Round 2 / 3 (two tickets per wave drawn at kernel start, which
@@ -134,32 +119,6 @@ int device_cus(int device)
 }
 
 }   // namespace
-
-// The library's choice between the two forms of the default path's kernel (gnn_loop_set_tile_form(l, 0)): the wave pair while no pair of the
-// launch gets a second tile (tiles <= 4 x CUs: the launch is one tile latency long and a pair's tile takes about half as long as a wave's:
-// N = 4 k .. 32 k: 7 - 11 % less time per iteration), one wave per tile beyond (N = 41 k: +13 %, BASELINE size: 0.78 against 0.68 ms -
-// the seven meetings of a pair per tile cost more than its shorter matrix phases return; profiles/r05_midsize_forms.txt, r05_pair_stamps.txt).
-bool gnn_fused_pair_selected(const gnn_loop *l)
-{
-    FusedPlan p;
-    if (l->impl_req != 2 || l->slice_mode || !make_plan(l->st, l->NLc, p)) return false;
-    if (!pair_covers(p, l->Ds) || pair_lds_bytes(p) > 160 * 1024) return false;
-    if (l->tile_form) return l->tile_form == 2;
-    return (l->g->n_rows + 31) / 32 <= (int64_t)4 * device_cus(l->device);
-}
-
-// Whether the loop's bodies gather from the graph's program (gnn_loop_set_gather_form): the launch must be the full-tile form of k_fused that
-// gathers (state width 64, a net with a 64-wide last layer, no feature-sliced exchange, not the wave pair), and the graph must have a program
-// - it is built here, on first demand.
-bool gnn_fused_program_selected(const gnn_loop *l)
-{
-    FusedPlan p;
-    if (l->impl_req < 1 || l->slice_mode || l->Ds != 64 || !make_plan(l->st, l->NLc, p) || p.NTL != 2) return false;
-    if ((l->gather_form ? l->gather_form : GNN_GATHER_FORM_DEFAULT) != 2) return false;
-    if (l->impl_req == 2 && gnn_fused_pair_selected(l)) return false;
-    if (gnn_gather_program_ensure(l->g) != GNN_OK) return false;
-    return l->g->sh->gp_ent != nullptr;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
@@ -291,11 +250,12 @@ void gnn_fused_release(gnn_mlp *m)
     m->packed_split_dwords = 0;
 }
 
-bool gnn_fused_supported(const gnn_loop *l)
+// The feasibility part of the form decision: the plan of the loop's net_state, its weight images - packed HERE when the weights (or the
+// concat layout) changed since they were built - and the shape limits of the kernels.
+static bool gnn_fused_supported(gnn_loop *l, FusedPlan &p)
 {
-    FusedPlan p;
     if (!make_plan(l->st, l->NLc, p)) return false;
-    if (l->st->pack_dirty || l->st->pack_nlc != l->NLc) {            // weights (or the concat layout) changed since the images were built
+    if (l->st->pack_dirty || l->st->pack_nlc != l->NLc) {
         if (gnn_fused_pack(l->st, l->NLc) != GNN_OK) return false;
         l->st->pack_dirty = false;
     }
@@ -307,16 +267,18 @@ bool gnn_fused_supported(const gnn_loop *l)
     return l->g->n_rows > 0;
 }
 
+// label block [n_rows, IW]; rows padded to whole 32-node tiles and zeroed: the full-tile kernel reads the label columns of a partial last
+// tile unguarded
+static size_t inv_floats(const gnn_loop *l) { return std::max<size_t>(1, (size_t)((l->g->n_rows + 31) / 32 * 32) * (2 * l->NLc + l->g->AL)); }
+
+// the loop-invariant label block of a fused run (allocated by the form decision)
 int gnn_fused_prepare(gnn_loop *l)
 {
     const gnn_graph *g = l->g;
-    l->gather_program = gnn_fused_program_selected(l);      // once per run (the first one builds the graph's program), not per launch
     const int IW = 2 * l->NLc + g->AL;
-    if (!l->inv) {
-        // (rows padded to whole 32-node tiles and zeroed: the full-tile kernel reads the label columns of a partial last tile unguarded)
-        const size_t inv_floats = std::max<size_t>(1, (size_t)((g->n_rows + 31) / 32 * 32) * IW);
-        HIPCHK(gnn_dev_malloc((void **)&l->inv, inv_floats * sizeof(float)));
-        HIPCHK(hipMemsetAsync(l->inv, 0, inv_floats * sizeof(float), l->stream));
+    if (!l->inv_zeroed) {
+        HIPCHK(hipMemsetAsync(l->inv, 0, inv_floats(l) * sizeof(float), l->stream));
+        l->inv_zeroed = true;
     }
     if (IW == 0) return GNN_OK;
     // [nodes | Adjacency^T . nodes | ArcNode^T . arc labels]  (GNN.py:263, :259): loop-invariant, and unchanged from run to run
@@ -336,21 +298,16 @@ int gnn_fused_prepare(gnn_loop *l)
     return GNN_OK;
 }
 
-// everything of the kernel arguments that does not depend on the launch geometry; split: arithmetic mode / tile layout
-static int fused_args(gnn_loop *l, int k, bool split, FusedPlan &p, GnnFusedArgs &a)
+// the kernel arguments that depend neither on the body nor on the launch geometry; split: arithmetic mode / tile layout
+static void fill_args(const gnn_loop *l, const FusedPlan &p, bool split, GnnFusedArgs &a)
 {
     const gnn_graph *g = l->g;
     const gnn_mlp *m = l->st;
-    if (!make_plan(m, l->NLc, p)) return gnn_fail(GNN_ERR_UNSUPPORTED, "fused path does not cover this net_state");
-    if (m->pack_nlc != l->NLc) return gnn_fail(GNN_ERR_STATE, "weight image laid out for another label width");
-    const int cur = k & 1, nxt = cur ^ 1, P = l->world;
     a = GnnFusedArgs{};
     a.n_rows = g->n_rows; a.row_begin = l->own_off;     // replica row of the first owned row
     a.indptr = g->sh->indptr; a.adj_src = g->sh->adj_src; a.adj_w = g->sh->adj_w;
     a.inv = l->inv;
-    a.state_cur = l->state[cur];
     a.state_bytes = (int64_t)l->N_pad * l->Ds * (int64_t)sizeof(float);
-    a.state_nxt = l->state[nxt] + (size_t)l->own_off * l->Ds;
     const int pad = split ? p.pad : 0;
     a.Ds = l->Ds; a.NLc = l->NLc; a.AL = g->AL; a.IW = 2 * l->NLc + g->AL; a.in_s = l->in_s + pad; a.c_aggs = l->Ds + l->NLc + pad;
     a.KP = split ? p.KPs : p.KP; a.kk0 = p.kk0;
@@ -378,50 +335,40 @@ static int fused_args(gnn_loop *l, int k, bool split, FusedPlan &p, GnnFusedArgs
     a.bn_scale = m->has_bn ? m->packed + p.bn_off : nullptr;
     a.bn_shift = m->has_bn ? m->packed + p.bn_off + 32 * p.NTL : nullptr;
     a.thr = l->thr;
-    a.gate = l->flags + (size_t)k * P * GNN_FLAG_WORDS;
-    a.flag_out = l->flags + ((size_t)(k + 1) * P + l->rank) * GNN_FLAG_WORDS;
-    a.world = P;
+    a.world = l->world;
     a.certify = split ? 1 : 0;
-    a.stamps = nullptr;
     a.agg_in = l->slice_mode ? l->agg_own : nullptr;
-    a.threads = 0;
     a.wstride = 1;
-    a.tile_base = 0;
-    a.full_tiles = 0;
-    return GNN_OK;
 }
 
-int gnn_fused_iteration(gnn_loop *l, int k)
+// the five fields of the arguments that depend on the body
+static void body_args(const gnn_loop *l, int k, GnnFusedArgs &a)
+{
+    const int cur = k & 1, P = l->world;
+    a.state_cur = l->state[cur];
+    a.state_nxt = l->state[cur ^ 1] + (size_t)l->own_off * l->Ds;
+    a.gate = l->flags + (size_t)k * P * GNN_FLAG_WORDS;
+    a.flag_out = l->flags + ((size_t)(k + 1) * P + l->rank) * GNN_FLAG_WORDS;
+    a.tile_ctr = l->tile_ctr + k;
+}
+
+// geometry of a run with one launch per body: grid, LDS, start-up spread, and what the recorded kernel takes beyond the common arguments
+static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
 {
     const gnn_graph *g = l->g;
-    FusedPlan p;
-    GnnFusedArgs a;
-    const bool split = l->impl_req == 2;
-    int rc = fused_args(l, k, split, p, a);
-    if (rc) return rc;
+    const FusedPlan &p = f.plan;
+    GnnFusedArgs &a = f.args;
+    fill_args(l, p, f.split, a);
     const size_t n_tiles = (size_t)((g->n_rows + 31) / 32);
-#ifdef GNN_DIAG
+#ifdef GNN_DIAG   // diagnostic build only (make DIAG=1): timing experiments; never in the shipped library
     static const int variant_env = getenv("GNN_FUSED_VARIANT") ? atoi(getenv("GNN_FUSED_VARIANT")) : GNN_FUSED_VARIANT_DEFAULT;
     a.variant = variant_env;
-#endif
-#ifdef GNN_DIAG   // diagnostic build only (make DIAG=1): timing experiments and per-wave phase stamps; never in the shipped library
     static const int debug = getenv("GNN_FUSED_DEBUG") ? atoi(getenv("GNN_FUSED_DEBUG")) : 0;
     a.wstride = (debug & 1) ? 0 : 1;                                  // 0: every K-step re-reads step 0 (results meaningless)
-    static const char *stamp_file = getenv("GNN_FUSED_STAMPS");       // dump per-wave phase stamps of body 1
-    static unsigned long long *stamp_buf = nullptr;
-    const size_t n_waves = n_tiles;
-    if (stamp_file && k == 1) {
-        if (!stamp_buf) HIPCHK(gnn_dev_malloc((void **)&stamp_buf, n_waves * 16 * sizeof(unsigned long long)));      // (8 slots per tile: k_fused; 16: k_fused_pair)
-        HIPCHK(hipMemsetAsync(stamp_buf, 0, n_waves * 16 * sizeof(unsigned long long), l->stream));
-        a.stamps = stamp_buf;
-    }
 #endif
-    if (l->device < 0 || l->device >= 64) return gnn_fail(GNN_ERR_ARG, "device %d out of range", l->device);
-    const int n_cu = device_cus(l->device);
     // one workgroup per CU; small graphs spread their tiles over as many CUs as they have tiles (a tile alone on a CU runs
     // faster than eight sharing its L1 / LDS / SIMDs; the waves without a tile leave at once)
     const unsigned grid = (unsigned)std::min<size_t>((size_t)n_cu, n_tiles);
-    a.tile_ctr = l->tile_ctr + k;
     int stagger_rounds = GNN_FUSED_SPREAD_DEFAULT;
 #ifdef GNN_DIAG
     static const int stagger_env = getenv("GNN_FUSED_STAGGER") ? atoi(getenv("GNN_FUSED_STAGGER")) : GNN_FUSED_SPREAD_DEFAULT;   // tuning experiments
@@ -440,102 +387,58 @@ int gnn_fused_iteration(gnn_loop *l, int k)
     // fewer tiles than waves: a wave that drew two tickets at start would run two tiles one after the other while another wave of the
     // launch gets none (N = 31k: 488 of 2,048 waves did all the work) - the look-ahead ticket is only drawn when every wave has a tile
     a.single_ticket = n_tiles <= (size_t)GNN_FUSED_WAVES * grid ? 1 : 0;
-    const size_t lds = lds_bytes(p);
-    a.lds_floats = gnn_poison_enabled() ? (int)(lds / sizeof(float)) : 0;
-    auto go = [&](const GnnFusedArgs &aa, unsigned gr) -> bool {
-        if (split) {
-            if (p.layers == 1) return gnn_fused_launch_s1(p.act, p.NT, p.NTL, aa, gr, lds, l->stream);
-            if (p.layers == 2) return gnn_fused_launch_s2(p.act, p.NT, p.NTL, aa, gr, lds, l->stream);
-            return gnn_fused_launch_s3(p.act, p.NT, p.NTL, aa, gr, lds, l->stream);
-        }
-        if (p.layers == 1) return gnn_fused_launch_l1(p.act, p.NT, p.NTL, aa, gr, lds, l->stream);
-        if (p.layers == 2) return gnn_fused_launch_l2(p.act, p.NT, p.NTL, aa, gr, lds, l->stream);
-        return gnn_fused_launch_l3(p.act, p.NT, p.NTL, aa, gr, lds, l->stream);
-    };
-    bool ok = false;
-    const int64_t n_tiles64 = (g->n_rows + 31) / 32;
-    bool pair = false;
-    if (split && gnn_fused_pair_selected(l)) {
+    f.grid = grid;
+    f.lds = lds_bytes(p);
+    if (f.kernel == GNN_BODY_PAIR) {
         // wave-pair form: four pairs per workgroup, one workgroup per CU; the tile counters, gates and flags are k_fused's
-        GnnFusedArgs ap = a;
-        ap.KP = pair_xs(p);
-        ap.full_tiles = 1; ap.tile_base = 0;
-        const unsigned grid_p = (unsigned)std::min<int64_t>((int64_t)n_cu, (n_tiles64 + 3) / 4);
-        ap.stagger = n_tiles64 >= (int64_t)4 * 4 * grid_p ? stagger_rounds : (n_tiles64 > (int64_t)4 * grid_p ? GNN_FUSED_SPREAD_SMALL_DEFAULT : 0);
-        const size_t lds_p = pair_lds_bytes(p);
-        ap.lds_floats = gnn_poison_enabled() ? (int)(lds_p / sizeof(float)) : 0;
-        pair = p.layers == 2 ? gnn_fused_launch_p2(p.act, ap, grid_p, lds_p, l->stream) : gnn_fused_launch_p3(p.act, ap, grid_p, lds_p, l->stream);
-    }
-    if (pair) ok = true;
-    else if (l->Ds == 64 && p.NTL == 2 && n_tiles64 >= 1) {
+        const int64_t n_tiles64 = (int64_t)n_tiles;
+        a.KP = pair_xs(p);
+        a.full_tiles = 1;
+        f.grid = (unsigned)std::min<int64_t>((int64_t)n_cu, (n_tiles64 + 3) / 4);
+        a.stagger = n_tiles64 >= (int64_t)4 * 4 * f.grid ? stagger_rounds : (n_tiles64 > (int64_t)4 * f.grid ? GNN_FUSED_SPREAD_SMALL_DEFAULT : 0);
+        f.lds = pair_lds_bytes(p);
+    } else if (f.kernel == GNN_BODY_FULL_TILE) {
         // the full-tile specialisation (no generic paths compiled in) on every tile; a partial last tile takes a wave-uniform
         // branch with masked row stores / condition votes (the row buffers are padded to whole tiles, rows past n_rows have no arcs)
-        GnnFusedArgs af = a;
-        af.full_tiles = 1; af.tile_base = 0;
-        if (l->gather_program) { af.gp_hdr = g->sh->gp_hdr; af.gp_ent = g->sh->gp_ent; af.gp_tiles = (int)g->sh->gp_tiles; }
-        ok = go(af, (unsigned)std::min<size_t>((size_t)n_cu, (size_t)n_tiles64));
-    } else
-        ok = go(a, grid);
-    if (!ok) return gnn_fail(GNN_ERR_UNSUPPORTED, "no fused instantiation for %d layers, tiles (%d,%d), activation %d", p.layers, p.NT, p.NTL, p.act);
-#ifdef GNN_DIAG
-    if (a.stamps) {
-        std::vector<unsigned long long> host(n_waves * (pair ? 16 : 8));
-        HIPCHK(hipStreamSynchronize(l->stream));
-        HIPCHK(hipMemcpy(host.data(), stamp_buf, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(stamp_file, "wb")) { fwrite(host.data(), sizeof(unsigned long long), host.size(), f); fclose(f); }
+        a.full_tiles = 1;
+        if (f.program) { a.gp_hdr = g->sh->gp_hdr; a.gp_ent = g->sh->gp_ent; a.gp_tiles = (int)g->sh->gp_tiles; }
     }
-#endif
-    HIPCHK(hipGetLastError());
-    return GNN_OK;
+    a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// persistent small-graph loop (device code: gnn_small_common.h, gnn_small.hip, gnn_small16.hip)
-// ---------------------------------------------------------------------------------------------------------------------
-bool gnn_small_supported(const gnn_loop *l)
+// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small.hip, gnn_small16.hip)
+static int decide_persistent(gnn_loop *l, LoopForm &f)
 {
-    if (l->world != 1 || l->impl_req < 1 || l->small_disabled || l->profiling) return false;
-    if (!gnn_fused_supported(l)) return false;
-    FusedPlan p;
-    if (!make_plan(l->st, l->NLc, p)) return false;
-    if (p.NT != 1 || p.NTL != 1) return false;                      // nets no wider than 32 (one 32-feature tile per layer)
-    const int64_t n_tiles = (l->g->n_rows + 31) / 32;
-    if (p.kk0 > 48) return false;                                   // layer-0 weights are kept in registers
-    return n_tiles >= 1 && n_tiles <= 256;                          // every tile resident at once (one wave each), with a wide margin
-}
-
-int gnn_small_run(gnn_loop *l, bool *output_done)
-{
-    FusedPlan p;
-    GnnFusedArgs a;
-    int rc = fused_args(l, 0, false, p, a);                          // exact f32-MFMA arithmetic, unpadded tile layout
-    if (rc) return rc;
     const gnn_graph *g = l->g;
-    a.gate = nullptr; a.flag_out = nullptr; a.tile_ctr = nullptr; a.stagger = 0;
-    GnnSmallCtl c{};
+    const FusedPlan &p = f.plan;
+    GnnFusedArgs &a = f.args;
+    fill_args(l, p, false, a);                                        // exact f32-MFMA arithmetic, unpadded tile layout; no gates, no tickets
+    a.state_cur = l->state[0];
+    a.state_nxt = l->state[1] + (size_t)l->own_off * l->Ds;
+    GnnSmallCtl &c = f.ctl;
     c.state0 = l->state[0]; c.state1 = l->state[1];
     c.init = l->D ? l->state_init : g->nodes + (size_t)g->own_off * g->NL;      // D == 0: NL == Ds (GNN.py:265)
     c.kfinal = l->kfinal_dev;
     c.host_result = l->kfinal_host;                                   // pinned, device-visible: no copy back
     // K-steps of layer 0 the kernels keep in registers: the smallest instantiated count that covers the concat width (32-node tiles: the
     // packed image has p.kk0 >= that many; the steps dropped are zero rows of the image)
-    int kk_small = p.kk0, s0 = 0;
+    f.kk_small = p.kk0;
     for (int cand : GnnSmallKK0::values)
-        if (2 * cand >= a.in_s && cand <= p.kk0) { kk_small = cand; break; }
+        if (2 * cand >= a.in_s && cand <= p.kk0) { f.kk_small = cand; break; }
     for (int cand : GnnSmall16S0::values)
-        if (4 * cand >= a.in_s) { s0 = cand; break; }
+        if (4 * cand >= a.in_s) { f.s0 = cand; break; }
     // 16-node tiles (gnn_small16.hip) while twice the workgroups are still resident at once (and an instantiation covers the concat width,
     // in_s <= 96): a body is a chain of latencies, and a 16-node tile's dense layers and activations are half as long
-    bool tile16 = g->n_rows <= 16 * 256 && s0 > 0;
+    bool tile16 = g->n_rows <= 16 * 256 && f.s0 > 0;
 #ifdef GNN_DIAG
     static const int tile_env = getenv("GNN_SMALL_TILE") ? atoi(getenv("GNN_SMALL_TILE")) : 0;
     if (tile_env == 32) tile16 = false;
 #endif
-    const int rows_per_tile = tile16 ? 16 : 32;
-    const unsigned grid = (unsigned)((g->n_rows + rows_per_tile - 1) / rows_per_tile);
+    f.small_tile = tile16 ? 16 : 32;
+    f.grid = (unsigned)((g->n_rows + f.small_tile - 1) / f.small_tile);
     c.DP = l->Ds <= 16 ? 16 : 32;
-    {   // padded exchange rows: allocated with the first persistent run of the loop, never initialised (every row is written before it is read)
-        const size_t need = (size_t)2 * grid * rows_per_tile * c.DP;
+    {   // padded exchange rows: allocated with the first persistent form of the loop, never initialised (every row is written before it is read)
+        const size_t need = (size_t)2 * f.grid * f.small_tile * c.DP;
         if (l->small_xs_floats < need) {
             if (l->small_xs) (void)hipFree(l->small_xs);
             l->small_xs = nullptr; l->small_xs_floats = 0;
@@ -550,22 +453,8 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
     static const int ecache_env = getenv("GNN_SMALL_ECACHE") ? atoi(getenv("GNN_SMALL_ECACHE")) : GNN_SMALL_ECACHE;
     c.ecache = std::min(GNN_SMALL_ECACHE, ecache_env);
 #endif
-    // Gate words: one per body, double-buffered by run parity at the start of the flag block.  This launch polls its own half
-    // and zeroes the other half for the next run, so a run costs no memset; both halves are cleared by the host only after
-    // something else (a per-body run) has used the block.
-    const size_t n_words = ((size_t)l->max_iter + 3 + 3) & ~(size_t)3;      // gate of every body, + 1, + the barrier in front of the folded graph readout
-    l->kfinal_host[1] = 0;                                            // status: cleared HERE, only ever set by the kernel (sticky)
-    if (!l->small_words_clean) {
-        HIPCHK(hipMemsetAsync(l->flags, 0, sizeof(int) * 2 * n_words, l->stream));
-        l->small_words_clean = true;
-        l->small_runs = 0;
-    }
-    c.flags = l->flags + (l->small_runs & 1) * n_words;
-    c.zero_words = l->flags + ((l->small_runs & 1) ^ 1) * n_words;
-    c.n_words = (int)n_words;
-    ++l->small_runs;
+    c.n_words = (int)(((size_t)l->max_iter + 3 + 3) & ~(size_t)3);      // gate of every body, + 1, + the barrier in front of the folded graph readout
     // output stage inside the launch when it is the usual one-layer head (same condition as k_out1)
-    *output_done = false;
     const gnn_mlp *ou = l->ou;
     if (!l->edge_mode && g->n_masked && ou->n_layers == 1 && l->T <= 8 && l->Ds + l->NLc <= 64 && l->Ds <= 32 && g->NL <= 32) {
         c.out = l->out; c.mask = g->sh->mask; c.mask_pos = g->sh->masked_rows + g->n_masked;
@@ -573,9 +462,8 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
         c.ow = ou->W[0]; c.ob = ou->b[0];
         c.obn_scale = ou->has_bn ? ou->bn_scale : nullptr; c.obn_shift = ou->has_bn ? ou->bn_shift : nullptr;
         c.NL = g->NL; c.NLc = l->NLc; c.T = l->T; c.oact = ou->acts[0];
-        *output_done = true;
+        f.fold_output = true;
         // graph readout in the same launch when a NodeGraph is already cached with the loop (gnn_loop_readout uploaded it after an earlier run)
-        l->ng_inlaunch = false;
         if (l->ng_ip && l->ng_G > 0 && g->n_masked == g->n_rows) {
             if (l->ng_host_floats < l->ng_G * l->T) {
                 if (l->ng_host) (void)hipHostFree(l->ng_host);
@@ -584,12 +472,134 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
             }
             if (l->ng_host) {
                 c.ng_ip = l->ng_ip; c.ng_node = l->ng_node; c.ng_w = l->ng_w; c.ng_host = l->ng_host; c.G = l->ng_G; c.ro_word = l->max_iter + 1;
-                l->ng_inlaunch = true;                            // (cleared again by run_loops if the launch gives up)
-                l->ng_inlaunch_run = l->out_runs;                 // ... and valid for THIS run's outputs only
+                f.fold_readout = true;
             }
         }
     }
     c.rnd = g->sh->max_degree > 8 ? 8 : 4;                       // entries per gather round
+    if (tile16) {
+        const gnn_mlp *m = l->st;
+        for (int q = 0; q < p.layers; ++q) { c.Wraw[q] = m->W[q]; c.din[q] = m->dims[q]; c.dout[q] = m->dims[q + 1]; }
+        c.KP16 = std::max((a.in_s + 3) / 4 * 4, 4 * f.s0);
+        if (c.KP16 % 8 == 0) c.KP16 += 4;                            // rows 16 bytes apart in the banks: the B-operand column reads do not conflict
+        f.lds = GnnSmallLds<16>::bytes(c.KP16);
+    } else
+        f.lds = GnnSmallLds<32>::bytes(p.KP);
+    a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
+    return GNN_OK;
+}
+
+// The launch form of the loop's next run (LoopForm, gnn_fused.h), from the loop's settings as they are now.
+//
+// Per-body kernel of the default path, the library's choice (gnn_loop_set_tile_form(l, 0)): the wave pair while no pair of the launch gets a
+// second tile (tiles <= 4 x CUs: the launch is one tile latency long and a pair's tile takes about half as long as a wave's: N = 4 k .. 32 k:
+// 7 - 11 % less time per iteration), one wave per tile beyond (N = 41 k: +13 %, BASELINE size: 0.78 against 0.68 ms - the seven meetings of
+// a pair per tile cost more than its shorter matrix phases return; profiles/r05_midsize_forms.txt, r05_pair_stamps.txt).
+// Gather form (gnn_loop_set_gather_form): the bodies read the graph's program when the launch is the full-tile form of k_fused that gathers
+// (state width 64, a net with a 64-wide last layer, no feature-sliced exchange, not the wave pair) and the graph has a program - it is
+// built here, on first demand.
+int gnn_loop_decide_form(gnn_loop *l)
+{
+    LoopForm &f = l->form;
+    f = LoopForm{};
+    if (l->impl_req < 1) return GNN_OK;
+    HIPCHK(hipSetDevice(l->device));
+    if (!gnn_fused_supported(l, f.plan)) return GNN_OK;               // (side effect 1: the weight images)
+    if (l->device < 0 || l->device >= 64) return gnn_fail(GNN_ERR_ARG, "device %d out of range", l->device);
+    const gnn_graph *g = l->g;
+    const FusedPlan &p = f.plan;
+    const int n_cu = device_cus(l->device);
+    const int64_t n_tiles = (g->n_rows + 31) / 32;
+    f.split = l->impl_req == 2;
+    f.pieces = l->pieces == 2 ? 2 : 3;
+    const bool pair = f.split && !l->slice_mode && pair_covers(p, l->Ds) && pair_lds_bytes(p) <= 160 * 1024 &&
+                      (l->tile_form ? l->tile_form == 2 : n_tiles <= (int64_t)4 * n_cu);
+    f.kernel = pair ? GNN_BODY_PAIR : (l->Ds == 64 && p.NTL == 2 ? GNN_BODY_FULL_TILE : GNN_BODY_GENERIC);
+    if (f.kernel == GNN_BODY_FULL_TILE && !l->slice_mode && (l->gather_form ? l->gather_form : GNN_GATHER_FORM_DEFAULT) == 2 &&
+        gnn_gather_program_ensure(g) == GNN_OK)                       // (side effect 2: the graph's gather program)
+        f.program = g->sh->gp_ent != nullptr;
+    // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
+    // 32-feature tile per layer), layer-0 weights kept in registers, every tile resident at once (one wave each) with a wide margin
+    const bool persistent = l->world == 1 && !l->small_disabled && !l->profiling && p.NT == 1 && p.NTL == 1 && p.kk0 <= 48 && n_tiles <= 256;
+    f.path = persistent ? GNN_PATH_PERSISTENT : GNN_PATH_BODIES;
+    // (side effect 3: the label block - the arguments point to it; gnn_fused_prepare zeroes and fills it when the loop runs)
+    if (!l->inv) HIPCHK(gnn_dev_malloc((void **)&l->inv, inv_floats(l) * sizeof(float)));
+    if (persistent) return decide_persistent(l, f);
+    decide_bodies(l, f, n_cu);
+    return GNN_OK;
+}
+
+// the recorded per-body kernel; false: no instantiation
+static bool launch_body(const LoopForm &f, const GnnFusedArgs &a, hipStream_t st)
+{
+    const FusedPlan &p = f.plan;
+    if (f.kernel == GNN_BODY_PAIR)
+        return p.layers == 2 ? gnn_fused_launch_p2(p.act, a, f.grid, f.lds, st) : gnn_fused_launch_p3(p.act, a, f.grid, f.lds, st);
+    if (f.split) {
+        if (p.layers == 1) return gnn_fused_launch_s1(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+        if (p.layers == 2) return gnn_fused_launch_s2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+        return gnn_fused_launch_s3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+    }
+    if (p.layers == 1) return gnn_fused_launch_l1(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+    if (p.layers == 2) return gnn_fused_launch_l2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+    return gnn_fused_launch_l3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+}
+
+// body k of a run whose form is one launch per body
+int gnn_fused_iteration(gnn_loop *l, int k)
+{
+    const LoopForm &f = l->form;
+    GnnFusedArgs a = f.args;
+    body_args(l, k, a);
+#ifdef GNN_DIAG   // diagnostic build only (make DIAG=1): per-wave phase stamps of body 1; never in the shipped library
+    static const char *stamp_file = getenv("GNN_FUSED_STAMPS");
+    static unsigned long long *stamp_buf = nullptr;
+    const size_t n_waves = (size_t)((l->g->n_rows + 31) / 32);
+    if (stamp_file && k == 1) {
+        if (!stamp_buf) HIPCHK(gnn_dev_malloc((void **)&stamp_buf, n_waves * 16 * sizeof(unsigned long long)));      // (8 slots per tile: k_fused; 16: k_fused_pair)
+        HIPCHK(hipMemsetAsync(stamp_buf, 0, n_waves * 16 * sizeof(unsigned long long), l->stream));
+        a.stamps = stamp_buf;
+    }
+#endif
+    const FusedPlan &p = f.plan;
+    if (!launch_body(f, a, l->stream))
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "no fused instantiation for %d layers, tiles (%d,%d), activation %d", p.layers, p.NT, p.NTL, p.act);
+#ifdef GNN_DIAG
+    if (a.stamps) {
+        std::vector<unsigned long long> host(n_waves * (f.kernel == GNN_BODY_PAIR ? 16 : 8));
+        HIPCHK(hipStreamSynchronize(l->stream));
+        HIPCHK(hipMemcpy(host.data(), stamp_buf, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (FILE *f_ = fopen(stamp_file, "wb")) { fwrite(host.data(), sizeof(unsigned long long), host.size(), f_); fclose(f_); }
+    }
+#endif
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// persistent small-graph loop (device code: gnn_small_common.h, gnn_small.hip, gnn_small16.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+int gnn_small_run(gnn_loop *l)
+{
+    const LoopForm &f = l->form;
+    const FusedPlan &p = f.plan;
+    GnnFusedArgs a = f.args;
+    GnnSmallCtl c = f.ctl;
+    // Gate words: one per body, double-buffered by run parity at the start of the flag block.  This launch polls its own half
+    // and zeroes the other half for the next run, so a run costs no memset; both halves are cleared by the host only after
+    // something else (a per-body run) has used the block.
+    const size_t n_words = (size_t)c.n_words;
+    l->kfinal_host[1] = 0;                                            // status: cleared HERE, only ever set by the kernel (sticky)
+    if (!l->small_words_clean) {
+        HIPCHK(hipMemsetAsync(l->flags, 0, sizeof(int) * 2 * n_words, l->stream));
+        l->small_words_clean = true;
+        l->small_runs = 0;
+    }
+    c.flags = l->flags + (l->small_runs & 1) * n_words;
+    c.zero_words = l->flags + ((l->small_runs & 1) ^ 1) * n_words;
+    ++l->small_runs;
+    l->ng_inlaunch = f.fold_readout;                                  // (cleared again by run_loops if the launch gives up)
+    if (f.fold_readout) l->ng_inlaunch_run = l->out_runs;             // ... and valid for THIS run's outputs only
 #ifdef GNN_DIAG
     static const char *small_stamp_file = getenv("GNN_SMALL_STAMPS");
     static unsigned long long *small_stamp_buf = nullptr;
@@ -599,20 +609,8 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
         a.stamps = small_stamp_buf;
     }
 #endif
-    bool launched;
-    if (tile16) {
-        const gnn_mlp *m = l->st;
-        for (int q = 0; q < p.layers; ++q) { c.Wraw[q] = m->W[q]; c.din[q] = m->dims[q]; c.dout[q] = m->dims[q + 1]; }
-        c.KP16 = std::max((a.in_s + 3) / 4 * 4, 4 * s0);
-        if (c.KP16 % 8 == 0) c.KP16 += 4;                            // rows 16 bytes apart in the banks: the B-operand column reads do not conflict
-        const size_t lds = GnnSmallLds<16>::bytes(c.KP16);
-        a.lds_floats = gnn_poison_enabled() ? (int)(lds / sizeof(float)) : 0;
-        launched = gnn_small16_launch(p.layers, p.act, s0, a, c, grid, lds, l->stream);
-    } else {
-        const size_t lds = GnnSmallLds<32>::bytes(p.KP);
-        a.lds_floats = gnn_poison_enabled() ? (int)(lds / sizeof(float)) : 0;
-        launched = gnn_small_launch(p.layers, p.act, kk_small, a, c, grid, lds, l->stream);
-    }
+    const bool launched = f.small_tile == 16 ? gnn_small16_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                                             : gnn_small_launch(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
     if (!launched)
         return gnn_fail(GNN_ERR_UNSUPPORTED, "no persistent-loop instantiation for %d layers, activation %d", p.layers, p.act);
     HIPCHK(hipGetLastError());
@@ -621,7 +619,7 @@ int gnn_small_run(gnn_loop *l, bool *output_done)
         unsigned long long host[256];
         HIPCHK(hipStreamSynchronize(l->stream));
         HIPCHK(hipMemcpy(host, small_stamp_buf, sizeof(host), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(small_stamp_file, "wb")) { fwrite(host, sizeof(unsigned long long), 256, f); fclose(f); }
+        if (FILE *fs = fopen(small_stamp_file, "wb")) { fwrite(host, sizeof(unsigned long long), 256, fs); fclose(fs); }
     }
 #endif
     return GNN_OK;      // k and the status word are written straight into the pinned host words

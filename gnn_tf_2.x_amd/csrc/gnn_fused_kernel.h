@@ -997,7 +997,7 @@ __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X
     int next_end = ipt[node + 1];
     v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
     // neighbour rows through a buffer descriptor: 32-bit byte offsets (src * 256 + 16 * lane-in-row) instead of 64-bit
-    // pointer arithmetic per row; the state replica is < 2 GiB by the fused path's precondition (gnn_fused_supported)
+    // pointer arithmetic per row; the state replica is < 2 GiB by the fused path's precondition (gnn_loop_decide_form)
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
     const int voff0 = gl * 16;
     float *xo = X + c_aggs + gl * 4;
@@ -1646,14 +1646,8 @@ inline void launch_one_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes
     if constexpr (FULL && !GIVEN && !PROG) {
         if (a.gp_tiles > 0) { launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, true>(a, grid, lds_bytes, st); return; }
     }
-    static bool raised[64] = {false};   // dynamic LDS above 64 KiB has to be requested once per kernel AND device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !raised[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (dev >= 0 && dev < 64) raised[dev] = true;
-    }
+    static bool lds_raised[64] = {false};   // (one table per instantiation)
+    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>), 160 * 1024, lds_raised);
     hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
 }
 // the split arithmetic in the piece format of the launch (a.pieces); the exact path has one

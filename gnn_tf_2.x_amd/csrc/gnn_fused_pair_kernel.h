@@ -450,13 +450,8 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_pair(const GnnFu
 template <int LAYERS, int ACT, int PC>
 inline void launch_pair_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    static bool raised[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !raised[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fused_pair<LAYERS, ACT, PC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (dev >= 0 && dev < 64) raised[dev] = true;
-    }
+    static bool lds_raised[64] = {false};
+    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_fused_pair<LAYERS, ACT, PC>), 160 * 1024, lds_raised);
     hipLaunchKernelGGL((k_fused_pair<LAYERS, ACT, PC>), grid, GNN_FUSED_THREADS, lds_bytes, st, a);
 }
 template <int LAYERS, int ACT>

@@ -456,13 +456,10 @@ inline int tg_kps(int K) { int kp = ((K + 15) / 16 * 16 + 3) / 4 * 4; if ((kp / 
 int launch_gemm_f32(hipStream_t st, Buf &buf, int64_t n, int K, int n_cols, const float *X, const float *M, const float *bias, int act, int mode,
                     const uint8_t *keep, float rate, const float *a_prev, float *Y)
 {
-    static bool raised = false;
-    if (!raised) {
-        const void *ks[6] = {reinterpret_cast<const void *>(&k_gemm_f32<4>), reinterpret_cast<const void *>(&k_gemm_f32<2>), reinterpret_cast<const void *>(&k_gemm_f32<1>),
-                             reinterpret_cast<const void *>(&k_gemm_split<4>), reinterpret_cast<const void *>(&k_gemm_split<2>), reinterpret_cast<const void *>(&k_gemm_split<1>)};
-        for (const void *k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        raised = true;
-    }
+    static bool lds_raised[64] = {false};
+    const void *ks[6] = {reinterpret_cast<const void *>(&k_gemm_f32<4>), reinterpret_cast<const void *>(&k_gemm_f32<2>), reinterpret_cast<const void *>(&k_gemm_f32<1>),
+                         reinterpret_cast<const void *>(&k_gemm_split<4>), reinterpret_cast<const void *>(&k_gemm_split<2>), reinterpret_cast<const void *>(&k_gemm_split<1>)};
+    (void)gnn_raise_dynamic_lds(ks, 6, 160 * 1024, lds_raised);
     bool split = true;                             // shipped: the split-bf16 products; the f32-MFMA form stays as the exact-chain cross-check
 #ifdef GNN_DIAG
     static const bool f32_env = getenv("GNN_TRAIN_GEMM_F32") != nullptr;
@@ -522,14 +519,11 @@ bool fwd3_covers(const gnn_mlp *m)
 
 int launch_fwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, int64_t n, const float *x, float *a0, float *a1, float *a2)
 {
-    static bool raised = false;
+    static bool lds_raised[64] = {false};
     const void *ks[6] = {reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_LINEAR>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_RELU>),
                          reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_SELU>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_ELU>),
                          reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_TANH>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_SIGMOID>)};
-    if (!raised) {
-        for (const void *k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        raised = true;
-    }
+    (void)gnn_raise_dynamic_lds(ks, 6, 160 * 1024, lds_raised);
     Fwd3Args p{};
     p.n = n; p.K = m->dims[0]; p.w1 = m->dims[1]; p.w2 = m->dims[2]; p.w3 = m->dims[3]; p.act = m->acts[0];
     p.KP = std::max(tg_kps(p.K), tg_kps(128));
@@ -753,11 +747,8 @@ bool bwd3_covers(const gnn_mlp *m)
 int launch_bwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, float *const *WT, int64_t n, const float *dz2, const float *a1, const float *a0, float *dz1,
                 float *dz0, float *dinp, float *dsg, int Ds, int c_aggs)
 {
-    static bool raised = false;
-    if (!raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bwd3_split), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        raised = true;
-    }
+    static bool lds_raised[64] = {false};
+    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_bwd3_split), 160 * 1024, lds_raised);
     Bwd3Args p{};
     p.n = n; p.K0 = m->dims[0]; p.w1 = m->dims[1]; p.w2 = m->dims[2]; p.w3 = m->dims[3]; p.act = m->acts[0];
     p.KP = std::max(tg_kps(128), tg_kps(p.K0));

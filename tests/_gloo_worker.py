@@ -94,7 +94,7 @@ def main():
             return buf
 
         def return_pipelined(slice_all):
-            # the schedule of slice_step_aggregate (csrc/gnn_engine.hip, gnn_loop_set_slice_exchange(l, 1)): the slice is aggregated in one
+            # the schedule of slice_step_aggregate (csrc/gnn_comm.hip, gnn_loop_set_slice_exchange(l, 1)): the slice is aggregated in one
             # row block per destination rank in the order rank + 1, ..., rank; at step t rank r sends block (r + 1 + t) % P to that rank
             # and receives its own rows' block from rank (r - 1 - t) % P - a permutation per step; the last step is the rank's own block
             back = [None] * world
