@@ -331,7 +331,7 @@ struct gnn_loop {
     bool last_run_range_rerun = false;
     bool small_words_clean = false;         // the double-buffered gate words of the persistent loop are zero / in their run-parity state
     unsigned small_runs = 0;
-    float *small_xs = nullptr;              // the persistent loop's padded exchange rows (gnn_small.hip), allocated with its first run
+    float *small_xs = nullptr;              // the persistent loop's padded exchange rows (gnn_small_kernel.h), allocated with its first run
     size_t small_xs_floats = 0;
     bool small_disabled = false;            // the persistent small-graph loop gave up once on this loop: keep to per-body launches
     int kfinal = -1;
@@ -345,7 +345,7 @@ struct gnn_loop {
     float *ng_w = nullptr, *ng_out = nullptr, *ng_part = nullptr;   // ng_part [world, G, T]: per-rank partial readouts
     std::vector<int32_t> ng_key;
     std::vector<float> ng_w_host;
-    // graph readout folded into the persistent small-graph launch (gnn_small.hip): result [G, T] in pinned host memory, valid for the last run
+    // graph readout folded into the persistent small-graph launch (gnn_small_kernel.h): result [G, T] in pinned host memory, valid for the last run
     float *ng_host = nullptr;
     int ng_G = 0, ng_host_floats = 0;
     bool ng_inlaunch = false;
@@ -416,5 +416,5 @@ int gnn_gather_program_ensure(const gnn_graph *g);
 int gnn_fused_prepare(gnn_loop *l);
 int gnn_fused_pack(gnn_mlp *m, int nlc);
 int gnn_fused_iteration(gnn_loop *l, int k);
-int gnn_small_run(gnn_loop *l);                // persistent small-graph loop (gnn_small.hip): all bodies in one launch
+int gnn_small_run(gnn_loop *l);                // persistent small-graph loop (gnn_small_kernel.h): all bodies in one launch
 void gnn_fused_release(gnn_mlp *m);

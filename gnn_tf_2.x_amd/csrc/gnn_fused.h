@@ -18,6 +18,9 @@ constexpr int GNN_FUSED_THREADS = 64 * GNN_FUSED_WAVES;
 #define GNN_GP_ROW_MASK 31u
 #define GNN_GP_ROW_END 32u
 #define GNN_GP_NOROW 0xfffffe00u
+// Last-layer activation of the kernels' ACTL template parameter for a net whose last layer has an activation of its own: "read
+// GnnFusedArgs::act_last" (one instantiation per hidden activation serves all last activations).  Library-internal, not a gnn_activation.
+constexpr int GNN_ACTL_FROM_ARGS = -1;
 
 struct GnnFusedArgs {
     // graph
@@ -74,6 +77,8 @@ struct GnnFusedArgs {
     // diagnostics only (GNN_POISON=1, diagnostic build): floats of the launch's dynamic LDS allocation that every workgroup fills with NaN
     // before its first tile (a read of a never-written LDS word then shows as a NaN instead of a stale value), else 0
     int lds_floats;
+    // activation of the last layer (gnn_activation, never softmax): read by the instantiations with ACTL == GNN_ACTL_FROM_ARGS only
+    int act_last;
 };
 
 // control block of the persistent small-graph loop (gnn_small_common.h)
@@ -87,7 +92,7 @@ struct GnnSmallCtl {
     float *xs;               // padded exchange rows [2][tiles * rows per tile][DP] (gnn_small_common.h, small_gather): the state between bodies
     int DP;                  // 16 (Ds <= 16) or 32 floats per exchange row
     int rnd;                 // arcs per gather round for DP == 16 (4, or 8 when some row has more than 8 arcs)
-    // 16-node-tile form (gnn_small16.hip): the Keras-layout kernels W[din][dout] (its A operands are read from them directly) and the
+    // 16-node-tile form (gnn_small16_kernel.h): the Keras-layout kernels W[din][dout] (its A operands are read from them directly) and the
     // row stride of its LDS tile
     const float *Wraw[GNN_FUSED_MAXL];
     int din[GNN_FUSED_MAXL], dout[GNN_FUSED_MAXL];
@@ -114,7 +119,8 @@ struct GnnSmallCtl {
 // Layout of a net_state's packed weight images and of the kernels' LDS tile (gnn_fused.hip, make_plan): a function of the net's widths and
 // activations and of the loop's node-label columns alone.
 struct FusedPlan {
-    int layers = 0, NT = 0, NTL = 0, KP = 0, kk0 = 0, act = 0;
+    int layers = 0, NT = 0, NTL = 0, KP = 0, kk0 = 0;
+    int act = 0, act_last = 0;       // activation of the hidden layers (one for all of them) / of the last layer; one layer: the same
     // split arithmetic, state width 64 (the tuned shape): the LDS tile is laid out for 16-byte accesses - rows 16-byte aligned
     // (KPs a multiple of 4 with KPs / 4 odd: ds_read_b128 down a column stays bank-conflict free) and the aggregated-state block
     // starting on a multiple of 4 columns, i.e. after a hole of `pad` zero columns behind [state | nodes]
@@ -185,6 +191,10 @@ using GnnSmall16S0 = GnnSteps<4, 8, 12, 16, 20, 24>;             // k_small16: K
 bool gnn_small_launch(int layers, int act, int kk0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes,
                       hipStream_t st);
 bool gnn_small16_launch(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
+// the same kernels for a net whose last layer has its own activation (a.act_last): gnn_small_m.hip, gnn_small16_m.hip; layers 2 or 3
+bool gnn_small_launch_mixed(int layers, int act, int kk0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes,
+                            hipStream_t st);
+bool gnn_small16_launch_mixed(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
 
 // one per translation unit gnn_fused_l{1,2,3}.hip; false = no instantiation for (act, nt, ntl)
 bool gnn_fused_launch_l1(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
@@ -197,3 +207,9 @@ bool gnn_fused_launch_p2(int act, const GnnFusedArgs &a, unsigned grid, size_t l
 bool gnn_fused_launch_p3(int act, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
 bool gnn_fused_launch_l2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
 bool gnn_fused_launch_l3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+// k_fused for a net whose last layer has its own activation (act: the hidden layers'; a.act_last): gnn_fused_ml{2,3}.hip (exact),
+// gnn_fused_ms{2,3}.hip (split)
+bool gnn_fused_launch_ml2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ml3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ms2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ms3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);

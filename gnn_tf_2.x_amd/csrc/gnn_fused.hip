@@ -33,14 +33,20 @@ constexpr int S_SLACK = 2;      // zero chunks after the layer-0 block of the sp
 
 int round_tiles(int width) { return width <= 32 ? 1 : (width <= 64 ? 2 : 4); }
 
+// The nets the fused paths cover: one to three Dense layers no wider than 128, no softmax, ONE activation for all hidden layers (p.act) and
+// any of the six for the last layer (p.act_last; a one-layer net has act == act_last).  Three layers with two different hidden activations
+// are not covered.  Feature tiles of 32: NTL = tiles of the last layer (width <= 32: 1, <= 64: 2, else 4), NT = tiles of the widest
+// hidden layer, at least NTL; of these only (NT, NTL) = (1,1) (2,2) (4,2) (4,4) are instantiated, so (2,1) and (4,1) become (2,2), (4,2).
 bool make_plan(const gnn_mlp *m, int nlc, FusedPlan &p)
 {
     if (m->n_layers < 1 || m->n_layers > MAXL) return false;
     p.layers = m->n_layers;
-    p.act = m->acts[0];
+    p.act_last = m->acts[m->n_layers - 1];
+    p.act = m->n_layers > 1 ? m->acts[0] : p.act_last;
     int hid = 0;
     for (int l = 0; l < m->n_layers; ++l) {
-        if (m->acts[l] != p.act || m->acts[l] == GNN_ACT_SOFTMAX) return false;   // one activation for all layers
+        if (m->acts[l] < GNN_ACT_LINEAR || m->acts[l] >= GNN_ACT_SOFTMAX) return false;
+        if (l < m->n_layers - 1 && m->acts[l] != p.act) return false;              // one activation for all hidden layers
         if (m->dims[l + 1] > 128) return false;
         if (l < m->n_layers - 1) hid = std::max(hid, m->dims[l + 1]);
     }
@@ -93,9 +99,12 @@ size_t lds_bytes(const FusedPlan &p)
 }
 
 // the wave-pair form (gnn_fused_pair_kernel.h) covers the tuned shape family only: split arithmetic, state width 64, two or three layers, 128-wide
-// hidden layers, a concat of nine K = 16 chunks
+// hidden layers, a concat of nine K = 16 chunks, one activation for all layers
 constexpr int PAIR_CH0 = 9;
-bool pair_covers(const FusedPlan &p, int ds) { return ds == 64 && p.NTL == 2 && p.NT == 4 && (p.layers == 2 || p.layers == 3) && p.chunks[0] == PAIR_CH0; }
+bool pair_covers(const FusedPlan &p, int ds)
+{
+    return ds == 64 && p.NTL == 2 && p.NT == 4 && (p.layers == 2 || p.layers == 3) && p.chunks[0] == PAIR_CH0 && p.act_last == p.act;
+}
 int pair_xs(const FusedPlan &p)       // row stride of a pair's gather tile X' (the LDS columns behind the own state), a multiple of 4 with XS / 4 odd
 {
     int xs = 16 * p.chunks[0] - 64 + 4;
@@ -172,6 +181,7 @@ int gnn_fused_pack(gnn_mlp *m, int nlc)
         // split image: [chunk][out tile][piece][lane][8 bf16]; element i of lane (m, h) is k(h, i) of gnn_fused_kernel.h
         // Folded SELU between the dense layers of the split path (gnn_fused_kernel.h, GNN_S1_E): a layer whose OUTPUT feeds the
         // folded activation is scaled by log2(e) (so is its bias, at staging), a layer whose INPUT comes from it by scale / log2(e).
+        // Keyed on the HIDDEN activation: the last layer's output (its own activation, p.act_last) is never folded.
         float fold = 1.0f;
         if (p.act == GNN_ACT_SELU && m->n_layers > 1) {
             const double LOG2E = 1.44269504088896341, SCALE = 1.0507009873554805;
@@ -237,6 +247,24 @@ int gnn_fused_pack(gnn_mlp *m, int nlc)
         m->packed_split_dwords = p.s_total;
     }
     HIPCHK(hipMemcpy(m->packed_split, simg.data(), p.s_total * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return GNN_OK;
+}
+
+// What the fused paths make of a net of this description (include/gnn_hip.h): make_plan itself, host code, no device
+extern "C" int gnn_fused_net_form(int n_layers, const int *dims, const int *acts, int n_label_cols_in_concat, int *out)
+{
+    ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && n_label_cols_in_concat >= 0 && out, "bad arguments");
+    gnn_mlp m;
+    m.n_layers = n_layers;
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.acts.assign(acts, acts + n_layers);
+    for (int l = 0; l <= n_layers; ++l) ARGCHK(m.dims[l] >= 1, "bad layer width");
+    for (int l = 0; l < n_layers; ++l) ARGCHK(m.acts[l] >= GNN_ACT_LINEAR && m.acts[l] <= GNN_ACT_SOFTMAX, "bad activation code");
+    FusedPlan p;
+    const bool covered = make_plan(&m, n_label_cols_in_concat, p);
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (!covered) return GNN_OK;
+    out[0] = 1; out[1] = p.act; out[2] = p.act_last; out[3] = p.NT; out[4] = p.NTL; out[5] = p.act_last != p.act ? 1 : 0;
     return GNN_OK;
 }
 
@@ -339,6 +367,7 @@ static void fill_args(const gnn_loop *l, const FusedPlan &p, bool split, GnnFuse
     a.certify = split ? 1 : 0;
     a.agg_in = l->slice_mode ? l->agg_own : nullptr;
     a.wstride = 1;
+    a.act_last = p.act_last;
 }
 
 // the five fields of the arguments that depend on the body
@@ -406,7 +435,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
 
-// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small.hip, gnn_small16.hip)
+// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h)
 static int decide_persistent(gnn_loop *l, LoopForm &f)
 {
     const gnn_graph *g = l->g;
@@ -427,7 +456,7 @@ static int decide_persistent(gnn_loop *l, LoopForm &f)
         if (2 * cand >= a.in_s && cand <= p.kk0) { f.kk_small = cand; break; }
     for (int cand : GnnSmall16S0::values)
         if (4 * cand >= a.in_s) { f.s0 = cand; break; }
-    // 16-node tiles (gnn_small16.hip) while twice the workgroups are still resident at once (and an instantiation covers the concat width,
+    // 16-node tiles (gnn_small16_kernel.h) while twice the workgroups are still resident at once (and an instantiation covers the concat width,
     // in_s <= 96): a body is a chain of latencies, and a 16-node tile's dense layers and activations are half as long
     bool tile16 = g->n_rows <= 16 * 256 && f.s0 > 0;
 #ifdef GNN_DIAG
@@ -494,7 +523,8 @@ static int decide_persistent(gnn_loop *l, LoopForm &f)
 // Per-body kernel of the default path, the library's choice (gnn_loop_set_tile_form(l, 0)): the wave pair while no pair of the launch gets a
 // second tile (tiles <= 4 x CUs: the launch is one tile latency long and a pair's tile takes about half as long as a wave's: N = 4 k .. 32 k:
 // 7 - 11 % less time per iteration), one wave per tile beyond (N = 41 k: +13 %, BASELINE size: 0.78 against 0.68 ms - the seven meetings of
-// a pair per tile cost more than its shorter matrix phases return; profiles/r05_midsize_forms.txt, r05_pair_stamps.txt).
+// a pair per tile cost more than its shorter matrix phases return; profiles/r05_midsize_forms.txt, r05_pair_stamps.txt).  The pair exists for
+// nets with one activation for all layers (pair_covers): a net whose last layer has its own takes one wave per tile there too.
 // Gather form (gnn_loop_set_gather_form): the bodies read the graph's program when the launch is the full-tile form of k_fused that gathers
 // (state width 64, a net with a 64-wide last layer, no feature-sliced exchange, not the wave pair) and the graph has a program - it is
 // built here, on first demand.
@@ -533,6 +563,11 @@ int gnn_loop_decide_form(gnn_loop *l)
 static bool launch_body(const LoopForm &f, const GnnFusedArgs &a, hipStream_t st)
 {
     const FusedPlan &p = f.plan;
+    if (p.act_last != p.act) {                                        // the last layer's own activation: a.act_last (never the wave pair)
+        if (f.kernel == GNN_BODY_PAIR || p.layers < 2) return false;
+        if (f.split) return p.layers == 2 ? gnn_fused_launch_ms2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st) : gnn_fused_launch_ms3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+        return p.layers == 2 ? gnn_fused_launch_ml2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st) : gnn_fused_launch_ml3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+    }
     if (f.kernel == GNN_BODY_PAIR)
         return p.layers == 2 ? gnn_fused_launch_p2(p.act, a, f.grid, f.lds, st) : gnn_fused_launch_p3(p.act, a, f.grid, f.lds, st);
     if (f.split) {
@@ -563,7 +598,7 @@ int gnn_fused_iteration(gnn_loop *l, int k)
 #endif
     const FusedPlan &p = f.plan;
     if (!launch_body(f, a, l->stream))
-        return gnn_fail(GNN_ERR_UNSUPPORTED, "no fused instantiation for %d layers, tiles (%d,%d), activation %d", p.layers, p.NT, p.NTL, p.act);
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "no fused instantiation for %d layers, tiles (%d,%d), activations %d / %d", p.layers, p.NT, p.NTL, p.act, p.act_last);
 #ifdef GNN_DIAG
     if (a.stamps) {
         std::vector<unsigned long long> host(n_waves * (f.kernel == GNN_BODY_PAIR ? 16 : 8));
@@ -577,7 +612,7 @@ int gnn_fused_iteration(gnn_loop *l, int k)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// persistent small-graph loop (device code: gnn_small_common.h, gnn_small.hip, gnn_small16.hip)
+// persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h)
 // ---------------------------------------------------------------------------------------------------------------------
 int gnn_small_run(gnn_loop *l)
 {
@@ -609,10 +644,15 @@ int gnn_small_run(gnn_loop *l)
         a.stamps = small_stamp_buf;
     }
 #endif
-    const bool launched = f.small_tile == 16 ? gnn_small16_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                                             : gnn_small_launch(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
+    bool launched;
+    if (p.act_last != p.act)
+        launched = f.small_tile == 16 ? gnn_small16_launch_mixed(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                                      : gnn_small_launch_mixed(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
+    else
+        launched = f.small_tile == 16 ? gnn_small16_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                                      : gnn_small_launch(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
     if (!launched)
-        return gnn_fail(GNN_ERR_UNSUPPORTED, "no persistent-loop instantiation for %d layers, activation %d", p.layers, p.act);
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "no persistent-loop instantiation for %d layers, activations %d / %d", p.layers, p.act, p.act_last);
     HIPCHK(hipGetLastError());
 #ifdef GNN_DIAG
     if (small_stamp_file) {

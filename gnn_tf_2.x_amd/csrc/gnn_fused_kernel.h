@@ -1,5 +1,5 @@
-// Fused iteration kernel for gfx950 (device code).  Included by gnn_fused_l{1,2,3}.hip, one translation unit per layer
-// count so that the instantiations compile in parallel.
+// Fused iteration kernel for gfx950 (device code).  Included by gnn_fused_{l,s}{1,2,3}.hip and gnn_fused_m{l,s}{2,3}.hip, one translation
+// unit per layer count, arithmetic mode and "the last layer has its own activation", so that the instantiations compile in parallel.
 //
 // One launch = one iteration of GNN.Loop (reference GNN/GNN.py:223-242 + :202-220):
 // CSR neighbour gather -> net_state (all Dense layers + BatchNormalization) -> convergence test.
@@ -21,7 +21,8 @@
 //     coalesced 256 B row stores, one slotted atomicOr per wave that still moves.
 //
 // Template parameters: LAYERS Dense layers; NT 32-wide feature tiles of every hidden layer; NTL tiles of the last layer;
-// ACT the activation shared by all layers (gnn_activation).
+// ACT the activation of the hidden layers (gnn_activation); ACTL that of the last layer: ACT (a net with one activation for all layers) or
+// GNN_ACTL_FROM_ARGS (a net whose last layer has its own: GnnFusedArgs::act_last, read in the last-layer epilogue only).
 #pragma once
 #include <utility>
 
@@ -250,6 +251,27 @@ __device__ __forceinline__ void tile_epilogue(f32x16 &a, const float *bias, cons
                 a[4 * q + t] = v.x;
                 a[4 * q + t + 1] = v.y;
             }
+        }
+    }
+}
+
+// The LAST layer's epilogue.  ACTL a gnn_activation: tile_epilogue<ACTL>.  ACTL == GNN_ACTL_FROM_ARGS: the same forms - act_t2 (exact) /
+// act_fast (split) of the activation act_last - behind a wave-uniform switch (act_last is a kernel argument), so one instantiation per
+// hidden activation serves every last activation with the bits of the instantiation that has it as a constant.
+template <int ACTL, bool BN, bool FAST = false, bool LDS = false, bool NOBIAS = false>
+__device__ __forceinline__ void tile_epilogue_last(int act_last, f32x16 &a, const float *bias, const float *bn_scale, const float *bn_shift,
+                                                   int jt, int half, int fmax = 1 << 30, float us = 1.0f)
+{
+    if constexpr (ACTL != GNN_ACTL_FROM_ARGS) {
+        tile_epilogue<ACTL, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us);
+    } else {
+        switch (act_last) {
+        case GNN_ACT_RELU: tile_epilogue<GNN_ACT_RELU, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us); break;
+        case GNN_ACT_SELU: tile_epilogue<GNN_ACT_SELU, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us); break;
+        case GNN_ACT_ELU: tile_epilogue<GNN_ACT_ELU, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us); break;
+        case GNN_ACT_TANH: tile_epilogue<GNN_ACT_TANH, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us); break;
+        case GNN_ACT_SIGMOID: tile_epilogue<GNN_ACT_SIGMOID, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us); break;
+        default: tile_epilogue<GNN_ACT_LINEAR, BN, FAST, LDS, NOBIAS>(a, bias, bn_scale, bn_shift, jt, half, fmax, us); break;
         }
     }
 }
@@ -1391,7 +1413,8 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N])
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
 // PROG (with FULL, not GIVEN): the full tiles are gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the
 // partial last tile of the range walks the CSR as before.  A template parameter for the same reason as GIVEN.
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3, bool PROG = false>
+// ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3, bool PROG = false, int ACTL = ACT>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedArgs a0)
 {
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
@@ -1597,8 +1620,8 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         if (fast64) {                                         // registers -> norms, LDS (16-byte pieces), row stores
 #pragma unroll
             for (int jt = 0; jt < NTL; ++jt) {
-                if (a.bn_scale) tile_epilogue<ACT, true, true, true, true>(out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, a.usc[LAYERS - 1]);
-                else tile_epilogue<ACT, false, true, true, true>(out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, a.usc[LAYERS - 1]);
+                if (a.bn_scale) tile_epilogue_last<ACTL, true, true, true, true>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, a.usc[LAYERS - 1]);
+                else tile_epilogue_last<ACTL, false, true, true, true>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, a.usc[LAYERS - 1]);
             }
             GNN_STAMP(6);
             if (nvalid == 32) finish_fast64_aligned(a, X, out, i0, lane, KP, c_aggs, peek);
@@ -1610,8 +1633,8 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
 #pragma unroll
         for (int jt = 0; jt < NTL; ++jt) {
             const float us = SPLIT ? a.usc[LAYERS - 1] : 1.0f;
-            if (a.bn_scale) tile_epilogue<ACT, true, SPLIT, true, SPLIT>(out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, us);
-            else tile_epilogue<ACT, false, SPLIT, true, SPLIT>(out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, us);
+            if (a.bn_scale) tile_epilogue_last<ACTL, true, SPLIT, true, SPLIT>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, us);
+            else tile_epilogue_last<ACTL, false, SPLIT, true, SPLIT>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, us);
             float *x = X + (lane & 31) * KP + c_aggs;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1639,50 +1662,50 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
   }
 }
 
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false, int PC = 3, bool PROG = false>
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL, bool FULL, bool GIVEN = false, int PC = 3, bool PROG = false>
 inline void launch_one_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     // the full-tile gathering kernel exists in both gather forms; the launch carries a program (gp_tiles > 0) when form 2 was chosen for it
     if constexpr (FULL && !GIVEN && !PROG) {
-        if (a.gp_tiles > 0) { launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, true>(a, grid, lds_bytes, st); return; }
+        if (a.gp_tiles > 0) { launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, ACTL, FULL, GIVEN, PC, true>(a, grid, lds_bytes, st); return; }
     }
     static bool lds_raised[64] = {false};   // (one table per instantiation)
-    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>), 160 * 1024, lds_raised);
-    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
+    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG, ACTL>), 160 * 1024, lds_raised);
+    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG, ACTL>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
 }
 // the split arithmetic in the piece format of the launch (a.pieces); the exact path has one
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL, bool GIVEN = false>
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL, bool FULL, bool GIVEN = false>
 inline void launch_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    if (SPLIT && a.pieces == 2) launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, 2>(a, grid, lds_bytes, st);
-    else launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, 3>(a, grid, lds_bytes, st);
+    if (SPLIT && a.pieces == 2) launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, ACTL, FULL, GIVEN, 2>(a, grid, lds_bytes, st);
+    else launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, ACTL, FULL, GIVEN, 3>(a, grid, lds_bytes, st);
 }
 
 // a.full_tiles: the host asks for the full-tile specialisation (state width 64); it exists for NTL == 2
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT>
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL>
 inline void launch(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     if constexpr (NTL == 2) {
-        if (a.full_tiles && a.agg_in) { launch_one<LAYERS, NT, NTL, ACT, SPLIT, true, true>(a, grid, lds_bytes, st); return; }
-        if (a.full_tiles) { launch_one<LAYERS, NT, NTL, ACT, SPLIT, true>(a, grid, lds_bytes, st); return; }
+        if (a.full_tiles && a.agg_in) { launch_one<LAYERS, NT, NTL, ACT, SPLIT, ACTL, true, true>(a, grid, lds_bytes, st); return; }
+        if (a.full_tiles) { launch_one<LAYERS, NT, NTL, ACT, SPLIT, ACTL, true>(a, grid, lds_bytes, st); return; }
     }
-    launch_one<LAYERS, NT, NTL, ACT, SPLIT, false>(a, grid, lds_bytes, st);
+    launch_one<LAYERS, NT, NTL, ACT, SPLIT, ACTL, false>(a, grid, lds_bytes, st);
 }
 
 // (NT, NTL) pairs that are instantiated; gnn_fused.hip rounds every net up to one of them
-template <int LAYERS, int ACT, bool SPLIT>
+template <int LAYERS, int ACT, bool SPLIT, int ACTL = ACT>
 inline bool launch_tiles(int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     if constexpr (LAYERS == 1) {
-        if (ntl == 1) launch<1, 1, 1, ACT, SPLIT>(a, grid, lds_bytes, st);
-        else if (ntl == 2) launch<1, 2, 2, ACT, SPLIT>(a, grid, lds_bytes, st);
-        else if (ntl == 4) launch<1, 4, 4, ACT, SPLIT>(a, grid, lds_bytes, st);
+        if (ntl == 1) launch<1, 1, 1, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        else if (ntl == 2) launch<1, 2, 2, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        else if (ntl == 4) launch<1, 4, 4, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
         else return false;
     } else {
-        if (nt == 1 && ntl == 1) launch<LAYERS, 1, 1, ACT, SPLIT>(a, grid, lds_bytes, st);
-        else if (nt == 2 && ntl == 2) launch<LAYERS, 2, 2, ACT, SPLIT>(a, grid, lds_bytes, st);
-        else if (nt == 4 && ntl == 2) launch<LAYERS, 4, 2, ACT, SPLIT>(a, grid, lds_bytes, st);
-        else if (nt == 4 && ntl == 4) launch<LAYERS, 4, 4, ACT, SPLIT>(a, grid, lds_bytes, st);
+        if (nt == 1 && ntl == 1) launch<LAYERS, 1, 1, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        else if (nt == 2 && ntl == 2) launch<LAYERS, 2, 2, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        else if (nt == 4 && ntl == 2) launch<LAYERS, 4, 2, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        else if (nt == 4 && ntl == 4) launch<LAYERS, 4, 4, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
         else return false;
     }
     return true;
@@ -1707,6 +1730,14 @@ template <int LAYERS, bool SPLIT>
 inline bool launch_act(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     return dispatch_act(act, [&](auto A) { return launch_tiles<LAYERS, A.value, SPLIT>(nt, ntl, a, grid, lds_bytes, st); });
+}
+
+// the instantiations of hidden activation act whose last layer reads its activation from a.act_last
+template <int LAYERS, bool SPLIT>
+inline bool launch_act_mixed(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+{
+    static_assert(LAYERS >= 2, "a one-layer net has one activation");
+    return dispatch_act(act, [&](auto A) { return launch_tiles<LAYERS, A.value, SPLIT, GNN_ACTL_FROM_ARGS>(nt, ntl, a, grid, lds_bytes, st); });
 }
 
 }   // namespace gnn_fused_dev

@@ -337,7 +337,7 @@ extern "C" int gnn_loop_drop_cached_aggregates(gnn_loop *l)
     return GNN_OK;
 }
 
-// small graphs run all bodies of a Loop inside one persistent launch (gnn_small.hip); enable = 0 keeps to one launch per body
+// small graphs run all bodies of a Loop inside one persistent launch (gnn_small_kernel.h); enable = 0 keeps to one launch per body
 extern "C" int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used)
 {
     ARGCHK(l, "loop is NULL");
@@ -645,7 +645,7 @@ static int run_loops_once(gnn_loop **ls, int n)
     int rc = 0;
     for (int r = 0; r < n; ++r) if ((rc = loop_prepare(ls[r]))) return rc;
     if (ls[0]->form.path == GNN_PATH_PERSISTENT) {
-        // small graphs: the initial state, the first condition and every body inside ONE persistent launch (gnn_small.hip)
+        // small graphs: the initial state, the first condition and every body inside ONE persistent launch (gnn_small_kernel.h)
         if ((rc = gnn_small_run(ls[0]))) return rc;             // (never a profiled run: no event to record)
     } else {
         const int max_iter = ls[0]->max_iter;
@@ -924,7 +924,7 @@ static int readout_partial(gnn_loop *lm, int G, const int32_t *ng_indptr, const 
     const bool same = lm->ng_key == key && lm->ng_w_host.size() == (size_t)nnz &&
                       (nnz == 0 || memcmp(lm->ng_w_host.data(), ng_w, sizeof(float) * nnz) == 0);
     int rc = GNN_OK;
-    if (same && gnn_loop_ng_folded(lm) && lm->ng_G == G) return GNN_OK;      // the persistent launch of this run has already computed it (gnn_small.hip)
+    if (same && gnn_loop_ng_folded(lm) && lm->ng_G == G) return GNN_OK;      // the persistent launch of this run has already computed it (gnn_small_kernel.h)
     if (!same) {
         lm->ng_inlaunch = false;
         (void)hipFree(lm->ng_ip); (void)hipFree(lm->ng_node); (void)hipFree(lm->ng_w); (void)hipFree(lm->ng_out); (void)hipFree(lm->ng_part);

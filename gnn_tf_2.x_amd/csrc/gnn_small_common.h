@@ -1,7 +1,7 @@
 // Shared phases of the persistent small-graph loop: ONE launch runs every body of a GNN.Loop (reference GNN/GNN.py:271, tf.while_loop
 // of condition :202-220 and convergence :223-242) when the batch is small enough for all of its tiles to be resident at once (BASELINE
 // configs[0] / [1]: a few hundred to a few thousand nodes, nets no wider than 32).  It has two forms that differ in the gather and the
-// dense layers only: k_small_loop on 32-node tiles (gnn_small.hip) and k_small16 on 16-node tiles (gnn_small16.hip); everything else is
+// dense layers only: k_small_loop on 32-node tiles (gnn_small_kernel.h) and k_small16 on 16-node tiles (gnn_small16_kernel.h); everything else is
 // here, templated on the rows per tile (ROWS = 32 or 16) where it depends on it, with the LDS layout (GnnSmallLds) and the instantiation
 // lists in gnn_fused.h.
 //

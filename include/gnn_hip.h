@@ -297,7 +297,12 @@ int gnn_loop_optimizer_step_scaled(gnn_loop *l, int kind, const float *hyper, fl
  *       tolerance of BASELINE.json), not bit for bit.  A Loop in which an activation leaves the fp16 range is repeated with
  *       three bf16 pieces per operand (six products on v_mfma_f32_32x32x16_bf16), the format of earlier releases
  *       (gnn_loop_set_pieces, gnn_loop_range_info).
- * 1 and 2 fall back to 0 when the shapes are not covered.  *used (may be NULL) reports the choice.
+ * 1 and 2 fall back to 0 when the net is not covered.  *used (may be NULL) reports the choice.  Covered: a net_state of one to three Dense
+ * layers no wider than 128 whose hidden layers share ONE activation; the last layer may have any other of linear / relu / selu / elu /
+ * tanh / sigmoid (['selu', 'selu', 'tanh'], ['relu', 'sigmoid'], ...) and runs the same kernels with the same arithmetic per mode.  Not
+ * covered (impl 0): two different hidden activations (['relu', 'tanh', 'tanh']), softmax in net_state, a wider layer.  (Training is a
+ * separate decision: a net whose activations differ keeps the per-layer matrix-core forms, not the three-layer chains k_fwd3_split /
+ * k_bwd3_split.)
  * k contract of impl 2 (reference GNN/GNN.py:202-220: `distance > threshold * norm`, reduce_any, k < max_iteration): its iteration count
  * is the bit-exact chain's.  Every body also records whether some node moved by a margin ("robust") and whether some node's test lay
  * within a guard band of the threshold ("borderline"; band = 1e-5 norm + 1e-3 threshold norm); a gate with a robust mover, or without
@@ -323,7 +328,9 @@ void gnn_split_f16(const float *v, int n, int e, uint16_t *p0, uint16_t *p1);
 /* Small graphs (every 32-node tile resident at once: <= 8,192 owned nodes, single GPU) with a net_state no wider than 32 run
  * the whole tf.while_loop of GNN/GNN.py:271 - initial state, first condition, every body with a grid barrier in between - in
  * ONE persistent launch when impl is 1 or 2 (exact f32-MFMA arithmetic in both cases, bit-identical to the oracle).  enable = 0
- * keeps such a loop to one launch per body; *used (may be NULL) tells whether the persistent launch will be taken. */
+ * keeps such a loop to one launch per body; *used (may be NULL) tells whether the persistent launch will be taken.  The nets are those of
+ * gnn_loop_set_impl: a last layer with an activation of its own takes the persistent launch too, two different hidden activations or a
+ * softmax do not (per-op kernels). */
 int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used);
 /* Which form of the fused iteration kernel runs the bodies of GNN/GNN.py:223-242 on the default path (impl 2) when both cover the
  * net (state width 64, two or three Dense layers, 128-wide hidden layers, concat width 129 .. 144, no feature-sliced exchange):
@@ -331,6 +338,8 @@ int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used);
  *   form 2  a wave PAIR shares the tile, each wave gathering 16 of its nodes and producing half of every layer's output features
  *           (k_fused_pair);
  *   form 0  the library's choice (default).
+ * The wave pair exists for nets with one activation for ALL layers only: a net whose last layer has its own activation takes form 1
+ * whatever is asked for (*used = 1).
  * The two forms evaluate the same arithmetic per node: states, outputs and k are identical bit for bit.  *used (may be NULL) = the form
  * the next run will take (1 or 2; 0 when the fused path does not cover the loop at all). */
 int gnn_loop_set_tile_form(gnn_loop *l, int form, int *used);
@@ -371,6 +380,12 @@ int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *b
 enum { GNN_FORM_PER_OP = 0, GNN_FORM_MLP_FWD = 1, GNN_FORM_WIDE = 2, GNN_FORM_CHAIN3 = 3, GNN_FORM_WGRAD_BF = 4, GNN_FORM_WGRAD_F32 = 5 };
 int gnn_train_forms(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int producer_dropout, int *out);
 int gnn_loop_train_forms(const gnn_loop *l, int net, int *out);
+/* What the fused inference paths (impl 1 / 2, the persistent launch) make of a net_state of this description - dims [n_layers + 1], acts
+ * [n_layers] (gnn_activation codes), node-label columns in the concat; host code, no device, the decision the loops themselves take.
+ * out receives 6 ints: out[0] = 1 covered / 0 not (then the rest is 0); out[1] = activation of the hidden layers; out[2] = activation of
+ * the last layer; out[3], out[4] = 32-feature tiles of the hidden layers and of the last layer in the instantiated kernel (NT, NTL);
+ * out[5] = 1 when the last layer's activation differs from the hidden one. */
+int gnn_fused_net_form(int n_layers, const int *dims, const int *acts, int n_label_cols_in_concat, int *out);
 /* per-kernel HIP-event timing of the last gnn_loop_run when profiling was enabled:
  * avg_iter_ms = mean duration of the per-iteration kernel(s), total_ms = whole loop on the stream. */
 int gnn_loop_set_profiling(gnn_loop *l, int enable);
