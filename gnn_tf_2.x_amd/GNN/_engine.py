@@ -20,7 +20,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_mlp_create', 'gnn_mlp_set_weights', 'gnn_mlp_get_weights', 'gnn_mlp_reset_optimizer', 'gnn_mlp_forward', 'gnn_mlp_destroy', 'gnn_loop_create',
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
-           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_fused_net_form',
+           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_fused_net_form', 'gnn_small_form',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -97,6 +97,19 @@ def fused_net_form(dims, activations, nlc=0) -> dict:
     _check(lib().gnn_fused_net_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(nlc)), _ip(out)))
     if not out[0]: return dict(covered=False, hidden=None, last=None, NT=0, NTL=0, mixed=False)
     return dict(covered=True, hidden=ACT_NAMES[int(out[1])], last=ACT_NAMES[int(out[2])], NT=int(out[3]), NTL=int(out[4]), mixed=bool(out[5]))
+
+
+def small_form(dims, activations, n_rows, nlc=0) -> dict:
+    """gnn_small_form (host code, no device): the persistent small-graph launch a net_state of this description takes on n_rows owned
+    nodes - dict(persistent; tile: 16 or 32 nodes per tile, 0 when not persistent; wide: the form with hidden layers up to 64 wide;
+    steps: first-layer K-steps kept in registers).  Single GPU, not disabled and not profiling are the loop's part of the decision."""
+    L = len(dims) - 1
+    if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
+    d = np.ascontiguousarray(dims, np.int32)
+    a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
+    out = np.zeros(3, np.int32)
+    _check(lib().gnn_small_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(nlc)), C.c_int64(int(n_rows)), _ip(out)))
+    return dict(persistent=bool(out[0]), tile=int(out[0]), wide=bool(out[1]), steps=int(out[2]))
 
 
 def split_f16(values, exponent=None):

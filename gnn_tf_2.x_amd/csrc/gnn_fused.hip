@@ -116,6 +116,46 @@ size_t pair_lds_bytes(const FusedPlan &p)
 {
     return sizeof(float) * ((size_t)4 * (32 * pair_xs(p) + p.chunks[0] * 768) + 16 + GNN_FUSED_WAVES * 20 + 3 * 32 * 2 + 2 * 32 * 4) + 128;
 }
+// The persistent small-graph launch (gnn_small_common.h) a net takes on n_rows owned rows, as far as the net and the row count decide it
+// (gnn_loop_decide_form adds what depends on the loop and the device: single GPU, not disabled, not profiling); m is covered by p.
+//   narrow: every layer one 32-feature tile - 16-node tiles (k_small16) up to 4,096 rows, 32-node tiles (k_small_loop) up to 8,192;
+//   wide:   two or three layers, every hidden layer <= 64 and at least one > 32, state <= 32 - 16-node tiles (k_small16w) up to 4,096 rows
+//           (256 one-wave workgroups); there is no 32-node wide form, so a wide net on more rows takes one launch per body.
+// Both need the concat (layer-0 K) within 96 columns: the largest instantiated step count, 24 x 4 = 48 x 2.  From the net's real widths:
+// make_plan turns the tiles (NT, NTL) = (2, 1) of a wide net into (2, 2).
+struct SmallForm {
+    int tile = 0;            // 0: not persistent; 16 / 32 rows per tile
+    bool wide = false;
+    int steps = 0;           // instantiated layer-0 K-steps: of 4 on 16-node tiles (GnnSmall16S0), of 2 on 32-node tiles (GnnSmallKK0)
+};
+SmallForm small_form(const gnn_mlp *m, const FusedPlan &p, int64_t n_rows)
+{
+    SmallForm f;
+    const int concat = m->dims[0];
+    if (n_rows < 1 || concat > 96) return f;
+    int hid = 0;
+    for (int l = 1; l < m->n_layers; ++l) hid = std::max(hid, m->dims[l]);
+    const bool narrow = hid <= 32 && m->dims.back() <= 32;
+    const bool wide = !narrow && (m->n_layers == 2 || m->n_layers == 3) && hid <= 64 && m->dims.back() <= 32;
+    if (!(narrow && n_rows <= 32 * 256) && !(wide && n_rows <= 16 * 256)) return f;
+    // K-steps of layer 0 the kernels keep in registers: the smallest instantiated count that covers the concat width (32-node tiles: the
+    // packed image has p.kk0 >= that many; the steps dropped are zero rows of the image)
+    if (n_rows <= 16 * 256) {
+        // 16-node tiles while twice the workgroups are still resident at once: a body is a chain of latencies, and a 16-node tile's dense
+        // layers and activations are half as long
+        f.tile = 16;
+        f.wide = wide;
+        for (int cand : GnnSmall16S0::values)
+            if (4 * cand >= concat) { f.steps = cand; break; }
+    } else {
+        f.tile = 32;
+        f.steps = p.kk0;
+        for (int cand : GnnSmallKK0::values)
+            if (2 * cand >= concat && cand <= p.kk0) { f.steps = cand; break; }
+    }
+    return f;
+}
+
 int device_cus(int device)
 {
     static int n_cu_dev[64] = {0};
@@ -265,6 +305,25 @@ extern "C" int gnn_fused_net_form(int n_layers, const int *dims, const int *acts
     for (int i = 0; i < 6; ++i) out[i] = 0;
     if (!covered) return GNN_OK;
     out[0] = 1; out[1] = p.act; out[2] = p.act_last; out[3] = p.NT; out[4] = p.NTL; out[5] = p.act_last != p.act ? 1 : 0;
+    return GNN_OK;
+}
+
+// Which persistent small-graph launch a net of this description takes on n_rows owned rows (include/gnn_hip.h): small_form itself, host
+// code, no device
+extern "C" int gnn_small_form(int n_layers, const int *dims, const int *acts, int n_label_cols_in_concat, int64_t n_rows, int *out)
+{
+    ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && n_label_cols_in_concat >= 0 && n_rows >= 0 && out, "bad arguments");
+    gnn_mlp m;
+    m.n_layers = n_layers;
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.acts.assign(acts, acts + n_layers);
+    for (int l = 0; l <= n_layers; ++l) ARGCHK(m.dims[l] >= 1, "bad layer width");
+    for (int l = 0; l < n_layers; ++l) ARGCHK(m.acts[l] >= GNN_ACT_LINEAR && m.acts[l] <= GNN_ACT_SOFTMAX, "bad activation code");
+    FusedPlan p;
+    out[0] = out[1] = out[2] = 0;
+    if (!make_plan(&m, n_label_cols_in_concat, p)) return GNN_OK;
+    const SmallForm f = small_form(&m, p, n_rows);
+    out[0] = f.tile; out[1] = f.wide ? 1 : 0; out[2] = f.steps;
     return GNN_OK;
 }
 
@@ -435,8 +494,9 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
 
-// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h)
-static int decide_persistent(gnn_loop *l, LoopForm &f)
+// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h,
+// gnn_small16w_kernel.h)
+static int decide_persistent(gnn_loop *l, LoopForm &f, const SmallForm &sf)
 {
     const gnn_graph *g = l->g;
     const FusedPlan &p = f.plan;
@@ -449,19 +509,16 @@ static int decide_persistent(gnn_loop *l, LoopForm &f)
     c.init = l->D ? l->state_init : g->nodes + (size_t)g->own_off * g->NL;      // D == 0: NL == Ds (GNN.py:265)
     c.kfinal = l->kfinal_dev;
     c.host_result = l->kfinal_host;                                   // pinned, device-visible: no copy back
-    // K-steps of layer 0 the kernels keep in registers: the smallest instantiated count that covers the concat width (32-node tiles: the
-    // packed image has p.kk0 >= that many; the steps dropped are zero rows of the image)
-    f.kk_small = p.kk0;
-    for (int cand : GnnSmallKK0::values)
-        if (2 * cand >= a.in_s && cand <= p.kk0) { f.kk_small = cand; break; }
-    for (int cand : GnnSmall16S0::values)
-        if (4 * cand >= a.in_s) { f.s0 = cand; break; }
-    // 16-node tiles (gnn_small16_kernel.h) while twice the workgroups are still resident at once (and an instantiation covers the concat width,
-    // in_s <= 96): a body is a chain of latencies, and a 16-node tile's dense layers and activations are half as long
-    bool tile16 = g->n_rows <= 16 * 256 && f.s0 > 0;
+    // tile rows, narrow or wide, and the layer-0 K-steps the kernel keeps in registers: small_form's
+    bool tile16 = sf.tile == 16;
+    f.small_wide = sf.wide;
+    if (tile16) f.s0 = sf.steps; else f.kk_small = sf.steps;
 #ifdef GNN_DIAG
     static const int tile_env = getenv("GNN_SMALL_TILE") ? atoi(getenv("GNN_SMALL_TILE")) : 0;
-    if (tile_env == 32) tile16 = false;
+    if (tile_env == 32 && !sf.wide) {                                // (the 32-node form of the same net, for comparison)
+        tile16 = false;
+        f.kk_small = small_form(l->st, p, 16 * 256 + 1).steps;
+    }
 #endif
     f.small_tile = tile16 ? 16 : 32;
     f.grid = (unsigned)((g->n_rows + f.small_tile - 1) / f.small_tile);
@@ -511,7 +568,7 @@ static int decide_persistent(gnn_loop *l, LoopForm &f)
         for (int q = 0; q < p.layers; ++q) { c.Wraw[q] = m->W[q]; c.din[q] = m->dims[q]; c.dout[q] = m->dims[q + 1]; }
         c.KP16 = std::max((a.in_s + 3) / 4 * 4, 4 * f.s0);
         if (c.KP16 % 8 == 0) c.KP16 += 4;                            // rows 16 bytes apart in the banks: the B-operand column reads do not conflict
-        f.lds = GnnSmallLds<16>::bytes(c.KP16);
+        f.lds = sf.wide ? GnnSmallLds<16, true>::bytes(c.KP16) : GnnSmallLds<16>::bytes(c.KP16);
     } else
         f.lds = GnnSmallLds<32>::bytes(p.KP);
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
@@ -549,12 +606,14 @@ int gnn_loop_decide_form(gnn_loop *l)
         gnn_gather_program_ensure(g) == GNN_OK)                       // (side effect 2: the graph's gather program)
         f.program = g->sh->gp_ent != nullptr;
     // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
-    // 32-feature tile per layer), layer-0 weights kept in registers, every tile resident at once (one wave each) with a wide margin
-    const bool persistent = l->world == 1 && !l->small_disabled && !l->profiling && p.NT == 1 && p.NTL == 1 && p.kk0 <= 48 && n_tiles <= 256;
+    // 32-feature tile per layer) or, up to 4,096 rows, with hidden layers up to 64 wide (small_form), layer-0 weights kept in registers,
+    // every tile resident at once (one wave each) with a wide margin
+    const SmallForm sf = small_form(l->st, p, g->n_rows);
+    const bool persistent = l->world == 1 && !l->small_disabled && !l->profiling && sf.tile != 0;
     f.path = persistent ? GNN_PATH_PERSISTENT : GNN_PATH_BODIES;
     // (side effect 3: the label block - the arguments point to it; gnn_fused_prepare zeroes and fills it when the loop runs)
     if (!l->inv) HIPCHK(gnn_dev_malloc((void **)&l->inv, inv_floats(l) * sizeof(float)));
-    if (persistent) return decide_persistent(l, f);
+    if (persistent) return decide_persistent(l, f, sf);
     decide_bodies(l, f, n_cu);
     return GNN_OK;
 }
@@ -612,7 +671,7 @@ int gnn_fused_iteration(gnn_loop *l, int k)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h)
+// persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h, gnn_small16w_kernel.h)
 // ---------------------------------------------------------------------------------------------------------------------
 int gnn_small_run(gnn_loop *l)
 {
@@ -646,11 +705,13 @@ int gnn_small_run(gnn_loop *l)
 #endif
     bool launched;
     if (p.act_last != p.act)
-        launched = f.small_tile == 16 ? gnn_small16_launch_mixed(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                                      : gnn_small_launch_mixed(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
+        launched = f.small_wide       ? gnn_small16w_launch_mixed(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                   : f.small_tile == 16 ? gnn_small16_launch_mixed(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                                        : gnn_small_launch_mixed(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
     else
-        launched = f.small_tile == 16 ? gnn_small16_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                                      : gnn_small_launch(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
+        launched = f.small_wide       ? gnn_small16w_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                   : f.small_tile == 16 ? gnn_small16_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
+                                        : gnn_small_launch(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
     if (!launched)
         return gnn_fail(GNN_ERR_UNSUPPORTED, "no persistent-loop instantiation for %d layers, activations %d / %d", p.layers, p.act, p.act_last);
     HIPCHK(hipGetLastError());

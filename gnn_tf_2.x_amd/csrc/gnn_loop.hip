@@ -337,7 +337,7 @@ extern "C" int gnn_loop_drop_cached_aggregates(gnn_loop *l)
     return GNN_OK;
 }
 
-// small graphs run all bodies of a Loop inside one persistent launch (gnn_small_kernel.h); enable = 0 keeps to one launch per body
+// small graphs run all bodies of a Loop inside one persistent launch (gnn_small_common.h); enable = 0 keeps to one launch per body
 extern "C" int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used)
 {
     ARGCHK(l, "loop is NULL");
@@ -771,6 +771,10 @@ extern "C" int gnn_loop_run_many(gnn_loop **loops, int n, float *k_out /* [n] */
     // resident at once.  A launch's workgroup is one wave with 10 - 40 KB of LDS: at least four fit on a CU; launches are queued side by
     // side only while their workgroups sum to no more than three per CU, then the queued ones are collected before the next is queued
     // (the barrier's spin time-out stays as the safety net, it is no longer the mechanism).
+    // The wide form (k_small16w) keeps the rule: its largest instantiations allocate 256 VGPRs + up to 72 AGPRs of the SIMD's 512, so such
+    // a wave is alone on its SIMD and a CU holds four of them - one more than the cap - and even if every narrow workgroup in flight took a
+    // SIMD of its own, 3 x CUs workgroups leave each of them one of the 4 x CUs SIMDs.  LDS: at most 16 x 100 + 4,920 words = 26 KB per
+    // wide workgroup, six per 160 KB.
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, loops[0]->device) != hipSuccess || n_cu <= 0) n_cu = 64;
     const long cap = 3L * n_cu;

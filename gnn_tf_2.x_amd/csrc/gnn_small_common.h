@@ -1,7 +1,8 @@
 // Shared phases of the persistent small-graph loop: ONE launch runs every body of a GNN.Loop (reference GNN/GNN.py:271, tf.while_loop
 // of condition :202-220 and convergence :223-242) when the batch is small enough for all of its tiles to be resident at once (BASELINE
-// configs[0] / [1]: a few hundred to a few thousand nodes, nets no wider than 32).  It has two forms that differ in the gather and the
-// dense layers only: k_small_loop on 32-node tiles (gnn_small_kernel.h) and k_small16 on 16-node tiles (gnn_small16_kernel.h); everything else is
+// configs[0] / [1]: a few hundred to a few thousand nodes, nets no wider than 32).  It has three forms that differ in the gather and the
+// dense layers only: k_small_loop on 32-node tiles (gnn_small_kernel.h), k_small16 on 16-node tiles (gnn_small16_kernel.h) and k_small16w on
+// 16-node tiles for hidden layers up to 64 wide (gnn_small16w_kernel.h); everything else is
 // here, templated on the rows per tile (ROWS = 32 or 16) where it depends on it, with the LDS layout (GnnSmallLds) and the instantiation
 // lists in gnn_fused.h.
 //
@@ -80,17 +81,23 @@ __device__ __forceinline__ int arrive_and_gate(const GnnSmallCtl &c, int b, int 
     return (seen >> 16) ? 1 : 0;
 }
 
-// Start of the launch: the last-layer bias and BatchNormalization scale / shift (ep [3][32]), the biases of the hidden layers (hb [2][32])
-// and, with the output stage folded in, the net_output head (hw: W [wf * T <= 512], then b | BN scale | BN shift [3][8]) into LDS
-template <int LAYERS>
+// Start of the launch: the last-layer bias and BatchNormalization scale / shift (ep [3][32]), the biases of the hidden layers (hb [2][HBW],
+// HBW = 32 or, for k_small16w, 64 floats of the bias image, which is zero behind the layer's width) and, with the output stage folded in,
+// the net_output head (hw: W [wf * T <= 512], then b | BN scale | BN shift [3][8]) into LDS
+template <int LAYERS, int HBW = 32>
 __device__ __forceinline__ void small_stage_vectors(const GnnFusedArgs &a0, const GnnSmallCtl &c, float *ep, float *hb, float *hw, int lane)
 {
+    static_assert(HBW == 32 || HBW == 64, "hidden layers of one or two 32-feature tiles");
     for (int t = lane; t < 3 * 32; t += 64) {
         const int which = t >> 5, f = t & 31;
         ep[t] = which == 0 ? a0.bias[LAYERS - 1][f] : (a0.bn_scale ? (which == 1 ? a0.bn_scale[f] : a0.bn_shift[f]) : 0.0f);
     }
-    if constexpr (LAYERS >= 2) {
+    if constexpr (LAYERS >= 2 && HBW == 32) {
         if (lane < 32 * (LAYERS - 1)) hb[lane] = a0.bias[lane >> 5][lane & 31];      // 64 lanes = 2 x 32 features
+    }
+    if constexpr (LAYERS >= 2 && HBW == 64) {
+#pragma unroll
+        for (int q = 0; q < LAYERS - 1; ++q) hb[64 * q + lane] = a0.bias[q][lane];
     }
     if (c.out) {
         const int nw = (a0.Ds + c.NLc) * c.T;

@@ -325,12 +325,16 @@ int gnn_loop_range_info(const gnn_loop *l, int *last_run_repeated, int *repeats_
  * [2^14, 2^15)), and the pieces p0 = fp16(v 2^e), p1 = fp16(v 2^e - p0) of n values (round to nearest even). */
 int gnn_split_f16_exponent(float max_abs);
 void gnn_split_f16(const float *v, int n, int e, uint16_t *p0, uint16_t *p1);
-/* Small graphs (every 32-node tile resident at once: <= 8,192 owned nodes, single GPU) with a net_state no wider than 32 run
- * the whole tf.while_loop of GNN/GNN.py:271 - initial state, first condition, every body with a grid barrier in between - in
- * ONE persistent launch when impl is 1 or 2 (exact f32-MFMA arithmetic in both cases, bit-identical to the oracle).  enable = 0
- * keeps such a loop to one launch per body; *used (may be NULL) tells whether the persistent launch will be taken.  The nets are those of
- * gnn_loop_set_impl: a last layer with an activation of its own takes the persistent launch too, two different hidden activations or a
- * softmax do not (per-op kernels). */
+/* Small graphs on a single GPU run the whole tf.while_loop of GNN/GNN.py:271 - initial state, first condition, every body with a grid
+ * barrier in between - in ONE persistent launch when impl is 1 or 2 (exact f32-MFMA arithmetic in both cases, bit-identical to the
+ * oracle).  The launch needs every tile resident at once and the net's weights in registers:
+ *   - a net_state no wider than 32 (every layer), concat width <= 96: up to 8,192 owned nodes;
+ *   - a net_state of two or three layers with hidden layers up to 64 wide (at least one above 32), state width <= 32, concat width
+ *     <= 96: up to 4,096 owned nodes.
+ * Everything else - a wide net on 4,097 .. 8,192 nodes, a state wider than 32, a concat wider than 96, 128-wide layers, more nodes, several
+ * ranks, profiling - takes one launch per body.  enable = 0 keeps such a loop to one launch per body too; *used (may be NULL) tells
+ * whether the persistent launch will be taken.  The nets are those of gnn_loop_set_impl: a last layer with an activation of its own takes
+ * the persistent launch too, two different hidden activations or a softmax do not (per-op kernels). */
 int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used);
 /* Which form of the fused iteration kernel runs the bodies of GNN/GNN.py:223-242 on the default path (impl 2) when both cover the
  * net (state width 64, two or three Dense layers, 128-wide hidden layers, concat width 129 .. 144, no feature-sliced exchange):
@@ -386,6 +390,12 @@ int gnn_loop_train_forms(const gnn_loop *l, int net, int *out);
  * the last layer; out[3], out[4] = 32-feature tiles of the hidden layers and of the last layer in the instantiated kernel (NT, NTL);
  * out[5] = 1 when the last layer's activation differs from the hidden one. */
 int gnn_fused_net_form(int n_layers, const int *dims, const int *acts, int n_label_cols_in_concat, int *out);
+/* Which persistent launch (gnn_loop_set_persistent) a net_state of this description takes on n_rows owned nodes, as far as the net and
+ * the node count decide it - host code, no device, the decision the loops themselves take; single GPU, "not disabled" and "not profiling"
+ * are the loop's part.  out receives 3 ints: out[0] = nodes per tile of the launch, 16 or 32, or 0 = no persistent launch (then the
+ * rest is 0); out[1] = 1 for the form with hidden layers up to 64 wide, 0 for the form with every layer <= 32; out[2] = K-steps of
+ * the first layer the kernel keeps in registers (of 4 concat columns on 16-node tiles, of 2 on 32-node tiles). */
+int gnn_small_form(int n_layers, const int *dims, const int *acts, int n_label_cols_in_concat, int64_t n_rows, int *out);
 /* per-kernel HIP-event timing of the last gnn_loop_run when profiling was enabled:
  * avg_iter_ms = mean duration of the per-iteration kernel(s), total_ms = whole loop on the stream. */
 int gnn_loop_set_profiling(gnn_loop *l, int enable);
