@@ -255,7 +255,8 @@ class LGNN(BaseClass):
             k, out_nodes = loop.train_forward(gnn.net_state.device_mlp(gnn.device), gnn.net_output.device_mlp(gnn.device), None,
                                               dropout_state=gnn.net_state.dropout_rates(), dropout_output=gnn.net_output.dropout_rates(),
                                               masks_state=masks_state[idx], masks_output=masks_output[idx],
-                                              seed=gnn.seed * 1000003 + gnn._train_calls, bn_state=None, bn_output=None)     # gamma / beta: the device copies
+                                              seed=((gnn.seed * 1000003 + gnn._train_calls) * 1000003 + idx) % 2 ** 64,    # (the layers' seeds advance in step: the layer index keeps their masks apart)
+                                              bn_state=None, bn_output=None)     # gamma / beta: the device copies
             loops.append(loop); K.append(k)
             outs.append(loop.readout(*g.nodegraph_csr()) if graph_based else out_nodes)
             if idx < L - 1:

@@ -20,7 +20,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_mlp_create', 'gnn_mlp_set_weights', 'gnn_mlp_get_weights', 'gnn_mlp_reset_optimizer', 'gnn_mlp_forward', 'gnn_mlp_destroy', 'gnn_loop_create',
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
-           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_fused_net_form', 'gnn_small_form',
+           'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_loop_train_mask', 'gnn_fused_net_form', 'gnn_small_form',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -694,6 +694,16 @@ class Loop:
         out = np.zeros(3 + 3 * self._keep[1 + net].n, np.int32)
         _check(lib().gnn_loop_train_forms(self._h, C.c_int(net), _ip(out)))
         return _forms_dict(out)
+
+    def train_mask(self, net: int, body: int, pos: int) -> np.ndarray:
+        """gnn_loop_train_mask (introspection for tests): the keep mask [rows, width] (bool) that the last train_forward() / train_step()
+        applied at Dropout position pos of net_state (net 0, body < k) or net_output (net 1) - injected or drawn."""
+        count = C.c_int64()
+        _check(lib().gnn_loop_train_mask(self._h, C.c_int(net), C.c_int(body), C.c_int(pos), None, C.byref(count)))
+        width = int(self._keep[1 + net].dims[pos])
+        out = np.zeros(count.value, np.uint8)
+        _check(lib().gnn_loop_train_mask(self._h, C.c_int(net), C.c_int(body), C.c_int(pos), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(count)))
+        return out.reshape(-1, width).astype(bool)
 
     def set_impl(self, impl: int) -> int:
         used = C.c_int(0)

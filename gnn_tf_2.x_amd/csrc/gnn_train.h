@@ -69,16 +69,31 @@ inline int64_t rows_per_block(int64_t n)
 inline unsigned elementwise_grid(int64_t total) { return (unsigned)std::min<int64_t>(std::max<int64_t>(1, (total + 255) / 256), 2048); }
 
 // ---- device code that two units inline ---------------------------------------------------------------------------------
-// mix64, alpha_dropout_coeffs: the Dropout masks of k_dropout_fwd (gnn_train_net.hip) and of k_train_input (gnn_train.hip: the Dropout in
+// mix64, dropout_key, dropout_keep, alpha_dropout_coeffs: the Dropout masks of k_dropout_fwd (gnn_train_net.hip) and of k_train_input (gnn_train.hip: the Dropout in
 // front of net_state's first layer rides on the concat) are one generator.  act_grad, dropout_grad: the way back through an activation /
 // a Dropout is the epilogue of k_act_bwd, k_bn_bwd_apply, k_layer_bwd (gnn_train_net.hip) and of k_gemm_f32, k_gemm_split, k_bwd3_split
 // (gnn_train_wide.hip).  All four are forced inline: a kernel's code does not depend on the unit it is compiled in.
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x)
 {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
+}
+
+// One stream of mask bits per use: the key of the Dropout at position `pos` of net `net` (0 net_state, 1 net_output) in body `body`
+// (net_output: 0) of a step with `seed`.  Element `index` of that mask - its flat index in the [rows of ALL ranks, width] matrix - is kept
+// when the top 24 bits of mix64(key ^ mix64(index)) / 2^24 >= rate (dropout_keep).  The key is HASHED from its parts: keys made by adding
+// multiples of constants to the seed met each other (seed + 7919 in body e drew the masks of seed in body e + 1), and neighbouring seeds
+// are what callers pass.
+__host__ __device__ __forceinline__ uint64_t dropout_key(uint64_t seed, int net, int body, int pos)
+{
+    return mix64(mix64(seed) ^ ((uint64_t)net << 56 | (uint64_t)(uint32_t)body << 16 | (uint64_t)(uint32_t)pos));
+}
+
+__device__ __forceinline__ uint8_t dropout_keep(uint64_t key, uint64_t index, float rate)
+{
+    return ((mix64(key ^ mix64(index)) >> 40) * (1.0f / 16777216.0f)) >= rate;
 }
 
 // AlphaDropout (Keras; reference GNN/MLP.py:59-61 with alphadropout=True) is passed as a NEGATIVE rate: dropped units are set to
@@ -125,6 +140,15 @@ struct Buf {                      // typed front end of the arena
         if (!*p) return gnn_fail(GNN_ERR_HIP, "hipMalloc of %zu bytes failed", count * sizeof(T));
         return GNN_OK;
     }
+};
+
+// Where the masks of one net_forward call come from when none are injected: the step's seed, which net and body this call is
+// (dropout_key) and the row of the whole graph's matrix that the call's first row is (0 on one GPU; on shards the rows / masked rows of
+// the lower ranks, so that a seed draws the same masks for any number of ranks).
+struct MaskStream {
+    uint64_t seed = 0;
+    int net = 0, body = 0;
+    int64_t row0 = 0;
 };
 
 struct NetCache {                 // what one training-mode forward of a Sequential leaves for the backward pass
@@ -212,7 +236,7 @@ inline bool state_rows16(int Ds, int64_t n) { return (Ds & 3) == 0 && Ds <= 64 &
 // gnn_train_net.hip: one Sequential in training mode
 int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
               int64_t rows, bool producer_dropout);
-int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, uint64_t seed, NetCache &c, float **y_out,
+int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, const MaskStream &rng, NetCache &c, float **y_out,
                 gnn_comm *comm = nullptr, const InputBuild *build = nullptr);
 int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job = nullptr,
                  gnn_comm *comm = nullptr, int64_t n_global = 0);
@@ -235,6 +259,7 @@ struct GNN_INTERNAL gnn_train_ctx {
     int k = 0;
     int64_t N = 0, M = 0;
     int64_t N_global = 0, M_global = 0;   // sharded forward: the rows / masked rows of all ranks
+    int64_t M_before = 0;                 // ... and the masked rows of the lower ranks
     bool backward_done = false;   // the gradients are complete (and the activations spent)
     bool applied = false;         // gnn_loop_optimizer_step has consumed them
     // regularizer penalty, per-block partials of k_grad_prepare: net_state's blocks, then net_output's (0 blocks: no regularizer there)

@@ -32,14 +32,15 @@ namespace {
 
 // The concat of one body (reference GNN/GNN.py:223-239) in one pass: [state | node labels | aggregated states | aggregated labels |
 // aggregated arc labels].  Everything but the state columns and their aggregate is loop-invariant and comes from the template.
-// Dropout in front of the first Dense layer (rate != 0) is applied on the way out.  The thread of column 0 also evaluates the
+// Dropout in front of the first Dense layer (rate != 0) is applied on the way out (own masks: stream `key`, element idx0 + i - idx0, the
+// elements of the lower ranks' rows, enters the hashed index only).  The thread of column 0 also evaluates the
 // while-condition of THIS body for its node (reference GNN/GNN.py:202-220: condition(state, state_old), ascending-feature sums as
 // k_check; so == NULL: ones) and raises the body's gate.
 // state: row 0 of the state REPLICA (the sources of the arcs are replica rows); own: the first OWNED row of it (== state on one GPU)
 __global__ void __launch_bounds__(256) k_train_input(int64_t n, int in_s, int Ds, int c_aggs, const float *__restrict__ tmpl, const float *__restrict__ state,
                                                      const float *__restrict__ own,
                                                      const int32_t *__restrict__ indptr, const int32_t *__restrict__ adj_src,
-                                                     const float *__restrict__ adj_w, float rate, const uint8_t *mask_in, uint64_t seed, uint8_t *keep,
+                                                     const float *__restrict__ adj_w, float rate, const uint8_t *mask_in, uint64_t key, int64_t idx0, uint8_t *keep,
                                                      float *__restrict__ inp, const float *__restrict__ so, float thr, int *flag)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -97,7 +98,7 @@ __global__ void __launch_bounds__(256) k_train_input(int64_t n, int in_s, int Ds
             const float rr = fabsf(rate);
             uint8_t kp;
             if (mask_in) kp = mask_in[i] != 0;
-            else kp = ((mix64(seed ^ mix64((uint64_t)i)) >> 40) * (1.0f / 16777216.0f)) >= rr;
+            else kp = dropout_keep(key, (uint64_t)(idx0 + i), rr);
             keep[i] = kp;
             if (rate < 0.0f) {
                 float a, b, ap;
@@ -533,7 +534,10 @@ struct Forward {
             std::vector<int> all((size_t)4 * l->world);
             HIPCHK(hipStreamSynchronize(st));
             HIPCHK(hipMemcpy(all.data(), cnt_all, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
-            for (int p = 0; p < l->world; ++p) { cx->N_global += all[(size_t)4 * p]; cx->M_global += all[(size_t)4 * p + 1]; }
+            for (int p = 0; p < l->world; ++p) {
+                cx->N_global += all[(size_t)4 * p]; cx->M_global += all[(size_t)4 * p + 1];
+                if (p < l->rank) cx->M_before += all[(size_t)4 * p + 1];
+            }
         } else if (src_indptr) {
             ARGCHK(src_indptr[0] == 0 && src_indptr[N] == E && (E == 0 || (src_dst && src_w)), "bad by-source CSR");
             if ((rc = upload_by_source(cx, N, E, src_indptr, src_dst, src_w))) return rc;
@@ -591,7 +595,7 @@ struct Forward {
         if ((rc = buf.get(&inp, (size_t)N * in_s))) return rc;
         if (r0 != 0.0f && (rc = buf.get(&keep0, (size_t)N * in_s))) return rc;
         const uint8_t *mk = d_masks_s ? d_masks_s + mask_iter_bytes * (size_t)enq : nullptr;
-        const uint64_t sd = seed + 7919ull * (uint64_t)(enq + 1);
+        const MaskStream rng{seed, 0, enq, sharded ? g->row_begin : 0};
         const float *state = states[enq], *own_cur = state + own_off * Ds, *own_prev = enq ? states[enq - 1] + own_off * Ds : (const float *)nullptr;
         int *gate = flags + (size_t)enq * GNN_FLAG_WORDS;
         // few rows: k_mlp_fwd builds the concat rows itself (one launch for input + all Dense layers) and evaluates the gate
@@ -607,11 +611,11 @@ struct Forward {
         } else {
             // the input kernel of body i also evaluates gate i = condition(state_i, state_{i-1})
             hipLaunchKernelGGL(k_train_input, cdiv(N * in_s, 256), 256, 0, st, N, in_s, Ds, c_aggs, tmpl, state, own_cur, g->sh->indptr, g->sh->adj_src,
-                               g->sh->adj_w, r0, mk, sd + 0x9E37ull, keep0, inp, own_prev, l->thr, gate);
+                               g->sh->adj_w, r0, mk, dropout_key(seed, 0, enq, 0), rng.row0 * in_s, keep0, inp, own_prev, l->thr, gate);
             HIPCHK(hipGetLastError());
         }
         cx->caches.emplace_back();
-        if ((rc = net_forward(st, buf, cx->ns, inp, keep0, mk, sd, cx->caches.back(), &y, comm, &build))) return rc;
+        if ((rc = net_forward(st, buf, cx->ns, inp, keep0, mk, rng, cx->caches.back(), &y, comm, &build))) return rc;
         if (sharded) {                               // the new rows of all ranks: what the next body gathers from
             float *rep = nullptr;
             if ((rc = train_replicate(l, buf, st, y, &rep))) return rc;
@@ -660,7 +664,7 @@ struct Forward {
             hipLaunchKernelGGL(k_gather_feats, cdiv(M * wf, 256), 256, 0, st, M, g->sh->masked_rows, state + own_off * Ds, Ds, g->nodes + (size_t)g->own_off * g->NL, g->NL, l->NLc, feats);
             HIPCHK(hipGetLastError());
         }
-        return net_forward(st, cx->buf, cx->no_, feats, nullptr, d_masks_o, seed + 104729ull, cx->co, &cx->out_nodes, comm, nullptr);
+        return net_forward(st, cx->buf, cx->no_, feats, nullptr, d_masks_o, MaskStream{seed, 1, 0, cx->M_before}, cx->co, &cx->out_nodes, comm, nullptr);
     }
 
     // publish the training-mode state / outputs as the loop's result: gnn_loop_get_state / get_output / readout and
@@ -930,6 +934,27 @@ extern "C" int gnn_loop_train_forms(const gnn_loop *l, int net, int *out)
     const gnn_train_ctx *cx = l->train_ctx;
     if (!cx) return gnn_fail(GNN_ERR_STATE, "gnn_loop_train_forward has not been called");
     gnn_train::net_forms(net == 0 ? cx->ns : cx->no_, out);
+    return GNN_OK;
+}
+
+// the keep bytes of one Dropout of the last training forward (they live in the arena, which only the next forward resets: neither the
+// backward pass nor the optimizer step nor an inference run writes them)
+extern "C" int gnn_loop_train_mask(const gnn_loop *l, int net, int body, int pos, uint8_t *out, int64_t *count)
+{
+    ARGCHK(l && count && (net == 0 || net == 1), "bad arguments");
+    const gnn_train_ctx *cx = l->train_ctx;
+    if (!cx) return gnn_fail(GNN_ERR_STATE, "gnn_loop_train_forward has not been called");
+    const Net &n = net == 0 ? cx->ns : cx->no_;
+    ARGCHK(net == 1 || (body >= 0 && body < cx->k), "body %d: the last training forward ran %d", body, cx->k);
+    ARGCHK(pos >= 0 && pos <= n.m->n_layers && n.rate[pos] != 0.0f, "no Dropout at position %d of this net", pos);
+    const NetCache &c = net == 0 ? cx->caches[(size_t)body] : cx->co;
+    if ((size_t)pos >= c.keep.size() || !c.keep[pos]) return gnn_fail(GNN_ERR_STATE, "internal: no mask recorded at position %d", pos);
+    *count = n.rows * n.m->dims[pos];
+    if (out && *count) {
+        HIPCHK(hipSetDevice(l->device));
+        HIPCHK(hipStreamSynchronize(l->stream));
+        HIPCHK(hipMemcpy(out, c.keep[pos], (size_t)*count, hipMemcpyDeviceToHost));
+    }
     return GNN_OK;
 }
 

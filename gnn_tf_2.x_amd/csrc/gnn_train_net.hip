@@ -9,15 +9,16 @@ using namespace gnn_train;
 
 namespace {
 
-// Dropout forward: keep[i] = injected mask or own RNG; y = x * keep / (1 - rate); keep bytes are stored for the backward pass
-__global__ void k_dropout_fwd(int64_t n, const float *x, const uint8_t *mask_in, float rate, uint64_t seed, uint8_t *keep, float *y)
+// Dropout forward: keep[i] = injected mask or own RNG (stream `key`, element idx0 + i: idx0 is added to the hashed index only, not to
+// addresses); y = x * keep / (1 - rate); keep bytes are stored for the backward pass
+__global__ void k_dropout_fwd(int64_t n, const float *x, const uint8_t *mask_in, float rate, uint64_t key, int64_t idx0, uint8_t *keep, float *y)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float r = fabsf(rate);
     uint8_t kp;
     if (mask_in) kp = mask_in[i] != 0;
-    else kp = ((mix64(seed ^ mix64((uint64_t)i)) >> 40) * (1.0f / 16777216.0f)) >= r;
+    else kp = dropout_keep(key, (uint64_t)(idx0 + i), r);
     keep[i] = kp;
     if (rate < 0.0f) {
         float a, b, ap;
@@ -799,10 +800,11 @@ int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float 
 }
 
 // training-mode forward of one Sequential on its net.rows rows (x: [rows, dims[0]]); *y_out: [rows, dims.back()].  keep0 != NULL: the Dropout
-// in front of the first Dense layer has been applied by the producer of x (k_train_input), its mask is keep0.
+// in front of the first Dense layer has been applied by the producer of x (k_train_input), its mask is keep0.  rng: the streams of the
+// masks that are not injected (masks == NULL).
 // comm != NULL (sharded forward, one process per rank): the BatchNormalization statistics are those of the rows of ALL ranks.
 // net.build_input: x has NOT been filled - k_mlp_fwd builds the concat rows itself (and writes them to x for the backward pass) from *build.
-int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, uint64_t seed, NetCache &c, float **y_out,
+int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, const MaskStream &rng, NetCache &c, float **y_out,
                 gnn_comm *comm, const InputBuild *build)
 {
     const gnn_mlp *m = net.m;
@@ -832,7 +834,7 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
                 if ((rc = buf.get(&hd, (size_t)n * width)) || (rc = buf.get(&c.keep[l], (size_t)n * width))) return rc;
                 if (n > 0) {
                     hipLaunchKernelGGL(k_dropout_fwd, cdiv(n * width, 256), 256, 0, st, n * width, h, masks ? masks + mask_off : nullptr, net.rate[l],
-                                       seed + 0x9E37ull * (uint64_t)(l + 1), c.keep[l], hd);
+                                       dropout_key(rng.seed, rng.net, rng.body, l), rng.row0 * width, c.keep[l], hd);
                     HIPCHK(hipGetLastError());
                 }
                 h = hd;

@@ -170,6 +170,13 @@ int gnn_loop_set_edge_readout(gnn_loop *l, const int32_t *entry_dst, const float
  *                    of rate r (MLP(..., alphadropout=True), GNN/MLP.py:59-61)
  *   masks_*          injected keep-masks (uint8, 1 = keep): for net_state max_iter blocks, each the concatenation over the
  *                    dropout positions of [N, width]; for net_output one such block over the masked rows; NULL = engine RNG(seed)
+ *   seed             defines every mask the engine draws in this step.  Each Dropout use - (net, body, position) - has a stream of its own,
+ *                    keyed by HASHING: key = mix64(mix64(seed) ^ tag), tag = net << 56 | body << 16 | position (net 0 = net_state, 1 =
+ *                    net_output with body 0; mix64 = the splitmix64 finalizer); element i of the mask, i its flat index in the
+ *                    [rows of the WHOLE graph, width] matrix, is kept when the top 24 bits of mix64(key ^ mix64(i)) / 2^24 >= rate.
+ *                    Neighbouring seeds, bodies and positions therefore draw unrelated masks, and because i counts the rows (net_output:
+ *                    the masked rows) of the lower ranks too, a seed defines the step whatever the number of ranks: the masks of a
+ *                    sharded gnn_loop_train_forward are the rows of the unsharded one's.  gnn_loop_train_mask reads them back.
  *   bn_state / bn_output   [gamma | beta] of the trailing BatchNormalization (NULL without one)
  * Outputs: *loss_out, *k_out (executed bodies), grads_* flat in get_weights() order of the TRAINABLE arrays
  * [dW1, db1, ..., dgamma, dbeta] (raw sums over the iterations: the division by k of :241 is the caller's), bn_batch_state
@@ -384,6 +391,14 @@ int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *b
 enum { GNN_FORM_PER_OP = 0, GNN_FORM_MLP_FWD = 1, GNN_FORM_WIDE = 2, GNN_FORM_CHAIN3 = 3, GNN_FORM_WGRAD_BF = 4, GNN_FORM_WGRAD_F32 = 5 };
 int gnn_train_forms(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int producer_dropout, int *out);
 int gnn_loop_train_forms(const gnn_loop *l, int net, int *out);
+/* Introspection for tests: the keep bytes (1 = kept) that the last gnn_loop_train_forward / gnn_loop_train_step of this loop recorded for the
+ * Dropout at position pos (0 .. n_layers, the index of dropout_state / dropout_output) of net 0 (net_state, in body `body` < k) or 1
+ * (net_output, body ignored) - the mask that was APPLIED, whether injected or drawn.  *count = rows * width of that position (this rank's rows /
+ * masked rows); out [*count] may be NULL to ask for the count alone.  Valid from the forward until the next training forward of the loop:
+ * the bytes stay intact through gnn_loop_train_backward, the optimizer step and inference runs (they live in the step's scratch, which
+ * only the next training forward reuses).  GNN_ERR_STATE before the first training forward; GNN_ERR_ARG for body >= k, a position whose
+ * rate is 0, a net other than 0 / 1. */
+int gnn_loop_train_mask(const gnn_loop *l, int net, int body, int pos, uint8_t *out, int64_t *count);
 /* What the fused inference paths (impl 1 / 2, the persistent launch) make of a net_state of this description - dims [n_layers + 1], acts
  * [n_layers] (gnn_activation codes), node-label columns in the concat; host code, no device, the decision the loops themselves take.
  * out receives 6 ints: out[0] = 1 covered / 0 not (then the rest is 0); out[1] = activation of the hidden layers; out[2] = activation of

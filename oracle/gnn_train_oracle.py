@@ -51,13 +51,15 @@ def act_backward(da, z, a, name):
 def mlp_train_forward(x, net, masks, dtype=np.float64):
     """Training-mode forward of the Sequential of MLP.py:46-64.
     net: dict(weights, activations, batch_normalization, dropout={dense_index: rate}) - a Dropout sits in FRONT of Dense
-    number dense_index; masks: {dense_index: 0/1 array shaped like that layer's input}.  Returns (y, cache)."""
+    number dense_index; dense_index == number of Dense layers: behind the last one, in front of BatchNormalization (MLP.py:54-55 with
+    dropout_pos = len(layers)); masks: {dense_index: 0/1 array shaped like that layer's input}.  Returns (y, cache)."""
     n = len(net['activations'])
     W = [np.asarray(net['weights'][2 * l], dtype) for l in range(n)]
     b = [np.asarray(net['weights'][2 * l + 1], dtype) for l in range(n)]
     h = np.asarray(x, dtype)
     cache = dict(h_in=[], z=[], a=[], scale={})
-    for l in range(n):
+
+    def dropout(h, l):
         rate = net.get('dropout', {}).get(l)
         if rate and net.get('alphadropout'):
             # Keras AlphaDropout (MLP.py:59-61 with alphadropout=True): dropped units -> alpha' = -scale * alpha, then a x + b
@@ -71,10 +73,15 @@ def mlp_train_forward(x, net, masks, dtype=np.float64):
             sc = np.asarray(masks[l], dtype) / dtype(1 - rate)
             cache['scale'][l] = sc
             h = h * sc
+        return h
+
+    for l in range(n):
+        h = dropout(h, l)
         z = h @ W[l] + b[l]
         a = act_forward(z, net['activations'][l])
         cache['h_in'].append(h); cache['z'].append(z); cache['a'].append(a)
         h = a
+    h = dropout(h, n)
     if net['batch_normalization']:
         gamma, beta = (np.asarray(v, dtype) for v in net['weights'][2 * n:2 * n + 2])
         mu = h.mean(axis=0)
@@ -98,6 +105,8 @@ def mlp_train_backward(dy, net, cache, dtype=np.float64):
         grads_bn = [np.sum(d * xhat, axis=0), np.sum(d, axis=0)]
         dxh = d * gamma
         d = inv / m * (m * dxh - dxh.sum(axis=0) - xhat * np.sum(dxh * xhat, axis=0))
+    if n in cache['scale']:
+        d = d * cache['scale'][n]
     grads = [None] * (2 * n)
     for l in reversed(range(n)):
         dz = act_backward(d, cache['z'][l], cache['a'][l], net['activations'][l])

@@ -10,6 +10,9 @@ for p in (ROOT, os.path.join(ROOT, 'gnn_tf_2.x_amd'), os.path.join(ROOT, 'tests'
     sys.path.insert(0, p)
 
 
+TRAIN_DROPOUT = ([0.2, 0, 0], [0.1, 0], 20261018)      # net_state rates, net_output rates, seed of the sharded step with drawn masks
+
+
 def main():
     rank, world, out_dir = int(os.environ['RANK']), int(os.environ['WORLD_SIZE']), sys.argv[1]
     import bench
@@ -127,10 +130,11 @@ def main():
         l1.close(); l0.close(); comm.close()
 
     # ---- training-mode forward on shards (gnn_loop_train_forward with world > 1): state rows all-gathered after every body, the
-    # BatchNormalization statistics and the iteration gates those of all ranks.  Two cases: few rows (per-op kernels) and, MP_TRAIN_WIDE,
-    # the wide-layer path.
+    # BatchNormalization statistics and the iteration gates those of all ranks.  Three cases: few rows (per-op kernels), the wide-layer path,
+    # and the few-rows shape with Dropout in front of both nets' first layer, the masks drawn by the engine (TRAIN_DROPOUT: rates and seed;
+    # every rank stores the masks it read back - the test holds their concatenation against the unsharded step's).
     from util import make_mlp
-    for tag, (nt, dt, hidden, thr_t) in (('train', (1531, 8, (16,), 0.02)), ('trainw', (12000, 64, (128, 128), 0.0))):
+    for tag, (nt, dt, hidden, thr_t) in (('train', (1531, 8, (16,), 0.02)), ('trainw', (12000, 64, (128, 128), 0.0)), ('traind', (1531, 8, (16,), 0.0))):
         gt, stt, out_, s0t = S._case(777 + nt, nt, dt, hidden=hidden)
         rngt = np.random.default_rng(nt)
         stt = make_mlp(rngt, stt['weights'][0].shape[0], list(hidden) + [dt], 'selu' if tag == 'train' else 'tanh', gain=0.6, bn_random=True)      # (wide case: a smooth activation - SELU's kink makes single gradient entries jump)
@@ -150,7 +154,11 @@ def main():
         from test_gpu_train import _by_source_csr
         sip, sdst, sw = _by_source_csr(gt, nt)
         own = (sip[rb:rb + nr + 1] - sip[rb]).astype(np.int32), sdst[sip[rb]:sip[rb + nr]], sw[sip[rb]:sip[rb + nr]]
-        k, outn = lp.train_forward(mst, mou, own, bn_state=np.concatenate(stt['weights'][-4:-2]), bn_output=np.concatenate(out_['weights'][-4:-2]))
+        drop = dict(dropout_state=TRAIN_DROPOUT[0], dropout_output=TRAIN_DROPOUT[1], seed=TRAIN_DROPOUT[2]) if tag == 'traind' else {}
+        k, outn = lp.train_forward(mst, mou, own, bn_state=np.concatenate(stt['weights'][-4:-2]), bn_output=np.concatenate(out_['weights'][-4:-2]), **drop)
+        if drop:
+            for body in range(int(k)): res[f'{tag}_ms{body}'] = lp.train_mask(0, body, 0)
+            res[f'{tag}_mo'] = lp.train_mask(1, 0, 0)
         res[f'{tag}_k'] = np.float64(k)
         res[f'{tag}_state'] = lp.state()
         res[f'{tag}_out'] = outn
@@ -165,6 +173,12 @@ def main():
         res[f'{tag}_loss'] = np.float64(loss)
         for i, garr in enumerate(back['grads_state']): res[f'{tag}_gs{i}'] = garr
         for i, garr in enumerate(back['grads_output']): res[f'{tag}_go{i}'] = garr
+        if drop:        # the engine's own initial state on shards: the rows of the unsharded draw (a Loop of no bodies returns it)
+            lp0 = e.Loop(gr, mst, mou, dt, 0, thr_t, comm)
+            lp0.set_state0(None, seed=TRAIN_DROPOUT[2])
+            assert lp0.run() == 0
+            res[f'{tag}_state0'] = lp0.state()
+            lp0.close()
         lp.close(); comm.close()
     np.savez(os.path.join(out_dir, f'rank{rank}.npz'), **res)
     print(f'MP_WORKER_OK rank={rank}')

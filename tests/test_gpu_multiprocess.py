@@ -41,7 +41,8 @@ def test_ranks_as_processes_match_oracle(world):
     """world processes, every exchange layout, impl 1 bit-identical to the C oracle (k, states, outputs), impl 2 within tolerance; then the
     training step on shards - forward (state all-gather per body, BatchNormalization statistics and gates of all ranks) and backward (the
     aggregate-column gradients all-gathered per body, BatchNormalization sums of all ranks, the ranks' weight-gradient shares added in rank
-    order) - against the float64 oracle and the one-GPU forward."""
+    order) - against the float64 oracle and the one-GPU forward; once more with Dropout masks drawn by the engine, which must be the
+    unsharded step's masks (as the engine's own initial state is the unsharded one's)."""
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import test_gpu_sharded as S
     n, d = 4099, 8
@@ -118,13 +119,38 @@ def test_ranks_as_processes_match_oracle(world):
     from oracle import gnn_train_oracle as tro
     from util import make_mlp
     from GNN import _engine as e
-    for tag, (nt, dt, hidden, thr_t) in (('train', (1531, 8, (16,), 0.02)), ('trainw', (12000, 64, (128, 128), 0.0))):
+    from _mp_worker import TRAIN_DROPOUT
+    for tag, (nt, dt, hidden, thr_t) in (('train', (1531, 8, (16,), 0.02)), ('trainw', (12000, 64, (128, 128), 0.0)), ('traind', (1531, 8, (16,), 0.0))):
         gt, stt, out_, s0t = S._case(777 + nt, nt, dt, hidden=hidden)
         rngt = np.random.default_rng(nt)
         stt = make_mlp(rngt, stt['weights'][0].shape[0], list(hidden) + [dt], 'selu' if tag == 'train' else 'tanh', gain=0.6, bn_random=True)      # (wide case: a smooth activation - SELU's kink makes single gradient entries jump)
         out_ = make_mlp(rngt, out_['weights'][0].shape[0], [2], 'softmax', bn_random=True)
         stt['dropout'], out_['dropout'] = {}, {}
-        ctx = tro.train_forward(gt, stt, out_, dt, 4, thr_t, s0t, [{}] * 4, {})
+        ipt, srct, wt, awt, alt = S._csr_parts(gt)
+        maskt = np.logical_and(gt['set_mask'], gt['output_mask'])
+        mst, mou = e.Mlp(stt['weights'], stt['activations'], True), e.Mlp(out_['weights'], out_['activations'], True)
+        lp = e.Loop(e.Graph(nt, ipt, srct, wt, awt, alt, gt['nodes'], maskt), mst, mou, dt, 4, thr_t)
+        lp.set_state0(s0t)
+        masks_s, masks_o, drop = [{}] * 4, {}, {}
+        if tag == 'traind':
+            # ---- masks drawn by the engine: a seed defines the step whatever the number of ranks - the ranks' masks, one after the other,
+            # are the masks of the unsharded forward with that seed; the float64 oracle below takes them
+            drop = dict(dropout_state=TRAIN_DROPOUT[0], dropout_output=TRAIN_DROPOUT[1], seed=TRAIN_DROPOUT[2])
+            stt['dropout'], out_['dropout'] = {0: TRAIN_DROPOUT[0][0]}, {0: TRAIN_DROPOUT[1][0]}
+            k1, _ = lp.train_forward(mst, mou, None, bn_state=np.concatenate(stt['weights'][-4:-2]), bn_output=np.concatenate(out_['weights'][-4:-2]), **drop)
+            assert k1 == 4 and {float(r[f'{tag}_k']) for r in res} == {4.0}
+            masks_s, masks_o = [{0: lp.train_mask(0, body, 0)} for body in range(4)], {0: lp.train_mask(1, 0, 0)}
+            for body in range(4):
+                got = np.concatenate([r[f'{tag}_ms{body}'] for r in res])
+                assert got.shape == masks_s[body][0].shape and np.array_equal(got, masks_s[body][0]), (body, float(np.mean(got == masks_s[body][0])))
+            got = np.concatenate([r[f'{tag}_mo'] for r in res])
+            assert got.shape == masks_o[0].shape and np.array_equal(got, masks_o[0]), float(np.mean(got == masks_o[0]))
+            # ... and set_state0(None, seed) on shards draws the rows of the unsharded initial state
+            lp0 = e.Loop(lp.graph, mst, mou, dt, 0, thr_t)
+            lp0.set_state0(None, seed=TRAIN_DROPOUT[2])
+            assert lp0.run() == 0
+            assert np.array_equal(np.concatenate([r[f'{tag}_state0'] for r in res]), lp0.state())
+        ctx = tro.train_forward(gt, stt, out_, dt, 4, thr_t, s0t, masks_s, masks_o)
         ks = {float(r[f'{tag}_k']) for r in res}
         assert ks == {float(ctx['k'])} and ctx['k'] >= 2, (tag, ks, ctx['k'])
         state = np.concatenate([r[f'{tag}_state'] for r in res])
@@ -135,12 +161,7 @@ def test_ranks_as_processes_match_oracle(world):
             (tag, float(np.max(np.abs(state - ctx['state']))), float(np.max(np.abs(outp - ctx['out_nodes']))))
         # one GPU: the order in which the chunk statistics of BatchNormalization are merged differs, and with few rows per rank the dense
         # products run on the FP32 ALUs instead of the matrix cores (gnn_train_wide.hip, tg_many_rows): float32-level differences
-        ipt, srct, wt, awt, alt = S._csr_parts(gt)
-        maskt = np.logical_and(gt['set_mask'], gt['output_mask'])
-        mst, mou = e.Mlp(stt['weights'], stt['activations'], True), e.Mlp(out_['weights'], out_['activations'], True)
-        lp = e.Loop(e.Graph(nt, ipt, srct, wt, awt, alt, gt['nodes'], maskt), mst, mou, dt, 4, thr_t)
-        lp.set_state0(s0t)
-        k1, out1 = lp.train_forward(mst, mou, None, bn_state=np.concatenate(stt['weights'][-4:-2]), bn_output=np.concatenate(out_['weights'][-4:-2]))
+        k1, out1 = lp.train_forward(mst, mou, None, bn_state=np.concatenate(stt['weights'][-4:-2]), bn_output=np.concatenate(out_['weights'][-4:-2]), **drop)
         so_ = max(1.0, float(np.max(np.abs(out1))))
         assert k1 == ctx['k'] and np.max(np.abs(lp.state() - state)) < 2e-5 * scale and np.max(np.abs(out1 - outp)) < 2e-5 * so_
         # ---- the backward half on the shards: every rank returns the same, complete gradients; against the float64 oracle's step
@@ -148,7 +169,7 @@ def test_ranks_as_processes_match_oracle(world):
         rngl = np.random.default_rng(99)
         targets = np.eye(2)[rngl.integers(0, 2, m_all)].astype(np.float32)
         weights = (rngl.uniform(0.5, 1.5, m_all) / m_all).astype(np.float32)
-        ref = tro.train_step(gt, stt, out_, dt, 4, thr_t, s0t, [{}] * 4, {}, targets, weights, loss='categorical_crossentropy', mean=False, graph_based=False)
+        ref = tro.train_step(gt, stt, out_, dt, 4, thr_t, s0t, masks_s, masks_o, targets, weights, loss='categorical_crossentropy', mean=False, graph_based=False)
         assert abs(sum(float(r[f'{tag}_loss']) for r in res) - ref['loss']) < 1e-5 * max(1.0, abs(ref['loss']))
         gscale = max(float(np.max(np.abs(w_))) for w_ in ref['grads_state'])
         for name, wl in (('gs', ref['grads_state']), ('go', ref['grads_output'])):

@@ -95,7 +95,8 @@ def test_train_step_matches_oracle(d, graph_based, act, loss, alpha):
     for a_, b_ in zip(again['grads_state'] + again['grads_output'], res['grads_state'] + res['grads_output']):
         assert np.array_equal(a_, b_)
     assert np.array_equal(again['bn_batch_state'], res['bn_batch_state']) and np.array_equal(again['bn_batch_output'], res['bn_batch_output'])
-    # engine RNG masks: same call without injected masks must run and give finite numbers with about the right keep rate
+    # engine RNG masks: same call without injected masks must run and give finite numbers (the drawn masks themselves - keep rate,
+    # independence, the oracle on them - are tests/test_gpu_dropout_rng.py)
     res2 = loop.train_step(mst, mou, _by_source_csr(g, n), targets, weights, kind, ng_csr,
                            dropout_state=[sgn * 0.2, 0, 0], dropout_output=[sgn * 0.1, sgn * 0.3, 0], seed=5,
                            bn_state=np.concatenate(st['weights'][-4:-2]), bn_output=np.concatenate(ou['weights'][-4:-2]))

@@ -67,6 +67,35 @@ def test_gradients_match_finite_differences(d, graph_based, act, loss, alpha):
         np.testing.assert_allclose(a, b, rtol=1e-12)
 
 
+@pytest.mark.parametrize('alpha', [False, True])
+def test_dropout_inside_and_behind_the_net_matches_finite_differences(alpha):
+    """Dropout in front of the second Dense layer and behind the last one, in front of BatchNormalization (dense_index == number of Dense
+    layers: MLP.py:54-55 with dropout_pos = len(layers)) - the positions the engine's k_dropout_fwd serves."""
+    rng = np.random.default_rng(17)
+    g, st, ou, s0, _, _, targets, weights = _case(rng, 4, act='selu')
+    n, m = g['nodes'].shape[0], len(targets)
+    st['dropout'], ou['dropout'] = {1: 0.25, 2: 0.15}, {2: 0.2}
+    if alpha: st['alphadropout'] = ou['alphadropout'] = True
+    ms = [{1: rng.random((n, 7)) > 0.25, 2: rng.random((n, 4)) > 0.15} for _ in range(3)]
+    mo = {2: rng.random((m, 2)) > 0.2}
+    kw = dict(state_vect_dim=4, max_iteration=3, threshold=0.0, state0=s0, masks_state=ms, masks_output=mo, targets=targets,
+              sample_weights=weights, loss='mean_squared_error', mean=False, graph_based=False)
+    res = tro.train_step(g, st, ou, **kw)
+    assert res['k'] == 3
+    eps = 1e-6
+    for net, grads in ((st, res['grads_state']), (ou, res['grads_output'])):
+        for wi in range(len(grads)):
+            w = net['weights'][wi] = np.asarray(net['weights'][wi], np.float64)
+            for _ in range(3):
+                idx = tuple(rng.integers(0, s) for s in w.shape)
+                old = w[idx]
+                w[idx] = old + eps; lp = tro.train_step(g, st, ou, **kw)['loss']
+                w[idx] = old - eps; lm = tro.train_step(g, st, ou, **kw)['loss']
+                w[idx] = old
+                fd = (lp - lm) / (2 * eps)
+                assert abs(fd - grads[wi][idx]) <= 1e-5 * max(1.0, abs(fd)), (wi, idx, fd, grads[wi][idx])
+
+
 def test_training_forward_semantics():
     rng = np.random.default_rng(0)
     g, st, ou, s0, ms, mo, targets, weights = _case(rng, 4)
