@@ -95,6 +95,7 @@ __device__ __forceinline__ float gnn_act(float v, int act)
 #define GNN_FLAG_STRIDE 32
 #define GNN_FLAG_WORDS (GNN_FLAG_SLOTS * GNN_FLAG_STRIDE)   // ints per (iteration, rank)
 #define GNN_BODY_CHUNK 16
+#define GNN_BODY_LOOKAHEAD 4      // bodies queued behind a gate's copy before the host waits for it (gnn_loop.hip, run_loops_once)
 
 __device__ __forceinline__ bool gnn_gate_open(const int *gate, int world)
 {
@@ -313,7 +314,8 @@ struct gnn_loop {
     int64_t shard_rows = 0, N_pad = 0, own_off = 0;   // rows per rank, rows of the state replica, replica row of the first owned row
     hipStream_t stream = nullptr;
     float *state[2] = {nullptr, nullptr};   // [N_pad, Ds] full replicas, ping-pong
-    float *state_init = nullptr;            // [n_rows, Ds] initial state of the owned rows (D > 0)
+    float *state_init = nullptr;            // initial state of the owned rows (D > 0): [N_pad, Ds] with a zeroed tail on one GPU, [n_rows, Ds] on a shard
+    bool init_in_place = false;             // the last run read its initial state from state_init itself, state[0] holds no copy (gnn_engine.h, gnn_state_after)
     float *inp = nullptr;                   // unfused: materialised concat [n_rows, in_s]
     float *inv = nullptr;                   // fused: loop-invariant label block [n_rows, inv_w]
     uint64_t inv_version = 0;               // label_version of the graph the block was built from
@@ -361,6 +363,7 @@ struct gnn_loop {
     // destination half of the readout features, 1: its source half.  Lets the backward pass GATHER per node in a fixed order (no atomics).
     int32_t *edge_inc_ptr = nullptr, *edge_inc = nullptr;
     int *gate_host = nullptr;               // pinned copy of one gate (early-exit check every GNN_BODY_CHUNK bodies)
+    hipEvent_t ev_gate = nullptr;           // ... and the event behind the copy
     bool profiling = false;
     std::vector<hipEvent_t> ev;
     hipEvent_t ev_total[2] = {nullptr, nullptr};

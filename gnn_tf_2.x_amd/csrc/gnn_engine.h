@@ -33,8 +33,23 @@ static inline int zero_on_stream(void *p, size_t bytes, hipStream_t st)
     return GNN_OK;
 }
 
+// "The state after k bodies" of a loop's last run, for every reader (host and device).  Bodies ping-pong between state[0] and state[1]:
+// body k writes state[(k + 1) & 1], so k >= 1 bodies leave the state in state[k & 1].  k == 0 is the initial state: a per-body run on one
+// GPU with D > 0 reads it where gnn_loop_set_state0 put it (l->init_in_place: state_init is then a full table of N_pad rows with a
+// zeroed tail, never written by a run); every other run - sharded, D == 0, persistent, training - has copied it into state[0].
+struct GnnStateTabs { const float *init, *s0, *s1; };
+__host__ __device__ __forceinline__ const float *gnn_state_after(const GnnStateTabs &t, int k) { return k == 0 ? t.init : ((k & 1) ? t.s1 : t.s0); }
+// the three tables from replica row `row_off` on (l->own_off: the owned rows; 0: the replica)
+static inline GnnStateTabs gnn_loop_state_tabs(const gnn_loop *l, size_t row_off)
+{
+    const size_t o = row_off * (size_t)l->Ds;
+    return GnnStateTabs{(l->init_in_place ? l->state_init : l->state[0]) + o, l->state[0] + o, l->state[1] + o};
+}
+static inline const float *gnn_loop_state_after(const gnn_loop *l, int k, size_t row_off) { return gnn_state_after(gnn_loop_state_tabs(l, row_off), k); }
+
 // gnn_engine.hip
 GNN_INTERNAL int launch_check(hipStream_t st, int64_t n_rows, int d, const float *s, const float *so, float thr, int *flag_out, const int *gate, int world);
+GNN_INTERNAL int launch_check_first(hipStream_t st, int64_t n_rows, int d, const float *s, float thr, int *flag_out);
 GNN_INTERNAL int launch_mlp(hipStream_t st, const gnn_mlp *m, int64_t n, const float *X, int64_t ldx, float *Y, int64_t ldy, float *t0, float *t1,
                             const int *gate, int world);
 

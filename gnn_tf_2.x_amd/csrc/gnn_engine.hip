@@ -329,6 +329,74 @@ __global__ void __launch_bounds__(256) k_check(int64_t n_rows, int d, const floa
     if (__any(f) && (threadIdx.x & 63) == 0) gnn_flag_raise(flag_out);
 }
 
+// The first condition of a Loop (state vs ones, GNN.py:266, :271) as one streamed pass: k_check's sums, rows and flag word, another
+// staging.  A one-wave block takes 64 consecutive rows, i.e. one contiguous 256 d bytes of the table, reads them in 16-byte pieces (all of
+// a lane's pieces in flight at once, no barrier between chunks of features) and stores them to LDS in 16-byte pieces; lane r then runs
+// row r's sums alone, in ascending feature order.  ld: row stride of the tile - d itself (the tile is then the flat image of the rows) or,
+// where d / 4 is even, d + 4, which spreads the 16-byte row reads of 16 lanes over all banks.
+#define GNN_CHECK1_MAX_D 124      // 64 rows of at most 128 floats: 32 KB of LDS per wave
+__global__ void __launch_bounds__(64) k_check_first(int64_t n_rows, int d, int ld, const float *__restrict__ s, float thr, int *flag_out)
+{
+    extern __shared__ float chk1_sh[];                     // [64, ld]
+    const int lane = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * 64;
+    const int rows = n_rows - r0 < 64 ? (int)(n_rows - r0) : 64;
+    const float *src = s + r0 * d;                         // 16-byte aligned: s is (launch_check_first), and 64 rows are a multiple of 16 bytes
+    const int n = rows * d, np = n >> 2;
+    if (ld == d) {
+#pragma unroll 8
+        for (int p = lane; p < np; p += 64) {
+            const float4 v = reinterpret_cast<const float4 *>(src)[p];
+            reinterpret_cast<float4 *>(chk1_sh)[p] = v;
+        }
+        for (int t = 4 * np + lane; t < n; t += 64) chk1_sh[t] = src[t];
+    } else {                                               // (d is a multiple of 4 here)
+        const int q = d >> 2, dr = 64 / q, dc = 64 - dr * q;
+        int r = lane / q, c = lane - r * q;
+#pragma unroll 8
+        for (int p = lane; p < np; p += 64) {
+            const float4 v = reinterpret_cast<const float4 *>(src)[p];
+            *reinterpret_cast<float4 *>(chk1_sh + r * ld + 4 * c) = v;
+            r += dr; c += dc;
+            if (c >= q) { c -= q; ++r; }
+        }
+    }
+    __syncthreads();
+    float dist = 0.0f, nrm = 0.0f;
+    int f = 0;
+    if (lane < rows) {
+        const float *x = chk1_sh + lane * ld;
+        const float o = 1.0f;
+        if ((d & 3) == 0) {
+            for (int c = 0; c < d; c += 4) {
+                const float4 v = *reinterpret_cast<const float4 *>(x + c);
+                const float xs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float df = xs[u] - o;
+                    const float dd = df * df;
+                    dist = dist + dd;
+                    const float oo = o * o;
+                    nrm = nrm + oo;
+                }
+            }
+        } else {
+            for (int c = 0; c < d; ++c) {
+                const float df = x[c] - o;
+                const float dd = df * df;
+                dist = dist + dd;
+                const float oo = o * o;
+                nrm = nrm + oo;
+            }
+        }
+        const float lhs = sqrtf(dist);
+        const float rn = sqrtf(nrm);
+        const float rhs = thr * rn;
+        f = lhs > rhs;
+    }
+    if (__any(f) && lane == 0) gnn_flag_raise(flag_out);
+}
+
 // dst[r, 0:w) = src[r, 0:w) for r < n_rows (strided rows on both sides).  Own kernel instead of hipMemcpy2DAsync: the
 // runtime's 2-D device-to-device copy was the only HIP call of the per-op path that the fused path never makes, and a
 // profiled run (rocprofv3 --kernel-trace) of the per-op path died inside the runtime on its first use.
@@ -402,6 +470,17 @@ int launch_check(hipStream_t st, int64_t n_rows, int d, const float *s, const fl
     static bool lds_raised[64] = {false};      // two staged tiles are 66 KB of dynamic LDS
     HIPCHK(gnn_raise_dynamic_lds(reinterpret_cast<const void *>(k_check), 2 * 256 * 33 * 4, lds_raised));
     hipLaunchKernelGGL(k_check, cdiv(n_rows, 256), 256, sizeof(float) * 256 * 33 * (so ? 2 : 1), st, n_rows, d, s, so, thr, flag_out, gate, world);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
+// the first condition of an inference Loop (against ones): the streamed form where a wave's 64 rows fit its LDS tile, k_check otherwise
+int launch_check_first(hipStream_t st, int64_t n_rows, int d, const float *s, float thr, int *flag_out)
+{
+    if (n_rows == 0) return GNN_OK;
+    if (d > GNN_CHECK1_MAX_D || ((uintptr_t)s & 15) != 0) return launch_check(st, n_rows, d, s, nullptr, thr, flag_out, nullptr, 1);
+    const int ld = ((d & 3) == 0 && ((d >> 2) & 1) == 0) ? d + 4 : d;
+    hipLaunchKernelGGL(k_check_first, cdiv(n_rows, 64), 64, sizeof(float) * 64 * ld, st, n_rows, d, ld, s, thr, flag_out);
     HIPCHK(hipGetLastError());
     return GNN_OK;
 }

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <vector>
 
-#include "gnn_common.h"
+#include "gnn_engine.h"
 #include "gnn_fused.h"
 
 namespace {
@@ -433,7 +433,7 @@ static void fill_args(const gnn_loop *l, const FusedPlan &p, bool split, GnnFuse
 static void body_args(const gnn_loop *l, int k, GnnFusedArgs &a)
 {
     const int cur = k & 1, P = l->world;
-    a.state_cur = l->state[cur];
+    a.state_cur = gnn_loop_state_after(l, k, 0);         // (body 0 of a one-GPU run gathers from state_init itself)
     a.state_nxt = l->state[cur ^ 1] + (size_t)l->own_off * l->Ds;
     a.gate = l->flags + (size_t)k * P * GNN_FLAG_WORDS;
     a.flag_out = l->flags + ((size_t)(k + 1) * P + l->rank) * GNN_FLAG_WORDS;

@@ -58,8 +58,8 @@ int gnn_graph_wait_ready(const gnn_graph *g, hipStream_t st)
 // kernels of the label relabelling
 // ---------------------------------------------------------------------------------------------------------------------
 // LGNN.update_graph: dst[i] = [base[i, :NLb] | state[i] (if get_state) | mask[i] ? out[pos(i)] : 0 (if get_output)]
-__global__ void k_relabel(int64_t N, int NLb, const float *__restrict__ base_nodes, int Ds, const float *s0,
-                          const float *s1, const int *kfinal, int get_state, int T, const float *__restrict__ out,
+__global__ void k_relabel(int64_t N, int NLb, const float *__restrict__ base_nodes, int Ds, GnnStateTabs tabs,
+                          const int *kfinal, int get_state, int T, const float *__restrict__ out,
                           const uint8_t *__restrict__ mask, const int32_t *__restrict__ mask_pos, int get_output,
                           float *__restrict__ dst, int NLd)
 {
@@ -73,7 +73,7 @@ __global__ void k_relabel(int64_t N, int NLb, const float *__restrict__ base_nod
     } else {
         c -= NLb;
         if (get_state && c < Ds) {
-            const float *state = ((*kfinal) & 1) ? s1 : s0;
+            const float *state = gnn_state_after(tabs, *kfinal);
             v = state[i * Ds + c];
         } else {
             if (get_state) c -= Ds;
@@ -389,7 +389,7 @@ static int relabel_own(gnn_graph *dst, const gnn_graph *base, const gnn_loop *fr
     if (rcw) return rcw;
     if (tot)
         hipLaunchKernelGGL(k_relabel, cdiv(tot, 256), 256, 0, from->stream, rows, base->NL, base->nodes + (size_t)off * base->NL, from->Ds,
-                           from->state[0] + (size_t)from->own_off * from->Ds, from->state[1] + (size_t)from->own_off * from->Ds, from->kfinal_dev, get_state, from->T,
+                           gnn_loop_state_tabs(from, (size_t)from->own_off), from->kfinal_dev, get_state, from->T,
                            from->out, base->sh->mask, graph_mask_pos(base), out_nodes ? 1 : 0, dst->nodes + (size_t)off * dst->NL, dst->NL);
     if (arc_side) {
         ARGCHK(dst->arc_labels_own && dst->arc_labels_orig_own && base->sh->arc_id, "dst must come from gnn_graph_derive_edge");

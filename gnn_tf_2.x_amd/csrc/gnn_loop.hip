@@ -23,7 +23,7 @@ __global__ void k_finalize(const int *flags, int world, int max_iter, int *kfina
         const unsigned long long m = __ballot(closed);
         if (m) { k_final = k0 + __builtin_ctzll(m); break; }
     }
-    if (lane == 0) *kfinal = k_final;
+    if (lane == 0) { kfinal[0] = k_final; kfinal[1] = 0; }      // (word 1: status of the persistent loop, which never comes here)
     // certified gate of the split-arithmetic path (gnn_common.h, gnn_flag_raise_certified): gates 1 .. k_final that decided this run (the
     // gate of body max_iter is never consulted; gate 0 is the first condition, the same arithmetic on every path).  Not certified: no node
     // moved robustly AND some node was borderline.  The exact paths never raise words 1 / 2, so this stays 0 for them.
@@ -50,14 +50,14 @@ __global__ void k_finalize(const int *flags, int world, int max_iter, int *kfina
 }
 
 // apply_filters(): feats[m] = [state_final[row_m] | nodes[row_m] (iff D > 0)]
-__global__ void k_feats(int64_t n_masked, const int32_t *__restrict__ masked_rows, const float *s0, const float *s1,
+__global__ void k_feats(int64_t n_masked, const int32_t *__restrict__ masked_rows, GnnStateTabs tabs,
                         const int *kfinal, int Ds, const float *__restrict__ nodes_own, int NL, int NLc,
                         float *__restrict__ feats)
 {
     const int wf = Ds + NLc;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_masked * wf) return;
-    const float *state = ((*kfinal) & 1) ? s1 : s0;
+    const float *state = gnn_state_after(tabs, *kfinal);
     const int64_t m = t / wf;
     const int c = (int)(t - m * wf);
     const int64_t row = masked_rows[m];
@@ -66,14 +66,14 @@ __global__ void k_feats(int64_t n_masked, const int32_t *__restrict__ masked_row
 
 // GNNedgeBased.apply_filters(): feats[m] = [F[dst(e)] | F[src(e)] | arc_labels[e]], e = m-th masked arc, F = [state | nodes?]
 __global__ void k_feats_edge(int64_t n_masked, const int32_t *__restrict__ rows, const int32_t *__restrict__ entry_dst,
-                             const int32_t *__restrict__ adj_src, const float *s0, const float *s1, const int *kfinal, int Ds,
+                             const int32_t *__restrict__ adj_src, GnnStateTabs tabs, const int *kfinal, int Ds,
                              const float *__restrict__ nodes, int NL, int NLc, const float *__restrict__ arc_labels, int AL,
                              float *__restrict__ feats, int64_t own_off)
 {
     const int wn = Ds + NLc, wf = 2 * wn + AL;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_masked * wf) return;
-    const float *state = ((*kfinal) & 1) ? s1 : s0;
+    const float *state = gnn_state_after(tabs, *kfinal);
     const int64_t m = t / wf;
     int c = (int)(t - m * wf);
     const int64_t e = rows[m];
@@ -89,69 +89,96 @@ __global__ void k_feats_edge(int64_t n_masked, const int32_t *__restrict__ rows,
 }
 
 // apply_filters + a ONE-layer net_output with few outputs (the usual classifier head, T <= 8) in one pass over the masked
-// rows.  A block stages 64 feature rows [state | labels] through LDS with coalesced reads, then thread (row, j) runs the
-// k-ordered fmaf chain of output j (same order as k_dense); softmax / activation / BatchNormalization as k_softmax_bn.
-// Saves materialising [M, NL + D] features and two more launches.
+// rows.  A one-wave block stages 64 feature rows [state | labels] into its LDS tile: 16-byte pieces of the rows, a lane's pieces all in
+// flight at once, 16-byte LDS stores where widths and strides allow.  Lane r then runs row r alone: the k-ordered fmaf chain of every
+// output j (same order as k_dense; the weights are wave-uniform reads), softmax / activation / BatchNormalization as k_softmax_bn.
+// Saves materialising [M, NL + D] features and two more launches.  ld: row stride of the tile, a multiple of 4 with ld / 4 odd, so that
+// the 16-byte row reads of 16 lanes fall on all banks.
 #define GNN_OUT1_ROWS 64
-__global__ void k_out1(int64_t n_masked, const int32_t *__restrict__ masked_rows, const float *s0, const float *s1,
-                       const int *kfinal, int Ds, const float *__restrict__ nodes_own, int NL, int NLc,
-                       const float *__restrict__ W, const float *__restrict__ b, int T, int act,
+static inline int out1_ld(int wf) { const int ld = (wf + 3) & ~3; return ((ld >> 2) & 1) ? ld : ld + 4; }
+
+// columns [col0, col0 + w) of the tile <- src[rows[r] * stride + 0 .. w) for r < live
+__device__ __forceinline__ void out1_stage(const float *__restrict__ src, int stride, int w, int col0, const int *rows, int live, float *tile, int ld, int lane)
+{
+    if (w == 0) return;
+    if (((w | stride | col0) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+        const int q = w >> 2, dr = GNN_OUT1_ROWS / q, dc = GNN_OUT1_ROWS - dr * q, n = live * q;
+        int r = lane / q, c = lane - r * q;
+#pragma unroll 8
+        for (int idx = lane; idx < n; idx += GNN_OUT1_ROWS) {
+            const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)rows[r] * stride + 4 * c);
+            *reinterpret_cast<float4 *>(tile + r * ld + col0 + 4 * c) = v;
+            r += dr; c += dc;
+            if (c >= q) { c -= q; ++r; }
+        }
+    } else {
+        const int dr = GNN_OUT1_ROWS / w, dc = GNN_OUT1_ROWS - dr * w, n = live * w;
+        int r = lane / w, c = lane - r * w;
+#pragma unroll 8
+        for (int idx = lane; idx < n; idx += GNN_OUT1_ROWS) {
+            tile[r * ld + col0 + c] = src[(int64_t)rows[r] * stride + c];
+            r += dr; c += dc;
+            if (c >= w) { c -= w; ++r; }
+        }
+    }
+}
+
+template <int T>
+__global__ void __launch_bounds__(GNN_OUT1_ROWS) k_out1(int64_t n_masked, const int32_t *__restrict__ masked_rows, GnnStateTabs tabs,
+                       const int *kfinal, int Ds, const float *__restrict__ nodes_own, int NL, int NLc, int ld,
+                       const float *__restrict__ W, const float *__restrict__ b, int act,
                        const float *__restrict__ bn_scale, const float *__restrict__ bn_shift, float *__restrict__ out)
 {
     extern __shared__ float osh[];
-    const int wf = Ds + NLc, ldw = wf | 1;
-    float *wsh = osh;                                      // W [wf, T] then b [T]
-    float *tile = wsh + (wf + 1) * T;                      // [64, ldw]
-    float *vsh = tile + GNN_OUT1_ROWS * ldw;               // [64, T]
-    const int nthr = blockDim.x, tid = threadIdx.x;
-    const float *state = ((*kfinal) & 1) ? s1 : s0;
-    const int64_t base = (int64_t)blockIdx.x * GNN_OUT1_ROWS;
-    for (int t = tid; t < (wf + 1) * T; t += nthr) wsh[t] = t < wf * T ? W[t] : b[t - wf * T];
-    if ((Ds & 3) == 0) {                                   // 16-byte pieces of the state rows, many rows in flight per thread
-        const int q = Ds >> 2;
-#pragma unroll 4
-        for (int idx = tid; idx < GNN_OUT1_ROWS * q; idx += nthr) {
-            const int r = idx / q, c = (idx - r * q) * 4;
-            if (base + r < n_masked) {
-                const float4 v = *reinterpret_cast<const float4 *>(state + (int64_t)masked_rows[base + r] * Ds + c);
-                float *t = tile + r * ldw + c;
-                t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-            }
-        }
-    } else {
-        for (int idx = tid; idx < GNN_OUT1_ROWS * Ds; idx += nthr) {
-            const int r = idx / Ds, c = idx - r * Ds;
-            if (base + r < n_masked) tile[r * ldw + c] = state[(int64_t)masked_rows[base + r] * Ds + c];
-        }
-    }
-    for (int idx = tid; idx < GNN_OUT1_ROWS * NLc; idx += nthr) {
-        const int r = idx / NLc, c = idx - r * NLc;
-        if (base + r < n_masked) tile[r * ldw + Ds + c] = nodes_own[(int64_t)masked_rows[base + r] * NL + c];
-    }
+    float *tile = osh;                                     // [64, ld]
+    int *rows = reinterpret_cast<int *>(osh + GNN_OUT1_ROWS * ld);      // [64] table rows of the block's masked rows
+    const int lane = threadIdx.x, wf = Ds + NLc;
+    const float *state = gnn_state_after(tabs, *kfinal);
+    const int64_t base = (int64_t)blockIdx.x * GNN_OUT1_ROWS, m = base + lane;
+    const int live = n_masked - base < GNN_OUT1_ROWS ? (int)(n_masked - base) : GNN_OUT1_ROWS;
+    rows[lane] = lane < live ? masked_rows[m] : 0;
     __syncthreads();
-    const int r = tid / T, j = tid - r * T;
-    const int64_t m = base + r;
-    const bool live = r < GNN_OUT1_ROWS && m < n_masked;
-    if (live) {
-        float acc = 0.0f;
-        const float *x = tile + r * ldw;
-        for (int k = 0; k < wf; ++k) acc = __builtin_fmaf(x[k], wsh[k * T + j], acc);
-        vsh[r * T + j] = acc + wsh[wf * T + j];
-    }
+    out1_stage(state, Ds, Ds, 0, rows, live, tile, ld, lane);
+    out1_stage(nodes_own, NL, NLc, Ds, rows, live, tile, ld, lane);
     __syncthreads();
-    if (!live) return;
-    const float *y = vsh + r * T;
-    float v;
+    if (lane >= live) return;
+    float y[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) y[j] = 0.0f;
+    const float *x = tile + lane * ld;
+    int k = 0;
+    for (; k + 4 <= wf; k += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(x + k);
+        const float xs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int j = 0; j < T; ++j) y[j] = __builtin_fmaf(xs[u], W[(k + u) * T + j], y[j]);
+    }
+    for (; k < wf; ++k)
+#pragma unroll
+        for (int j = 0; j < T; ++j) y[j] = __builtin_fmaf(x[k], W[k * T + j], y[j]);
+#pragma unroll
+    for (int j = 0; j < T; ++j) y[j] = y[j] + b[j];
     if (act == GNN_ACT_SOFTMAX) {
         float mx = y[0];
+#pragma unroll
         for (int q = 1; q < T; ++q) mx = y[q] > mx ? y[q] : mx;
-        float sum = 0.0f, mine = 0.0f;
-        for (int q = 0; q < T; ++q) { const float e = gnn_expf(y[q] - mx); sum = sum + e; if (q == j) mine = e; }
-        v = __fdiv_rn(mine, sum);
-    } else
-        v = gnn_act(y[j], act);
-    if (bn_scale) { const float t2 = v * bn_scale[j]; v = t2 + bn_shift[j]; }
-    out[m * T + j] = v;
+        float sum = 0.0f;
+#pragma unroll
+        for (int q = 0; q < T; ++q) { y[q] = gnn_expf(y[q] - mx); sum = sum + y[q]; }
+#pragma unroll
+        for (int j = 0; j < T; ++j) y[j] = __fdiv_rn(y[j], sum);
+    } else {
+#pragma unroll
+        for (int j = 0; j < T; ++j) y[j] = gnn_act(y[j], act);
+    }
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        float v = y[j];
+        if (bn_scale) { const float t2 = v * bn_scale[j]; v = t2 + bn_shift[j]; }
+        out[m * T + j] = v;
+    }
 }
 
 // graph readout: out_graph[g, t] = sum over the stored (node, w) of graph g, ascending node, fmaf(w, out_nodes[node, t])
@@ -205,7 +232,7 @@ int gnn_launch_feats_edge(hipStream_t st, const gnn_loop *l, const float *state,
     if (!l->n_edge_masked) return GNN_OK;
     const gnn_graph *g = l->g;
     const int64_t tot = l->n_edge_masked * l->ou->dims[0];
-    hipLaunchKernelGGL(k_feats_edge, cdiv(tot, 256), 256, 0, st, l->n_edge_masked, l->edge_rows, l->edge_dst, g->sh->adj_src, state, state,
+    hipLaunchKernelGGL(k_feats_edge, cdiv(tot, 256), 256, 0, st, l->n_edge_masked, l->edge_rows, l->edge_dst, g->sh->adj_src, GnnStateTabs{state, state, state},
                        l->kfinal_dev, l->Ds, g->nodes, g->NL, l->NLc, g->arc_labels_orig_own ? g->arc_labels_orig_own : l->edge_labels, g->AL, feats, l->own_off);
     HIPCHK(hipGetLastError());
     return GNN_OK;
@@ -214,6 +241,9 @@ int gnn_launch_feats_edge(hipStream_t st, const gnn_loop *l, const float *state,
 // ---------------------------------------------------------------------------------------------------------------------
 // loop
 // ---------------------------------------------------------------------------------------------------------------------
+static size_t loop_flag_words(const gnn_loop *l) { return (size_t)(l->max_iter + 2) * l->world * GNN_FLAG_WORDS; }
+static size_t loop_ctr_words(const gnn_loop *l) { return (2 * ((size_t)l->max_iter + 1) + 3) & ~(size_t)3; }
+
 extern "C" int gnn_loop_create(gnn_graph *g, gnn_mlp *net_state, gnn_mlp *net_output, int state_dim, int max_iter,
                                float threshold, gnn_comm *comm, gnn_loop **out)
 {
@@ -264,9 +294,11 @@ extern "C" int gnn_loop_create(gnn_graph *g, gnn_mlp *net_state, gnn_mlp *net_ou
         rc = dev_alloc(&l->state[b], (size_t)l->N_pad * Ds);
         if (!rc) rc = zero_on_stream(l->state[b], sizeof(float) * (size_t)l->N_pad * Ds, l->stream);      // ordered before everything this loop ever queues
     }
-    if (!rc) rc = dev_alloc(&l->flags, (size_t)(max_iter + 2) * world * GNN_FLAG_WORDS + 4);   // + barrier counter / status of the persistent loop
+    // gate words, then one ticket counter per body (the second half is spare: a partial last tile used to get a launch of its own) in the
+    // same block, so that loop_begin clears both with one fill; + barrier counter / status of the persistent loop
+    if (!rc) rc = dev_alloc(&l->flags, loop_flag_words(l) + loop_ctr_words(l) + 4);
+    if (!rc) l->tile_ctr = l->flags + loop_flag_words(l);
     if (!rc) rc = dev_alloc(&l->kfinal_dev, 4);        // k, status word of the persistent loop, "gate not certified", pad
-    if (!rc) rc = dev_alloc(&l->tile_ctr, (2 * ((size_t)max_iter + 1) + 3) & ~(size_t)3);      // one ticket counter per body (the second half is spare: a partial last tile used to get a launch of its own)
     if (!rc && hipHostMalloc((void **)&l->kfinal_host, 4 * sizeof(int)) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipHostMalloc");
     if (!rc) l->kfinal_host[1] = l->kfinal_host[2] = l->kfinal_host[3] = 0;
     if (!rc && hipHostMalloc((void **)&l->gate_host, sizeof(int) * (size_t)world * GNN_FLAG_WORDS) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipHostMalloc");
@@ -275,6 +307,7 @@ extern "C" int gnn_loop_create(gnn_graph *g, gnn_mlp *net_state, gnn_mlp *net_ou
         if (!rc) rc = dev_alloc(&l->out, (size_t)g->n_masked * l->T);
         for (int b = 0; b < 2 && !rc; ++b) rc = dev_alloc(&l->otmp[b], (size_t)g->n_masked * maxw_o);
     }
+    if (!rc && hipEventCreateWithFlags(&l->ev_gate, hipEventDisableTiming) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipEventCreate");
     if (!rc && hipEventCreate(&l->ev_total[0]) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipEventCreate");
     if (!rc && hipEventCreate(&l->ev_total[1]) != hipSuccess) rc = gnn_fail(GNN_ERR_HIP, "hipEventCreate");
     if (rc) { gnn_loop_destroy(l); return rc; }
@@ -414,7 +447,13 @@ extern "C" int gnn_loop_set_state0(gnn_loop *l, const float *state0, uint64_t se
     HIPCHK(hipSetDevice(l->device));
     const gnn_graph *g = l->g;
     const size_t cnt = (size_t)g->n_rows * l->Ds;
-    if (!l->state_init && l->D) { int rc = dev_alloc(&l->state_init, cnt); if (rc) return rc; }
+    if (!l->state_init && l->D) {
+        // One GPU: a drop-in table for body 0's gather (loop_begin) - the replica's padded row count, the tail zeroed once and never written again.
+        const size_t rows = l->world == 1 ? (size_t)std::max<int64_t>(l->N_pad, g->n_rows) : (size_t)g->n_rows;
+        int rc = dev_alloc(&l->state_init, rows * l->Ds);
+        if (!rc && rows > (size_t)g->n_rows) rc = zero_on_stream(l->state_init + cnt, sizeof(float) * (rows - (size_t)g->n_rows) * l->Ds, l->stream);
+        if (rc) return rc;
+    }
     float *own = l->state_init;
     if (l->D == 0) {   // state <- node labels (GNN.py:265); taken from the graph at run time
         l->have_state0 = true;
@@ -462,14 +501,14 @@ static int unfused_iteration(gnn_loop *l, int k)
     const gnn_graph *g = l->g;
     const int cur = k & 1, nxt = cur ^ 1, P = l->world;
     const int *gate = l->flags + (size_t)k * P * GNN_FLAG_WORDS;
-    const float *own_cur = l->state[cur] + (size_t)l->own_off * l->Ds;
+    const float *rep_cur = gnn_loop_state_after(l, k, 0), *own_cur = rep_cur + (size_t)l->own_off * l->Ds;
     float *own_nxt = l->state[nxt] + (size_t)l->own_off * l->Ds;
     // node_components (GNN.py:228): own state into columns [0, Ds) of the concat
     int rc = gnn_launch_copy_cols(l->stream, g->n_rows, l->Ds, own_cur, l->Ds, l->inp, l->in_s, gate, P);
     if (rc) return rc;
     // aggregated_states (GNN.py:234) into columns [Ds + NLc, +Ds)
     if (l->slice_mode) rc = gnn_launch_copy_cols(l->stream, g->n_rows, l->Ds, l->agg_own, l->Ds, l->inp + l->Ds + l->NLc, l->in_s, gate, P);
-    else rc = gnn_launch_spmm(l->stream, g->n_rows, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, l->state[cur], l->Ds, l->Ds,
+    else rc = gnn_launch_spmm(l->stream, g->n_rows, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, rep_cur, l->Ds, l->Ds,
                               l->inp + l->Ds + l->NLc, l->in_s, gate, P);
     if (rc) return rc;
     // net_state (GNN.py:240)
@@ -487,15 +526,17 @@ static int loop_begin(gnn_loop *l)
     const int P = l->world;
     hipStream_t st = l->stream;
     int rc = 0;
-    HIPCHK(hipMemsetAsync(l->flags, 0, sizeof(int) * (size_t)(l->max_iter + 2) * P * GNN_FLAG_WORDS, st));
+    HIPCHK(hipMemsetAsync(l->flags, 0, sizeof(int) * (loop_flag_words(l) + loop_ctr_words(l)), st));      // gate words and tile counters, one fill
     l->small_words_clean = false;       // the persistent loop's gate words share this block
-    HIPCHK(hipMemsetAsync(l->tile_ctr, 0, sizeof(int) * ((2 * ((size_t)l->max_iter + 1) + 3) & ~(size_t)3), st));
+    // One GPU, D > 0: body 0 gathers from state_init itself (a table of N_pad rows, gnn_loop_set_state0) and writes state[1]; no run writes
+    // state_init.  Shards exchange rows inside state[0], and with D == 0 the initial state is the unpadded label table: those keep the copy.
+    l->init_in_place = P == 1 && !l->comm && l->D > 0 && !l->slice_mode && !g->halo_world && l->own_off == 0;
     float *own0 = l->state[0] + (size_t)l->own_off * l->Ds;
-    if (g->n_rows)   // state <- nodes (GNN.py:265) or the injected / drawn initial state (GNN.py:262)
+    if (g->n_rows && !l->init_in_place)   // state <- nodes (GNN.py:265) or the injected / drawn initial state (GNN.py:262)
         HIPCHK(hipMemcpyAsync(own0, l->D ? l->state_init : g->nodes + (size_t)g->own_off * g->NL,
                               sizeof(float) * (size_t)g->n_rows * l->Ds, hipMemcpyDeviceToDevice, st));
     // first condition: state vs ones (GNN.py:266, :271)
-    if ((rc = launch_check(st, g->n_rows, l->Ds, own0, nullptr, l->thr, l->flags + (size_t)l->rank * GNN_FLAG_WORDS, nullptr, 1))) return rc;
+    if ((rc = launch_check_first(st, g->n_rows, l->Ds, gnn_loop_state_after(l, 0, (size_t)l->own_off), l->thr, l->flags + (size_t)l->rank * GNN_FLAG_WORDS))) return rc;
     if (l->form.path == GNN_PATH_UNFUSED) {
         const int c_nodes = l->Ds, c_aggn = l->Ds + l->NLc + l->Ds, c_agga = c_aggn + l->NLc;
         rc = gnn_launch_spmm(st, g->n_rows, g->sh->indptr, nullptr, g->sh->arc_w, gnn_graph_arc_labels(g), g->AL, g->AL, l->inp + c_agga, l->in_s, nullptr, 1);
@@ -519,12 +560,20 @@ static int loop_body(gnn_loop *l, int k)
     return GNN_OK;
 }
 
-// gate of body k -> host; every rank reads the same exchanged gate, so all ranks stop at the same body
-static int loop_gate_closed(gnn_loop *l, int k, bool *closed)
+// gate of body k -> host, in two steps, so that further bodies can be queued behind the copy before the host waits for it; every rank
+// reads the same exchanged gate, so all ranks stop at the same body
+static int loop_gate_fetch(gnn_loop *l, int k)
 {
     const size_t words = (size_t)l->world * GNN_FLAG_WORDS;
     HIPCHK(hipMemcpyAsync(l->gate_host, l->flags + (size_t)k * words, sizeof(int) * words, hipMemcpyDeviceToHost, l->stream));
-    HIPCHK(hipStreamSynchronize(l->stream));
+    HIPCHK(hipEventRecord(l->ev_gate, l->stream));
+    return GNN_OK;
+}
+
+static int loop_gate_closed(gnn_loop *l, bool *closed)
+{
+    const size_t words = (size_t)l->world * GNN_FLAG_WORDS;
+    HIPCHK(hipEventSynchronize(l->ev_gate));
     int any = 0;
     for (size_t i = 0; i < words; i += GNN_FLAG_STRIDE) any |= l->gate_host[i];
     *closed = !any;
@@ -541,35 +590,45 @@ static int loop_finish(gnn_loop *l)
     if (!persistent) {     // (the persistent small-graph loop has written k itself)
         hipLaunchKernelGGL(k_finalize, 1, 64, 0, st, l->flags, l->world, l->max_iter, l->kfinal_dev);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(l->kfinal_host, l->kfinal_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(l->kfinal_host + 2, l->kfinal_dev + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, st));      // "a gate was not certified", "out of fp16 range"
+        HIPCHK(hipMemcpyAsync(l->kfinal_host, l->kfinal_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, st));      // k, 0, "a gate was not certified", "out of fp16 range"
     }
     if (output_done) return GNN_OK;     // (the persistent loop wrote k into the pinned host words and ran the output stage itself)
-    const float *own0 = l->state[0] + (size_t)l->own_off * l->Ds, *own1 = l->state[1] + (size_t)l->own_off * l->Ds;
+    const GnnStateTabs own = gnn_loop_state_tabs(l, (size_t)l->own_off);
     const float *nodes_own = g->nodes + (size_t)g->own_off * g->NL;
 
     if (l->edge_mode) {      // GNNedgeBased.apply_filters + net_output on the masked arcs (GNN.py:289-302, :279)
         if (l->n_edge_masked) {
             const int we = l->ou->dims[0];
             const int64_t tot = l->n_edge_masked * we;
-            hipLaunchKernelGGL(k_feats_edge, cdiv(tot, 256), 256, 0, st, l->n_edge_masked, l->edge_rows, l->edge_dst, g->sh->adj_src, l->state[0],
-                               l->state[1], l->kfinal_dev, l->Ds, g->nodes, g->NL, l->NLc, g->arc_labels_orig_own ? g->arc_labels_orig_own : l->edge_labels, g->AL, l->feats, l->own_off);
+            hipLaunchKernelGGL(k_feats_edge, cdiv(tot, 256), 256, 0, st, l->n_edge_masked, l->edge_rows, l->edge_dst, g->sh->adj_src, gnn_loop_state_tabs(l, 0),
+                               l->kfinal_dev, l->Ds, g->nodes, g->NL, l->NLc, g->arc_labels_orig_own ? g->arc_labels_orig_own : l->edge_labels, g->AL, l->feats, l->own_off);
             HIPCHK(hipGetLastError());
             rc = launch_mlp(st, l->ou, l->n_edge_masked, l->feats, we, l->out, l->T, l->otmp[0], l->otmp[1], nullptr, 1);
             if (rc) return rc;
         }
         return GNN_OK;
     }
-    const size_t out1_lds = sizeof(float) * ((size_t)(l->wf + 1) * l->T + (size_t)GNN_OUT1_ROWS * (l->wf | 1) + (size_t)GNN_OUT1_ROWS * l->T);
-    if (g->n_masked && l->ou->n_layers == 1 && l->T <= 8 && out1_lds <= 64 * 1024) {
+    // (the conditions of the fused output stage are those of its first form, whose block also held W and the outputs in LDS; the tile of this one is never larger than 64 KB under them)
+    const size_t out1_cond = sizeof(float) * ((size_t)(l->wf + 1) * l->T + (size_t)GNN_OUT1_ROWS * (l->wf | 1) + (size_t)GNN_OUT1_ROWS * l->T);
+    const int ld = out1_ld(l->wf);
+    const size_t out1_lds = sizeof(float) * GNN_OUT1_ROWS * ((size_t)ld + 1);
+    if (g->n_masked && l->ou->n_layers == 1 && l->T <= 8 && out1_cond <= 64 * 1024 && out1_lds <= 64 * 1024) {
         const gnn_mlp *ou = l->ou;
-        hipLaunchKernelGGL(k_out1, cdiv(g->n_masked, GNN_OUT1_ROWS), GNN_OUT1_ROWS * l->T < 64 ? 64 : GNN_OUT1_ROWS * l->T, out1_lds, st, g->n_masked, g->sh->masked_rows,
-                           own0, own1, l->kfinal_dev, l->Ds, nodes_own, g->NL, l->NLc, ou->W[0], ou->b[0], l->T, ou->acts[0],
-                           ou->has_bn ? ou->bn_scale : (const float *)nullptr, ou->has_bn ? ou->bn_shift : (const float *)nullptr, l->out);
+#define GNN_OUT1_LAUNCH(T_)                                                                                                                        \
+    case T_:                                                                                                                                       \
+        hipLaunchKernelGGL(k_out1<T_>, cdiv(g->n_masked, GNN_OUT1_ROWS), GNN_OUT1_ROWS, out1_lds, st, g->n_masked, g->sh->masked_rows, own,       \
+                           l->kfinal_dev, l->Ds, nodes_own, g->NL, l->NLc, ld, ou->W[0], ou->b[0], ou->acts[0],                                    \
+                           ou->has_bn ? ou->bn_scale : (const float *)nullptr, ou->has_bn ? ou->bn_shift : (const float *)nullptr, l->out);        \
+        break;
+        switch (l->T) {
+            GNN_OUT1_LAUNCH(1) GNN_OUT1_LAUNCH(2) GNN_OUT1_LAUNCH(3) GNN_OUT1_LAUNCH(4) GNN_OUT1_LAUNCH(5) GNN_OUT1_LAUNCH(6) GNN_OUT1_LAUNCH(7) GNN_OUT1_LAUNCH(8)
+        default: return gnn_fail(GNN_ERR_UNSUPPORTED, "no output-stage instantiation for %d outputs", l->T);
+        }
+#undef GNN_OUT1_LAUNCH
         HIPCHK(hipGetLastError());
     } else if (g->n_masked) {
         const int64_t tot = g->n_masked * l->wf;
-        hipLaunchKernelGGL(k_feats, cdiv(tot, 256), 256, 0, st, g->n_masked, g->sh->masked_rows, own0, own1, l->kfinal_dev, l->Ds, nodes_own, g->NL, l->NLc, l->feats);
+        hipLaunchKernelGGL(k_feats, cdiv(tot, 256), 256, 0, st, g->n_masked, g->sh->masked_rows, own, l->kfinal_dev, l->Ds, nodes_own, g->NL, l->NLc, l->feats);
         HIPCHK(hipGetLastError());
         rc = launch_mlp(st, l->ou, g->n_masked, l->feats, l->wf, l->out, l->T, l->otmp[0], l->otmp[1], nullptr, 1);
         if (rc) return rc;
@@ -587,6 +646,7 @@ static int loop_prepare(gnn_loop *l)
         return gnn_fail(GNN_ERR_STATE, "net_output has the edge-based input width: call gnn_loop_set_edge_readout first");
     HIPCHK(hipSetDevice(l->device));
     l->ng_inlaunch = false;          // (set again by gnn_small_run when its form folds the graph readout into the launch)
+    l->init_in_place = false;        // (set again by loop_begin when this run's body 0 reads state_init itself)
     ++l->out_runs;                   // this run rewrites l->out: a readout folded into an earlier launch is stale from here on
     if (!l->graph_ready_seen) {      // a derived graph's creation-time fills (gnn_graph_derive) come before the first read of its labels
         int rcw = gnn_graph_wait_ready(l->g, l->stream);
@@ -637,7 +697,9 @@ static int loop_collect(gnn_loop *l, float *k_out)
 
 // Everything the ranks in `ls` put on their streams for one Loop, and the wait for it.  Bodies are enqueued without waiting for each
 // other; every GNN_BODY_CHUNK bodies the gate of the next body is copied to the host and checked, so that a loop that converged
-// does not pay for max_iteration - k empty launches (about 3 us each).  n == 1: one rank of an RCCL job (or a single GPU);
+// does not pay for max_iteration - k empty launches (about 3 us each).  The host looks at the copy only GNN_BODY_LOOKAHEAD bodies later:
+// those are queued behind it first, so the stream does not run dry while the host wakes up (behind a closed gate they return at once, and
+// k comes from the gate words: k_finalize).  n == 1: one rank of an RCCL job (or a single GPU);
 // n == world: all ranks of a loopback group, stepped phase by phase on the group's stream.  The path of every rank is its form's
 // (the persistent path only exists for world == 1, i.e. n == 1).
 static int run_loops_once(gnn_loop **ls, int n)
@@ -655,7 +717,18 @@ static int run_loops_once(gnn_loop **ls, int n)
         }
         // (feature-sliced exchange: no rank ever needs another rank's state rows, only the gates travel)
         for (int r = 0; r < n; ++r) if ((rc = loop_exchange(ls[r], ls[r]->slice_mode ? -1 : 0, 0))) return rc;
+        int fetched = -1;       // the body whose gate is on its way to the host
         for (int k = 0; k < max_iter; ++k) {
+            if (fetched >= 0 && k == fetched + GNN_BODY_LOOKAHEAD) {
+                bool closed = false, c = false;
+                for (int r = 0; r < n; ++r) {
+                    if ((rc = loop_gate_closed(ls[r], &c))) return rc;
+                    if (r == 0) closed = c;
+                    else if (c != closed) return gnn_fail(GNN_ERR_STATE, "ranks disagree on the gate of body %d", fetched);
+                }
+                if (closed) break;
+                fetched = -1;
+            }
             if (ls[0]->slice_mode) {
                 for (int r = 0; r < n; ++r) if ((rc = slice_step_pack(ls[r], k))) return rc;
                 for (int r = 0; r < n; ++r) if ((rc = slice_step_aggregate(ls[r], k))) return rc;
@@ -665,13 +738,8 @@ static int run_loops_once(gnn_loop **ls, int n)
             for (int r = 0; r < n; ++r)
                 if ((rc = loop_exchange(ls[r], ls[r]->slice_mode ? -1 : (k & 1) ^ 1, (size_t)(k + 1) * ls[r]->world * GNN_FLAG_WORDS))) return rc;
             if ((k + 1) % GNN_BODY_CHUNK == 0 && k + 1 < max_iter) {
-                bool closed = false, c = false;
-                for (int r = 0; r < n; ++r) {
-                    if ((rc = loop_gate_closed(ls[r], k + 1, &c))) return rc;
-                    if (r == 0) closed = c;
-                    else if (c != closed) return gnn_fail(GNN_ERR_STATE, "ranks disagree on the gate of body %d", k + 1);
-                }
-                if (closed) break;
+                for (int r = 0; r < n; ++r) if ((rc = loop_gate_fetch(ls[r], k + 1))) return rc;
+                fetched = k + 1;
             }
         }
     }
@@ -843,7 +911,7 @@ extern "C" int gnn_loop_get_state(const gnn_loop *l, float *state_out)
     ARGCHK(l && state_out, "bad arguments");
     if (!l->ran) return gnn_fail(GNN_ERR_STATE, "gnn_loop_run has not been called");
     HIPCHK(hipSetDevice(l->device));
-    const float *src = l->state[l->kfinal & 1] + (size_t)l->own_off * l->Ds;
+    const float *src = gnn_loop_state_after(l, l->kfinal, (size_t)l->own_off);
     HIPCHK(hipMemcpy(state_out, src, sizeof(float) * (size_t)l->g->n_rows * l->Ds, hipMemcpyDeviceToHost));
     return GNN_OK;
 }
@@ -1026,12 +1094,13 @@ extern "C" int gnn_loop_destroy(gnn_loop *l)
     gnn_train_ctx_free(l);
     gnn_train_arena_free(l);
     for (int b = 0; b < 2; ++b) { (void)hipFree(l->state[b]); (void)hipFree(l->tmp[b]); (void)hipFree(l->otmp[b]); }
-    (void)hipFree(l->inp); (void)hipFree(l->inv); (void)hipFree(l->state_init); (void)hipFree(l->feats); (void)hipFree(l->out); (void)hipFree(l->flags); (void)hipFree(l->kfinal_dev); (void)hipFree(l->tile_ctr);
+    (void)hipFree(l->inp); (void)hipFree(l->inv); (void)hipFree(l->state_init); (void)hipFree(l->feats); (void)hipFree(l->out); (void)hipFree(l->flags); (void)hipFree(l->kfinal_dev);      // (tile_ctr lives in the flag block)
     if (l->kfinal_host) (void)hipHostFree(l->kfinal_host);
     (void)hipFree(l->small_xs);
     for (hipEvent_t e : l->ev) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) if (l->ev_total[i]) (void)hipEventDestroy(l->ev_total[i]);
     if (l->gate_host) (void)hipHostFree(l->gate_host);
+    if (l->ev_gate) (void)hipEventDestroy(l->ev_gate);
     if (l->ng_host) (void)hipHostFree(l->ng_host);
     (void)hipFree(l->edge_dst); (void)hipFree(l->edge_rows); (void)hipFree(l->edge_labels); (void)hipFree(l->edge_inc_ptr); (void)hipFree(l->edge_inc);
     (void)hipFree(l->sl_send); (void)hipFree(l->sl_state); (void)hipFree(l->sl_agg); (void)hipFree(l->sl_recv); (void)hipFree(l->agg_own);

@@ -6,7 +6,7 @@
 #include <array>
 #include <vector>
 
-#include "gnn_common.h"
+#include "gnn_engine.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Device scratch of the training step: a bump allocator over slabs that stay with the loop from step to step (a step makes
@@ -54,7 +54,7 @@ struct GNN_INTERNAL gnn_train_arena {
 
 namespace gnn_train GNN_INTERNAL {
 
-inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+using ::cdiv;
 
 // rows handled by one block of the column reductions / weight-gradient tiles: about 64 blocks along the rows, so that small
 // batches (a few hundred rows) still spread over the chip; a multiple of 16 (k_wgrad's row tile), at most 1024

@@ -673,7 +673,8 @@ struct Forward {
     {
         gnn_graph *g = l->g;
         const int Ds = l->Ds, T = l->T;
-        if (sharded) {                                   // the whole replica, as after an inference Loop (k == 0 with D == 0: the label rows there are)
+        l->init_in_place = false;                        // published as "k == 0 bodies" with the state in state[0] (gnn_engine.h, gnn_state_after)
+        if (sharded) {                                  // the whole replica, as after an inference Loop (k == 0 with D == 0: the label rows there are)
             const size_t replica_floats = (size_t)l->N_pad * Ds, have = state == g->nodes ? (size_t)g->nodes_rows * Ds : replica_floats;
             HIPCHK(hipMemcpyAsync(l->state[0], state, sizeof(float) * std::min(have, replica_floats), hipMemcpyDeviceToDevice, st));
         }

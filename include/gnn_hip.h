@@ -121,10 +121,12 @@ int gnn_mlp_destroy(gnn_mlp *m);
  *   state_dim      state_vect_dim (0: state is initialised with the node labels, GNN.py:265)
  *   max_iter, thr  max_iteration, state_threshold (GNN.py:61-62)
  * gnn_loop_set_state0: injected initial state [n_rows owned, state_dim] (the reference draws tf.random.normal(stddev=0.1),
- * GNN.py:262, whose stream cannot be reproduced); NULL draws N(0, 0.1^2) from the engine's own counter RNG with `seed`.
+ * GNN.py:262, whose stream cannot be reproduced); NULL draws N(0, 0.1^2) from the engine's own counter RNG with `seed`.  The loop keeps
+ * the state in a table of its own, which only this call writes: on one GPU the first body of every later run reads it where it lies (no
+ * run copies or modifies it), so it stays byte for byte what was set until the next gnn_loop_set_state0.
  * gnn_loop_run: runs the whole loop on the device.  Bodies are enqueued 16 at a time without waiting for them (a body whose gate is
- * closed returns at once); after each 16 the host reads the next body's gate so that a converged loop stops enqueuing, and it
- * synchronises once at the end.  Small graphs (all tiles resident, nets <= 32 wide) take ONE persistent launch for the whole loop,
+ * closed returns at once); after each 16 the next body's gate is copied to the host, which looks at it four bodies later (those are
+ * queued behind the copy first), so that a converged loop stops enqueuing, and it synchronises once at the end. Small graphs (all tiles resident, nets <= 32 wide) take ONE persistent launch for the whole loop,
  * the output stage and - once a NodeGraph is cached with the loop by an earlier gnn_loop_readout - the graph readout.  *k_out = number of executed iterations as float (GNN.py:267).  This is the
  * inference Loop (training=False); training != 0 is GNN_ERR_UNSUPPORTED here: the training-mode Loop and its backward pass
  * are gnn_loop_train_forward / gnn_loop_train_backward / gnn_loop_train_step below.
