@@ -287,34 +287,44 @@ extern "C" int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, c
 // The program of g's graph on g's device, built once (with the first fused Loop, or the first gnn_loop_set_gather_form, that takes gather
 // form 2).  Never an error: a graph whose program cannot be built or kept keeps walking the CSR (sh->gp_ent stays nullptr).  The attempt is
 // made ONCE per graph (gp_tried): a graph that failed for want of memory is not tried again when memory has become free.
+// A partial last tile gets a program too: the builder on that tile's 33 row pointers, the rows past the end repeating the last offset - empty
+// rows, one GNN_GP_NOROW | GNN_GP_ROW_END slot each, an exact +0 aggregate as the CSR walk gives them.  Its batches follow the full tiles'
+// in gp_ent; its header stays on the host (gp_last_first, gp_last_nb) and travels in the kernel arguments, so that gp_hdr / gp_tiles keep
+// describing the full tiles only.
 int gnn_gather_program_ensure(const gnn_graph *g)
 {
     gnn_graph_shared *sh = g->sh;
     if (sh->gp_tried) return GNN_OK;
     sh->gp_tried = true;
-    const int64_t tiles = g->n_rows / 32;
+    const int64_t tiles = g->n_rows / 32, rem = g->n_rows % 32;
     if (tiles == 0) return GNN_OK;
     // the caller may be a setter outside any run: the copies and allocations below belong on the graph's device, whatever device is current
     int dev_before = -1;
     if (hipGetDevice(&dev_before) != hipSuccess || hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return GNN_OK; }
     const auto t0 = std::chrono::steady_clock::now();
     int32_t *d_hdr = nullptr, *d_ent = nullptr;
-    int64_t batches = 0;
+    int64_t batches = 0, last_batches = 0;
+    int32_t last_hdr[2] = {0, 0};
     bool ok = false;
     try {
-        std::vector<int32_t> indptr((size_t)tiles * 32 + 1), hdr((size_t)tiles * 2), src, ent;
+        std::vector<int32_t> indptr((size_t)g->n_rows + 1), hdr((size_t)tiles * 2), src, ent;
         std::vector<float> w;
         ok = hipMemcpy(indptr.data(), sh->indptr, sizeof(int32_t) * indptr.size(), hipMemcpyDeviceToHost) == hipSuccess;
         const size_t E = ok ? (size_t)indptr.back() : 0;
+        if (rem) indptr.resize((size_t)(tiles + 1) * 32 + 1, indptr.back());
         src.resize(E); w.resize(E);
         ok = ok && (E == 0 || (hipMemcpy(src.data(), sh->adj_src, sizeof(int32_t) * E, hipMemcpyDeviceToHost) == hipSuccess &&
                                hipMemcpy(w.data(), sh->adj_w, sizeof(float) * E, hipMemcpyDeviceToHost) == hipSuccess));
         // what the builder would refuse is looked for here, so that a graph without a program leaves no error text behind a Loop that succeeds
         for (size_t e = 0; ok && e < E; ++e) ok = src[e] >= 0 && src[e] < (1 << 23);
+        const int32_t *last_ip = indptr.data() + tiles * 32;          // the partial tile's 33 row pointers (offsets into the same arc arrays)
         ok = ok && gnn_gather_program_build(tiles * 32, indptr.data(), src.data(), w.data(), hdr.data(), nullptr, &batches) == GNN_OK;
+        if (ok && rem) ok = gnn_gather_program_build(32, last_ip, src.data(), w.data(), last_hdr, nullptr, &last_batches) == GNN_OK;
+        ok = ok && batches + last_batches < ((int64_t)1 << 31) / 64;
         if (ok) {
-            ent.resize((size_t)batches * 128);
+            ent.resize((size_t)(batches + last_batches) * 128);
             ok = gnn_gather_program_build(tiles * 32, indptr.data(), src.data(), w.data(), nullptr, ent.data(), &batches) == GNN_OK;
+            if (ok && rem) ok = gnn_gather_program_build(32, last_ip, src.data(), w.data(), nullptr, ent.data() + (size_t)batches * 128, &last_batches) == GNN_OK;
         }
         ok = ok && gnn_dev_malloc((void **)&d_hdr, sizeof(int32_t) * hdr.size()) == hipSuccess &&
              gnn_dev_malloc((void **)&d_ent, sizeof(int32_t) * ent.size()) == hipSuccess &&
@@ -322,7 +332,8 @@ int gnn_gather_program_ensure(const gnn_graph *g)
              hipMemcpy(d_ent, ent.data(), sizeof(int32_t) * ent.size(), hipMemcpyHostToDevice) == hipSuccess;
     } catch (const std::bad_alloc &) { ok = false; }
     if (ok) {
-        sh->gp_hdr = d_hdr; sh->gp_ent = d_ent; sh->gp_tiles = tiles; sh->gp_batches = batches;
+        sh->gp_hdr = d_hdr; sh->gp_ent = d_ent; sh->gp_tiles = tiles; sh->gp_batches = batches + last_batches;
+        sh->gp_rows = g->n_rows; sh->gp_last_first = (int32_t)batches; sh->gp_last_nb = (int32_t)last_batches;
         sh->gp_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     } else {
         (void)hipFree(d_hdr); (void)hipFree(d_ent);

@@ -204,7 +204,9 @@ struct gnn_graph_shared {
     // graph has no program (no full tile, sources beyond the source word's range, or no memory) and keeps walking the CSR - for its
     // lifetime: the attempt is made once, also when what failed was an allocation that might succeed later.
     int32_t *gp_hdr = nullptr, *gp_ent = nullptr;
-    int64_t gp_tiles = 0, gp_batches = 0;
+    int64_t gp_tiles = 0, gp_batches = 0;   // full tiles; batches of the full tiles and of the partial last tile together
+    int64_t gp_rows = 0;                    // rows the program was built for: gp_tiles full tiles and, if gp_last_nb > 0, one partial tile
+    int32_t gp_last_first = 0, gp_last_nb = 0;      // header of the partial last tile's program (no entry of gp_hdr), or gp_last_nb == 0
     bool gp_tried = false;
     float gp_build_ms = 0.0f;               // host time of the build, copies included
 };

@@ -68,8 +68,9 @@ struct GnnFusedArgs {
     // gather program of the graph (gnn_gather_program_build; gather form 2 of the full-tile kernel), or gp_tiles == 0: walk the CSR.
     // gp_hdr [gp_tiles][2] = {first batch, batches} of every full 32-row tile; gp_ent [batches][64][2] = {source word, weight} of lane
     // 16 g + j: entry j of lane group g in that batch, in the order the group consumes them
+    // gp_last_first / gp_last_nb: the same header for tile gp_tiles, the partial last tile of the graph (gp_last_nb == 0: it has none)
     const int32_t *gp_hdr, *gp_ent;
-    int gp_tiles;
+    int gp_tiles, gp_last_first, gp_last_nb;
     int threads;             // threads per workgroup of the launch (0: GNN_FUSED_THREADS)
     int single_ticket;       // 1: the launch has no more tiles than waves - a wave draws ONE ticket at start (no look-ahead tile)
     // diagnostics only (GNN_FUSED_STAMPS=<file>): s_memtime stamps per wave at the phase boundaries, else nullptr

@@ -489,7 +489,10 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
         // the full-tile specialisation (no generic paths compiled in) on every tile; a partial last tile takes a wave-uniform
         // branch with masked row stores / condition votes (the row buffers are padded to whole tiles, rows past n_rows have no arcs)
         a.full_tiles = 1;
-        if (f.program) { a.gp_hdr = g->sh->gp_hdr; a.gp_ent = g->sh->gp_ent; a.gp_tiles = (int)g->sh->gp_tiles; }
+        if (f.program) {
+            a.gp_hdr = g->sh->gp_hdr; a.gp_ent = g->sh->gp_ent; a.gp_tiles = (int)g->sh->gp_tiles;
+            a.gp_last_first = g->sh->gp_last_first; a.gp_last_nb = g->sh->gp_last_nb;
+        }
     }
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
@@ -604,7 +607,10 @@ int gnn_loop_decide_form(gnn_loop *l)
     f.kernel = pair ? GNN_BODY_PAIR : (l->Ds == 64 && p.NTL == 2 ? GNN_BODY_FULL_TILE : GNN_BODY_GENERIC);
     if (f.kernel == GNN_BODY_FULL_TILE && !l->slice_mode && (l->gather_form ? l->gather_form : GNN_GATHER_FORM_DEFAULT) == 2 &&
         gnn_gather_program_ensure(g) == GNN_OK)                       // (side effect 2: the graph's gather program)
-        f.program = g->sh->gp_ent != nullptr;
+        // the program kernel has no CSR walk: every tile of the launch must be a tile of the program.  A launch covers the rows [0, n_rows)
+        // of its graph from tile 0 (tile_base stays 0), so it can only end inside the graph's last tile when it has the rows the program was
+        // built for - a graph that shares the arrays but not the row count keeps form 1.
+        f.program = g->sh->gp_ent != nullptr && g->sh->gp_rows == g->n_rows;
     // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
     // 32-feature tile per layer) or, up to 4,096 rows, with hidden layers up to 64 wide (small_form), layer-0 weights kept in registers,
     // every tile resident at once (one wave each) with a wide margin

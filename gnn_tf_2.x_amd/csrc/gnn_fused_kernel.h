@@ -684,7 +684,12 @@ __device__ __forceinline__ void layer_split_from_regs(f32x16 (&hin)[NI], const f
 {
     using TM = SplitTerms<PC>;
     constexpr int TPU = NO >= 2 ? 2 : 1, UPC = NO / TPU, CH = 2 * NI, U = CH * UPC;
-    constexpr int DEPTH = (NI + NO >= 8) ? 1 : 3;       // 24 VGPRs per unit in flight next to 16 (NI + NO) of activations (128 -> 128: depth 2 spills ~40 VGPRs and is slower)
+    // 24 VGPRs per unit in flight next to 16 (NI + NO) of activations (128 -> 128: depth 2 spills ~40 VGPRs and is slower in the bf16 format;
+    // the fp16 pieces leave room for it: GNN_S1_DEPTH_WIDE, an A/B switch)
+#ifndef GNN_S1_DEPTH_WIDE
+#define GNN_S1_DEPTH_WIDE 1
+#endif
+    constexpr int DEPTH = (NI + NO >= 8) ? (PC == 2 ? GNN_S1_DEPTH_WIDE : 1) : 3;
     constexpr int NM = TM::N * NO, NTASK = 12;              // MFMAs per chunk; VALU tasks per chunk: 8 E elements, then 4 S pairs (late:
                                                         // the pieces of chunk c + 1 become live when b2 / b1 of chunk c are dead)
     v4i w[U][TPU][PC];
@@ -1105,11 +1110,11 @@ __device__ __forceinline__ void prog_consume_all(int words, const float (&w)[GB]
     (prog_consume<AL16, J>(words, w[J], x[J], acc01, acc23, xo, KP), ...);
 }
 typedef int v2i __attribute__((ext_vector_type(2)));
-// header {first batch, batches} of a tile's program, {0, 0} for a tile without one (the partial last tile, a ticket past the end): the same
-// 8 bytes for every lane
+// header {first batch, batches} of a tile's program: the same 8 bytes for every lane.  The partial last tile's header (tile gp_tiles) comes
+// with the arguments; zero batches mean "no such tile" (a ticket past the end, the look-ahead of a wave's last tile).
 __device__ __forceinline__ v2i prog_header_request(const GnnFusedArgs &a, int tile)
 {
-    v2i h = {0, 0};
+    v2i h = {a.gp_last_first, tile == a.gp_tiles ? a.gp_last_nb : 0};
     if (tile < a.gp_tiles) h = *reinterpret_cast<const GNN_GLOBAL v2i *>(gptr(a.gp_hdr) + 2 * (int64_t)tile);
     return h;
 }
@@ -1138,6 +1143,75 @@ __device__ __forceinline__ void load_tile_prog64(const GnnFusedArgs &a, float *X
         if (b + 1 < nb) ent = prog_entry(a, first + b + 1, lane);           // (wave-uniform)
         prog_consume_all<AL16, GB>(words, w, x, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
     }
+    own.write(a, X, i0, lane, KP, c_aggs);
+}
+
+// ---- the tile's first batch a tile ahead (GNN_FIRST_BATCH_AHEAD) ----
+// Every batch is a dependent round trip, and the first of a tile has nothing to hide behind.  Its 16 rows are therefore requested during the
+// PREVIOUS tile, behind the last weight loads of the dense layers (vector-memory results return in issue order: in front of them the rows
+// would hold up every weight wait), and stay in 64 registers across the epilogue, the condition and the row stores, where the dense layers'
+// registers are free.  The entry they are requested from comes with the previous tile's last gather batch (the header of this tile is back
+// by then) and is held across the dense layers: two registers.  A tile that does not exist has the entry {GNN_GP_NOROW, 0}: offsets past the
+// end of the buffer descriptor, for which the texture unit returns zeros without asking memory for anything - so the requests need no branch,
+// and the waits in front of the epilogue's gate words and of the first row count past all sixteen on every path.
+#ifndef GNN_FIRST_BATCH_AHEAD
+#define GNN_FIRST_BATCH_AHEAD 1
+#endif
+template <int GB, int... J>
+__device__ __forceinline__ void prog_rows_request(int words, __amdgpu_buffer_rsrc_t rsrc, int voff0, v4f (&x)[GB], std::integer_sequence<int, J...>)
+{
+    ((x[J] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (row_bcast_i<J>(words) & ~0xff) | voff0, 0, 0))), ...);
+}
+template <bool AL16, int GB, int... J>
+__device__ __forceinline__ void prog_consume_first(v2i ent, const v4f (&x)[GB], v2f &acc01, v2f &acc23, float *xo, int KP, std::integer_sequence<int, J...>)
+{
+    (prog_consume<AL16, J>(ent.x, row_bcast_f<J>(__int_as_float(ent.y)), x[J], acc01, acc23, xo, KP), ...);
+}
+// the entry of batch 1 of the tile with header (first, nb), if it has one, and the rows of its batch 0 from that batch's entry ent0.  The
+// conditional request goes FIRST: the compiler counts a wait down from the path with the fewest requests behind what it waits for, so behind
+// the rows it would make every wait in front of them (the gate words') reach one request further - to the first row.
+__device__ __forceinline__ void prog_first_batch_request(const GnnFusedArgs &a, int first, int nb, v2i ent0, int lane, v4f (&x0)[16], v2i &ent1)
+{
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
+    if (nb > 1) ent1 = prog_entry(a, first + 1, lane);                      // (wave-uniform)
+    __builtin_amdgcn_sched_barrier(0);
+    prog_rows_request<16>(ent0.x, rsrc, (lane & 15) * 16, x0, std::make_integer_sequence<int, 16>{});
+}
+// The loader that starts by consuming that batch.  ent0 / x0: entry and rows of batch 0; ent: entry of batch 1 (nb > 1).  hdr_next_raw: the
+// next tile's header, requested at the top of this tile; with the last batch of this tile it is read (first_next, nb_next) and the entry of
+// the next tile's batch 0 requested (ent_next; {GNN_GP_NOROW, 0} when there is no such tile).  A one-batch tile waits for the header.
+template <bool AL16>
+__device__ __forceinline__ void load_tile_prog64_ahead(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs, int first, int nb,
+                                                       v2i ent0, const v4f (&x0)[16], v2i ent, v2i hdr_next_raw, int &first_next, int &nb_next,
+                                                       v2i &ent_next)
+{
+    constexpr int GB = 16;
+    const int gl = lane & 15;
+    TileOwn64<AL16> own;
+    own.request(a, i0, lane);
+    v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
+    const int voff0 = gl * 16;
+    float *xo = X + c_aggs + gl * 4;
+    // (one variable for "the entry requested with this batch" - the next batch's, or behind the last batch the next tile's first: a second
+    // one made the compiler copy it inside the loop, behind a wait for the batch's rows)
+    auto request_next = [&]() {
+        first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
+        ent = v2i{(int)GNN_GP_NOROW, 0};
+        if (nb_next > 0) ent = prog_entry(a, first_next, lane);             // (wave-uniform)
+    };
+    if (nb <= 1) request_next();
+    prog_consume_first<AL16, GB>(ent0, x0, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
+    for (int b = 1; b < nb; ++b) {
+        float w[GB];
+        v4f x[GB];
+        const int words = ent.x;
+        prog_batch<AL16, GB>(words, __int_as_float(ent.y), rsrc, voff0, w, x, std::make_integer_sequence<int, GB>{});
+        if (b + 1 < nb) ent = prog_entry(a, first + b + 1, lane);           // (wave-uniform)
+        else request_next();
+        prog_consume_all<AL16, GB>(words, w, x, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
+    }
+    ent_next = ent;
     own.write(a, X, i0, lane, KP, c_aggs);
 }
 
@@ -1268,8 +1342,11 @@ __device__ __forceinline__ void check_store_fast64(const GnnFusedArgs &a, float 
 // across lanes l / l + 32.  The summation order differs from the oracle's ascending-feature chain; on this path the state
 // itself already differs from the oracle in the last bits, so that is within the same tolerance (k is compared in the tests).
 // peek: the gate words of this wave's slot, requested by lane 0 behind the last weight loads (gnn_flag_peek)
+// LATE: the words are first looked at HERE.  Without it the compiler compares them with zero in the block that requests them (the other
+// lanes' constant zeros invite it to) and waits for them there, in front of the epilogue instead of behind it.
+template <bool LATE = false>
 __device__ __forceinline__ void finish_fast64_aligned(const GnnFusedArgs &a, float *X, f32x16 (&out)[2], int64_t i0, int lane, int KP, int c_aggs,
-                                                      const GnnFlagPeek &peek)
+                                                      GnnFlagPeek peek)
 {
     const int half = lane >> 5;
     float *xrow = X + (lane & 31) * KP;
@@ -1292,6 +1369,7 @@ __device__ __forceinline__ void finish_fast64_aligned(const GnnFusedArgs &a, flo
     {   // certified gate (gnn_common.h): both half-lanes of a node hold the same sums
         const float rhs = a.thr * nrm, band = GNN_BAND_ABS * nrm + GNN_BAND_REL * rhs;
         const bool am = __any(root > rhs), ar = __any(root > rhs + band), ab = __any(gnn_gate_borderline(root, rhs, band));
+        if constexpr (LATE) asm volatile("" : "+v"(peek.c0), "+v"(peek.c1), "+v"(peek.c2));
         if (lane == 0) gnn_flag_raise_peeked(a.flag_out, peek, am, ar, ab);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1411,8 +1489,9 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N])
 // GIVEN (with FULL): the aggregated states come from a.agg_in (feature-sliced exchange) - row copies instead of the gather.  A
 // template parameter, not a branch: a wave-uniform branch in the tile loop of the full-tile kernel cost 3 % (0.700 -> 0.721 ms).
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
-// PROG (with FULL, not GIVEN): the full tiles are gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the
-// partial last tile of the range walks the CSR as before.  A template parameter for the same reason as GIVEN.
+// PROG (with FULL, not GIVEN): every tile is gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the partial
+// last tile of the graph too (its header comes with the arguments): no CSR walk is compiled in.  A template parameter for the same reason as
+// GIVEN.  With GNN_FIRST_BATCH_AHEAD a tile's first batch is requested during the previous tile (load_tile_prog64_ahead).
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
 template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3, bool PROG = false, int ACTL = ACT>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedArgs a0)
@@ -1471,12 +1550,17 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     }
     int ip_cur = 0, src_cur = 0;
     float w_cur = 0.0f;
-    // PROG: header of the current tile (wave-uniform) and this lane's entry of its first batch
+    // PROG: header of the current tile (wave-uniform) and this lane's entry of its first batch; AHEAD: the rows of that batch and the entry of
+    // the second too
+    // (not the bf16-piece format on 128-wide hidden layers: those instantiations stand at 254 - 255 registers without it and spill with it)
+    constexpr bool AHEAD = PROG && GNN_FIRST_BATCH_AHEAD && !(SPLIT && PC == 3 && NT == 4);
     int hdr_first = 0, hdr_nb = 0;
-    v2i ent_cur = {0, 0};
+    v2i ent_cur = {AHEAD ? (int)GNN_GP_NOROW : 0, 0}, ent_second = {0, 0};
+    v4f x_first[16];
     if constexpr (PROG) {
         hdr_first = __builtin_amdgcn_readfirstlane(hdr_first_raw.x); hdr_nb = __builtin_amdgcn_readfirstlane(hdr_first_raw.y);
         if (hdr_nb > 0) ent_cur = prog_entry(a, hdr_first, lane);
+        if constexpr (AHEAD) prog_first_batch_request(a, hdr_first, hdr_nb, ent_cur, lane, x_first, ent_second);
     } else {
         ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
         if (FULL || Ds == 64) tile_first_ids(a, ip_cur, lane, src_cur, w_cur);
@@ -1509,8 +1593,10 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
 
     // the tile's 33 row pointers go through LDS: the gather re-reads them inside divergent code, where a cross-lane
     // broadcast from lanes of another group would not be safe
-    int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
+    [[maybe_unused]] int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
     int ip_next_raw = 0;
+    int hdr_first_next = 0, hdr_nb_next = 0;
+    v2i ent_next = {0, 0};
     v2i hdr_next_raw = {0, 0};
     if constexpr (PROG) hdr_next_raw = prog_header_request(a, next_tile);     // program header of the NEXT tile: on its way during the gather
     else {
@@ -1522,15 +1608,9 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     // SIMD partner's dense VALU / MFMA stream instead of behind it
     if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
     if constexpr (FULL && GIVEN) load_tile_given64<SPLIT>(a, X, i0, lane, KP, c_aggs);      // feature-sliced exchange: no gather (a.agg_in)
-    else if constexpr (PROG) {
-        if (hdr_nb > 0) load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur);      // (wave-uniform)
-        else {                                        // the partial last tile: its row pointers and first ids are asked for here, once per launch
-            const int ip = tile_rowptr_clamp(a, tile, lane, tile_rowptr_request(a, tile, lane));
-            if (lane <= 32) ipt[lane] = ip;
-            tile_first_ids(a, ip, lane, src_cur, w_cur);
-            load_tile_fast64<SPLIT, true>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
-        }
-    }
+    else if constexpr (AHEAD)
+        load_tile_prog64_ahead<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, x_first, ent_second, hdr_next_raw, hdr_first_next, hdr_nb_next, ent_next);
+    else if constexpr (PROG) load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur);      // (every tile of the launch has a program)
     else if constexpr (FULL) load_tile_fast64<SPLIT, true>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
     else {
         if (fast64) load_tile_fast64<SPLIT>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
@@ -1597,24 +1677,37 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     // behind the last weight loads, because vector-memory results return in issue order - in front of the dense layers these
     // HBM-latency loads would hold up every weight wait - and the epilogue / norm / stores below cover their latency.
     // (no draw when the launch has no third round: two static tiles per wave cover it)
+    // AHEAD: the range flag first (it waits for its word when it is raised), then the ticket and the gate words, and only behind them the
+    // next tile's second entry and first batch: what is read first is requested first, so that no wait in the epilogue reaches the sixteen rows.
+    if constexpr (AHEAD && SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
+    // (AHEAD: the counter's address through a vector register.  An atomic at a wave-uniform address inside divergent code is rewritten by the
+    // compiler into "one lane adds, v_readfirstlane hands the result round" - and that read waits for the ticket on the spot, with the rows
+    // below queued behind it.  The only read of the ticket is the one at the end of the tile.)
     int next2_tile = 0x3fffffff;
     if (third_round) {
-        if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr, 1) + 2 * W_launch;
+        int64_t ctr_off = 0;
+        if constexpr (AHEAD) asm volatile("" : "+v"(ctr_off));
+        if constexpr (AHEAD) { if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr + ctr_off, 1); }      // (+ 2 W where it is read)
+        else if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr, 1) + 2 * W_launch;
     }
     int ip_next = 0, src_next = 0;
     float w_next = 0.0f;
-    int hdr_first_next = 0, hdr_nb_next = 0;
-    v2i ent_next = {0, 0};
-    if constexpr (PROG) {
+    if constexpr (AHEAD) { }                                  // (header and batch-0 entry of the next tile: read with this tile's last gather batch)
+    else if constexpr (PROG) {
         hdr_first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); hdr_nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
         if (hdr_nb_next > 0) ent_next = prog_entry(a, hdr_first_next, lane);
     } else {
         ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
         if (FULL || Ds == 64) tile_first_ids(a, ip_next, lane, src_next, w_next);
     }
-    if constexpr (SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
+    if constexpr (!AHEAD && SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
     GnnFlagPeek peek = {0, 0, 0};                             // the gate words of this wave's slot: on their way across the epilogue arithmetic
     if (SPLIT && NTL == 2 && lane == 0) peek = gnn_flag_peek(a.flag_out);
+    if constexpr (AHEAD) {
+        __builtin_amdgcn_sched_barrier(0);                    // (the scheduler is free to move a load in front of an earlier one)
+        prog_first_batch_request(a, hdr_first_next, hdr_nb_next, ent_next, lane, x_first, ent_second);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     bool finished = false;
     if constexpr (SPLIT && NTL == 2) {
         if (fast64) {                                         // registers -> norms, LDS (16-byte pieces), row stores
@@ -1624,7 +1717,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
                 else tile_epilogue_last<ACTL, false, true, true, true>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, a.usc[LAYERS - 1]);
             }
             GNN_STAMP(6);
-            if (nvalid == 32) finish_fast64_aligned(a, X, out, i0, lane, KP, c_aggs, peek);
+            if (nvalid == 32) finish_fast64_aligned<AHEAD>(a, X, out, i0, lane, KP, c_aggs, peek);
             else finish_fast64_partial(a, X, out, i0, lane, KP, c_aggs, nvalid);       // (full-tile kernel on the range's last, partial tile)
             finished = true;
         }
@@ -1656,7 +1749,10 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
 #undef GNN_STAMP
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next tile re-uses this wave's LDS region
     tile = next_tile;
-    next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + a0.tile_base;
+    if constexpr (AHEAD) {
+        asm volatile("" : "+v"(next2_tile));                    // first look at the ticket: here
+        next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + (third_round ? 2 * W_launch : 0) + a0.tile_base;
+    } else next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + a0.tile_base;
     ip_cur = ip_next; src_cur = src_next; w_cur = w_next;
     hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; ent_cur = ent_next;
   }
