@@ -21,6 +21,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_state0', 'gnn_loop_run', 'gnn_loop_get_state', 'gnn_loop_get_output', 'gnn_loop_readout', 'gnn_loop_set_edge_readout', 'gnn_loop_train_step',
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
            'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_loop_train_mask', 'gnn_fused_net_form', 'gnn_small_form',
+           'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -110,6 +111,24 @@ def small_form(dims, activations, n_rows, nlc=0) -> dict:
     out = np.zeros(3, np.int32)
     _check(lib().gnn_small_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(nlc)), C.c_int64(int(n_rows)), _ip(out)))
     return dict(persistent=bool(out[0]), tile=int(out[0]), wide=bool(out[1]), steps=int(out[2]))
+
+
+TRAIN_PERSISTENT_MAX_BYTES = 256 << 20      # GNN_TRAIN_PERSISTENT_MAX_BYTES of include/gnn_hip.h
+
+
+def train_persistent_form(dims, activations, n_rows, max_iter, rates=None) -> dict:
+    """gnn_train_persistent_form (host code, no device): whether a net_state of this description runs the training-mode forward of all
+    its bodies in ONE persistent launch on n_rows rows, as far as the net, the rows and the byte cap decide - dict(persistent; workgroups;
+    rows: rows per workgroup; lds: bytes of LDS per workgroup; body_bytes: what one body's caches count towards TRAIN_PERSISTENT_MAX_BYTES).
+    One GPU, allowed, not profiling and "the grid is resident at once" are the loop's part (Loop.set_train_persistent)."""
+    L = len(dims) - 1
+    if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
+    d = np.ascontiguousarray(dims, np.int32)
+    a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
+    r = _f32(rates if rates is not None else np.zeros(L + 1), (L + 1,))
+    out = np.zeros(5, np.int32)
+    _check(lib().gnn_train_persistent_form(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int64(int(n_rows)), C.c_int(int(max_iter)), _ip(out)))
+    return dict(persistent=bool(out[0]), workgroups=int(out[1]), rows=int(out[2]), lds=int(out[3]), body_bytes=int(out[4]))
 
 
 def split_f16(values, exponent=None):
@@ -736,6 +755,22 @@ class Loop:
         used = C.c_int(0)
         _check(lib().gnn_loop_set_persistent(self._h, C.c_int(bool(enable)), C.byref(used)))
         return bool(used.value)
+
+    def set_train_persistent(self, enable: bool) -> bool:
+        """gnn_loop_set_train_persistent: allow / forbid the persistent training forward of small batches (all bodies of net_state in one
+        launch, bit-identical to one launch per kernel and body); returns whether a training forward without Dropout in net_state would
+        take it on this loop now.  What the last forward actually took: train_info()."""
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_train_persistent(self._h, C.c_int(bool(enable)), C.byref(used)))
+        return bool(used.value)
+
+    def train_info(self) -> dict:
+        """gnn_loop_train_info: dict(persistent: the last train_forward() / train_step() ran its bodies in the persistent launch;
+        workgroups, barriers_per_body of that launch (0 otherwise); timeouts: how often a persistent forward of this loop gave up at a
+        barrier and was repeated launch by launch)."""
+        out = np.zeros(4, np.int32)
+        _check(lib().gnn_loop_train_info(self._h, _ip(out)))
+        return dict(persistent=bool(out[0]), workgroups=int(out[1]), barriers_per_body=int(out[2]), timeouts=int(out[3]))
 
     def set_tile_form(self, form: int) -> int:
         """gnn_loop_set_tile_form: 1 = one wave per 32-node tile, 2 = a wave pair per tile, 0 = the library's choice; returns the form the

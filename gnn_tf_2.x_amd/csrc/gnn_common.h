@@ -300,6 +300,10 @@ struct gnn_train_settings {
     struct { float value = 0.0f; double norm = 0.0, global = 0.0; } clip;
     // parameters of the loss inside gnn_loop_train_step (gnn_loop_set_loss_params)
     struct { double smoothing = 0.0, delta = 1.0; } loss;
+    // persistent training forward of small batches (gnn_loop_set_train_persistent): asked for by the caller (opt-in: measured slower than
+    // the per-body launches on MUTAG batches); a barrier of it timed out on this loop since (per-body launches until it
+    // is set again); how often that happened
+    struct { bool allowed = false, failed = false; int timeouts = 0; } persistent;
     int k_hint = 0;               // bodies the last training forward of this loop ran (the next one enqueues that many + 1 before it looks at the gates)
 };
 #define GNN_INTERNAL __attribute__((visibility("hidden")))      // the library's own: kept out of its dynamic symbol table

@@ -233,7 +233,63 @@ int launch_wgrad_f32(hipStream_t st, int64_t n, int64_t rpb, int parts, int64_t 
 // k_state_grad_rows): state rows of whole 16-byte pieces, at most 16 of them, on many rows
 inline bool state_rows16(int Ds, int64_t n) { return (Ds & 3) == 0 && Ds <= 64 && tg_many_rows(n); }
 
+// ---- persistent training forward of small batches (gnn_train_small.hip: k_train_small) ------------------------------------------------
+// Every body of net_state in ONE launch: one workgroup per BatchNormalization chunk of rows_per_block(n) rows (32, 48 or 64 below
+// GNN_TRAIN_MFMA_MIN_ROWS rows: at most 64 workgroups), which runs k_mlp_fwd's tile code on its rows and k_bn_stats / k_bn_apply's on its
+// chunk, with the grid barrier of gnn_small_common.h between the bodies.  The caches of ALL max_iter bodies are one arena block laid out
+// body after body (the kernel finds body b's arrays at b * body_floats): it must fit GNN_TRAIN_PERSISTENT_MAX_BYTES (include/gnn_hip.h).
+constexpr size_t GNN_TRAIN_PERSISTENT_MAX_LDS = (size_t)156 * 1024;      // of the 160 KiB a workgroup can have: the kernel's static words beside it
+constexpr size_t GNN_TRAIN_PERSISTENT_MIN_LDS = (size_t)84 * 1024;       // asked for at least: more than half a CU's LDS, so ONE workgroup per CU
+
+struct SmallTrainForm {
+    bool ok = false;
+    int rows = 0, grid = 0, barriers = 0;         // rows per workgroup, workgroups, grid barriers per body
+    size_t lds = 0;                               // dynamic LDS of the launch
+    // floats of one body's cache block and where its arrays start: concat rows at 0, the Dense outputs, xhat / new state / chunk statistics
+    size_t body_floats = 0, off_a[GNN_FUSED_MAXL + 1] = {}, off_xhat = 0, off_y = 0, off_part = 0;
+    size_t cap_body_bytes = 0, cap_bytes = 0;     // what the byte cap is compared with: one block WITH the BatchNormalization arrays, max_iter of them
+};
+
+// The part of the decision that the net, the rows and max_iter make (gnn_train_persistent_form, include/gnn_hip.h); net: decided by
+// net_decide_form for net_state (producer_dropout).  The loop's part (one GPU, not disabled, not profiling, co-resident): gnn_train.hip.
+inline SmallTrainForm small_train_form(const Net &net, int max_iter)
+{
+    SmallTrainForm f;
+    const gnn_mlp *m = net.m;
+    const int L = m->n_layers;
+    const int64_t n = net.rows;
+    if (n < 1) return f;
+    auto pad64 = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
+    const int F = m->dims[L];
+    f.rows = (int)rows_per_block(n);
+    f.grid = (int)cdiv(n, f.rows);
+    f.barriers = m->has_bn ? 2 : 1;
+    size_t off = pad64((size_t)n * m->dims[0]);
+    for (int l = 0; l < L && l <= GNN_FUSED_MAXL; ++l) { f.off_a[l] = off; off += pad64((size_t)n * m->dims[l + 1]); }
+    const size_t bn_floats = 2 * pad64((size_t)n * F) + pad64((size_t)f.grid * 2 * F);
+    if (m->has_bn) {
+        f.off_xhat = off; f.off_y = f.off_xhat + pad64((size_t)n * F); f.off_part = f.off_y + pad64((size_t)n * F);
+        f.body_floats = off + bn_floats;
+    } else
+        f.body_floats = off;
+    f.cap_body_bytes = sizeof(float) * (off + bn_floats);
+    f.cap_bytes = f.cap_body_bytes * (size_t)std::max(max_iter, 0);
+    // LDS: two row tiles of the widest layer, the partial sums of dense_rows (BatchNormalization's scratch takes their place afterwards)
+    const size_t need = sizeof(float) * ((size_t)2 * f.rows * net.small_maxpad + (size_t)256 * f.rows);
+    f.lds = std::max(need, GNN_TRAIN_PERSISTENT_MIN_LDS);
+    f.ok = net.build_input && net.rate[L] == 0.0f && max_iter >= 1 && f.rows <= 64 && f.grid <= 64 && need <= GNN_TRAIN_PERSISTENT_MAX_LDS &&
+           (size_t)4 * F + 1100 <= (size_t)256 * f.rows && f.cap_bytes <= GNN_TRAIN_PERSISTENT_MAX_BYTES;
+    return f;
+}
+
+// can the launch's grid be resident at once on the device (occupancy query x compute units)?
+int small_train_resident(int device, const SmallTrainForm &f, bool *ok);
+// the launch: body 0 reads build.state (== build.own), body b's cache block is cache + b * f.body_floats, words [1 + 2 max_iter] zeroed,
+// host_result: pinned [k, status] (status cleared by the caller)
+int small_train_launch(hipStream_t st, const Net &net, const SmallTrainForm &f, const InputBuild &build, int max_iter, float *cache, int *words, int *host_result);
+
 // gnn_train_net.hip: one Sequential in training mode
+void net_decide_form(Net &net, int64_t n, bool producer_dropout);
 int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
               int64_t rows, bool producer_dropout);
 int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, const MaskStream &rng, NetCache &c, float **y_out,
@@ -257,6 +313,8 @@ struct GNN_INTERNAL gnn_train_ctx {
     float *d_sw = nullptr;
     float *state = nullptr, *out_nodes = nullptr;
     int k = 0;
+    bool persistent = false;      // the bodies ran in the persistent launch (k_train_small) ...
+    int workgroups = 0, barriers = 0;     // ... of that many workgroups, with that many grid barriers per body
     int64_t N = 0, M = 0;
     int64_t N_global = 0, M_global = 0;   // sharded forward: the rows / masked rows of all ranks
     int64_t M_before = 0;                 // ... and the masked rows of the lower ranks

@@ -650,6 +650,69 @@ struct Forward {
         return GNN_OK;
     }
 
+    // The bodies, one launch per kernel and body.  Gate i = condition(state_i, state_{i-1}) decides whether body i runs; it is evaluated by
+    // the body's own first kernel.  The bodies are enqueued TRAIN_CHUNK at a time without waiting for their gates; the host then reads the
+    // gates of the chunk in one synchronisation, and the bodies enqueued from a closed gate on (at most TRAIN_CHUNK of them) are dropped:
+    // their results are never read.  *k: the executed bodies; cx->caches holds theirs, states[*k] the final state.
+    int bodies_by_launch(int *k_out)
+    {
+        const int max_iter = l->max_iter;
+        int enq = 0, k = -1, rc;
+        if ((!sharded && N == 0) || max_iter == 0) k = 0;  // no node can raise a gate / no body allowed (a rank without rows still follows the others)
+        if (sharded && (rc = cx->buf.get(&flags_all, flag_words * (size_t)l->world))) return rc;
+        while (k < 0) {
+            // the first look at the gates comes behind as many bodies as the loop's last training forward ran, plus one (a batch's iteration
+            // count moves slowly from epoch to epoch: k = 11 is then one synchronisation and one dropped body instead of three and four)
+            int chunk = enq == 0 && l->train.k_hint >= TRAIN_CHUNK ? l->train.k_hint + 1 : TRAIN_CHUNK;
+#ifdef GNN_DIAG
+            static const bool hint_off = getenv("GNN_TRAIN_K_HINT") && atoi(getenv("GNN_TRAIN_K_HINT")) == 0;
+            if (hint_off) chunk = TRAIN_CHUNK;
+#endif
+            for (const int target = std::min(max_iter, enq + chunk); enq < target; ++enq)
+                if ((rc = enqueue_body(enq))) return rc;
+            if ((rc = read_gates(enq, &k))) return rc;
+            if (k < 0 && enq == max_iter) k = max_iter;
+        }
+        cx->caches.resize((size_t)k);
+        *k_out = k;
+        return GNN_OK;
+    }
+
+    // The bodies in ONE persistent launch (gnn_train_small.hip), which stops at the first closed gate: the caches of all max_iter bodies are
+    // one block, the host reads k and the status word in one synchronisation and keeps the first k caches.  *gave_up: a barrier spin of the
+    // kernel ran out (the grid was not resident at once?) - nothing of this forward is valid, the caller repeats it launch by launch.
+    int bodies_persistent(const SmallTrainForm &pf, int *k_out, bool *gave_up)
+    {
+        gnn_graph *g = l->g;
+        Net &ns = cx->ns;
+        const gnn_mlp *m = ns.m;
+        const int Ds = l->Ds, L = m->n_layers, F = m->dims[L];
+        float *cache = nullptr;
+        int rc;
+        if ((rc = cx->buf.get(&cache, pf.body_floats * (size_t)l->max_iter))) return rc;
+        hflags[0] = 0; hflags[1] = 0;                  // [k, status]: the status word is cleared HERE, the kernel only ever sets it
+        const InputBuild build{Ds, Ds + l->NLc, tmpl, states[0], states[0], nullptr, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, l->thr, nullptr};
+        if ((rc = small_train_launch(st, ns, pf, build, l->max_iter, cache, flags, hflags))) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        if (hflags[1] != 0) { *gave_up = true; return GNN_OK; }
+        const int k = hflags[0];
+        if (k < 0 || k > l->max_iter) return gnn_fail(GNN_ERR_STATE, "internal: the persistent training forward reports %d bodies", k);
+        for (int b = 0; b < k; ++b) {
+            float *blk = cache + (size_t)b * pf.body_floats;
+            cx->caches.emplace_back();
+            NetCache &c = cx->caches.back();
+            c.n = N;
+            c.hin.assign(L, nullptr); c.a.assign(L, nullptr); c.keep.assign(L + 1, nullptr);
+            for (int q = 0; q < L; ++q) { c.a[q] = blk + pf.off_a[q]; c.hin[q] = q == 0 ? blk : c.a[q - 1]; }
+            if (m->has_bn) { c.xhat = blk + pf.off_xhat; c.stats = ns.stats_all + (size_t)b * 2 * F; }
+            states.push_back(m->has_bn ? blk + pf.off_y : c.a[L - 1]);
+        }
+        if (m->has_bn) ns.calls = k;
+        cx->persistent = true; cx->workgroups = pf.grid; cx->barriers = pf.barriers;
+        *k_out = k;
+        return GNN_OK;
+    }
+
     // net_output on the masked rows of `state`
     int output(const float *state)
     {
@@ -694,10 +757,30 @@ struct Forward {
     }
 };
 
-// Training-mode Loop.  final_sync: wait for the published state / outputs (and out_nodes_host) before returning.
-static int train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w, const float *dropout_state,
-                         const float *dropout_output, const uint8_t *masks_state, const uint8_t *masks_output, uint64_t seed,
-                         const float *bn_state, const float *bn_output, float *k_out, float *out_nodes_host, bool final_sync)
+// The loop's part of the decision for the persistent training forward (the net's, the rows' and the byte cap's part: small_train_form):
+// one GPU, allowed (gnn_loop_set_train_persistent) and never timed out on this loop, the conditions gnn_loop_decide_form applies to the
+// persistent inference launch (not disabled, not profiling), the whole grid resident at once.  f->ok says whether it is taken.
+static int train_persistent_decide(gnn_loop *l, const Net &ns, SmallTrainForm *f)
+{
+    *f = SmallTrainForm{};
+    if (l->world != 1 || !l->train.persistent.allowed || l->train.persistent.failed || l->small_disabled || l->profiling) return GNN_OK;
+    SmallTrainForm t = small_train_form(ns, l->max_iter);
+    if (!t.ok) return GNN_OK;
+    bool resident = false;
+    const int rc = small_train_resident(l->device, t, &resident);
+    if (rc) return rc;
+    if (resident) *f = t;
+    return GNN_OK;
+}
+
+// One training-mode Loop from a fresh arena.  allow_persistent: the bodies may run in the persistent launch where it is eligible;
+// *gave_up: that launch timed out at a barrier - nothing was published, the caller repeats the forward without it.  Everything else -
+// an ineligible loop, a repeat after a time-out - runs the bodies launch by launch (Forward::bodies_by_launch).
+// final_sync: wait for the published state / outputs (and out_nodes_host) before returning.
+static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w, const float *dropout_state,
+                              const float *dropout_output, const uint8_t *masks_state, const uint8_t *masks_output, uint64_t seed,
+                              const float *bn_state, const float *bn_output, float *k_out, float *out_nodes_host, bool final_sync,
+                              bool allow_persistent, bool *gave_up)
 {
     ARGCHK(l && dropout_state && dropout_output && k_out, "bad arguments");
     // Sharded FORWARD (round 3): node-range shards with full-replica numbering, one process per rank - the state rows are all-gathered
@@ -744,10 +827,9 @@ static int train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t *
         (rc = f.upload_masks(dropout_output, masks_state, masks_output))) return rc;
 
     // ---- while condition: state <- net_state(concat), training mode (GNN.py:271 with training=True) ----------------------
-    // Gate i = condition(state_i, state_{i-1}) decides whether body i runs; it is evaluated by the body's own first kernel.  The
-    // bodies are enqueued TRAIN_CHUNK at a time without waiting for their gates; the host then reads the gates of the chunk in one
-    // synchronisation, and the bodies enqueued from a closed gate on (at most TRAIN_CHUNK of them) are dropped: their results are
-    // never read.
+    // small batches: every body in ONE persistent launch (decided once per forward, here beside net_setup); else launch by launch
+    SmallTrainForm pf;
+    if (allow_persistent && !sharded && (rc = train_persistent_decide(l, cx->ns, &pf))) return rc;
     f.hflags = static_cast<int *>(arena->host.get(std::max<size_t>(sizeof(int) * f.flag_words, 4096)));
     if (!f.hflags) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
     if (sharded && l->D) {
@@ -756,29 +838,70 @@ static int train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t *
         f.states.push_back(rep0);
     } else
         f.states.push_back(const_cast<float *>(l->D ? l->state_init : g->nodes));      // (D == 0: the node labels, a replica already)
-    int enq = 0, k = -1;
-    if ((!sharded && N == 0) || max_iter == 0) k = 0;  // no node can raise a gate / no body allowed (a rank without rows still follows the others)
-    if (sharded && (rc = buf.get(&f.flags_all, f.flag_words * (size_t)l->world))) return rc;
-    while (k < 0) {
-        // the first look at the gates comes behind as many bodies as the loop's last training forward ran, plus one (a batch's iteration
-        // count moves slowly from epoch to epoch: k = 11 is then one synchronisation and one dropped body instead of three and four)
-        int chunk = enq == 0 && l->train.k_hint >= TRAIN_CHUNK ? l->train.k_hint + 1 : TRAIN_CHUNK;
-#ifdef GNN_DIAG
-        static const bool hint_off = getenv("GNN_TRAIN_K_HINT") && atoi(getenv("GNN_TRAIN_K_HINT")) == 0;
-        if (hint_off) chunk = TRAIN_CHUNK;
-#endif
-        for (const int target = std::min(max_iter, enq + chunk); enq < target; ++enq)
-            if ((rc = f.enqueue_body(enq))) return rc;
-        if ((rc = f.read_gates(enq, &k))) return rc;
-        if (k < 0 && enq == max_iter) k = max_iter;
-    }
-    cx->caches.resize((size_t)k);
+    int k = 0;
+    if (pf.ok) {
+        if ((rc = f.bodies_persistent(pf, &k, gave_up))) return rc;
+        if (*gave_up) return GNN_OK;
+    } else if ((rc = f.bodies_by_launch(&k)))
+        return rc;
     cx->state = f.states[(size_t)k];
     if ((rc = f.output(cx->state))) return rc;
     cx->k = k;
     l->train.k_hint = k;
     if ((rc = f.publish(cx->state, out_nodes_host, final_sync))) return rc;
     *k_out = (float)k;
+    return GNN_OK;
+}
+
+// Training-mode Loop: with the persistent forward where it is eligible; after a time-out of its barrier the arena is reset and the whole
+// forward repeated with one launch per kernel and body (fresh launches in this process), the event is counted and the loop keeps to
+// per-body launches until gnn_loop_set_train_persistent is called again.
+static int train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w, const float *dropout_state,
+                         const float *dropout_output, const uint8_t *masks_state, const uint8_t *masks_output, uint64_t seed,
+                         const float *bn_state, const float *bn_output, float *k_out, float *out_nodes_host, bool final_sync)
+{
+    bool gave_up = false;
+    const int rc = train_forward_once(l, src_indptr, src_dst, src_w, dropout_state, dropout_output, masks_state, masks_output, seed, bn_state, bn_output, k_out,
+                                      out_nodes_host, final_sync, true, &gave_up);
+    if (rc || !gave_up) return rc;
+    ++l->train.persistent.timeouts;
+    l->train.persistent.failed = true;
+    return train_forward_once(l, src_indptr, src_dst, src_w, dropout_state, dropout_output, masks_state, masks_output, seed, bn_state, bn_output, k_out,
+                              out_nodes_host, final_sync, false, &gave_up);
+}
+
+// allow / forbid the persistent training forward; *used: whether a forward WITHOUT Dropout in net_state would take it on this loop now
+extern "C" int gnn_loop_set_train_persistent(gnn_loop *l, int enable, int *used)
+{
+    ARGCHK(l, "loop is NULL");
+    l->train.persistent.allowed = enable != 0;
+    l->train.persistent.failed = false;
+    if (used) {
+        *used = 0;
+        if (l->world == 1 && l->g->n_rows >= 1) {
+            HIPCHK(hipSetDevice(l->device));
+            Net net;
+            net.m = l->st;
+            net.rate.assign((size_t)l->st->n_layers + 1, 0.0f);
+            net_decide_form(net, l->g->n_rows, true);
+            SmallTrainForm f;
+            const int rc = train_persistent_decide(l, net, &f);
+            if (rc) return rc;
+            *used = f.ok ? 1 : 0;
+        }
+    }
+    return GNN_OK;
+}
+
+// out[4]: the last training forward ran persistently (0 / 1), its workgroups, its grid barriers per body; time-out fall-backs of this loop so far
+extern "C" int gnn_loop_train_info(const gnn_loop *l, int *out)
+{
+    ARGCHK(l && out, "bad arguments");
+    const gnn_train_ctx *cx = l->train_ctx;
+    out[0] = cx && cx->persistent ? 1 : 0;
+    out[1] = cx ? cx->workgroups : 0;
+    out[2] = cx ? cx->barriers : 0;
+    out[3] = l->train.persistent.timeouts;
     return GNN_OK;
 }
 

@@ -3,7 +3,7 @@
 #include <stdlib.h>
 
 #include "gnn_train.h"
-#include "gnn_fused.h"            // GNN_FUSED_MAXL: k_mlp_fwd takes a Sequential of up to one layer more
+#include "gnn_train_dev.h"        // what the persistent forward of small batches (gnn_train_small.hip) runs too
 
 using namespace gnn_train;
 
@@ -45,13 +45,7 @@ __global__ void k_act_fwd(int64_t n, int F, const float *z, int act, float *a)
     if (act == GNN_ACT_SOFTMAX) {
         const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         if (r >= n) return;
-        const float *zr = z + r * F;
-        float *ar = a + r * F;
-        float m = zr[0];
-        for (int j = 1; j < F; ++j) m = zr[j] > m ? zr[j] : m;
-        float s = 0.0f;
-        for (int j = 0; j < F; ++j) { const float e = gnn_expf(zr[j] - m); ar[j] = e; s = s + e; }
-        for (int j = 0; j < F; ++j) ar[j] = __fdiv_rn(ar[j], s);
+        softmax_row(F, z + r * F, a + r * F);
     } else {
         const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         if (i < n * F) a[i] = gnn_act(z[i], act);
@@ -74,12 +68,7 @@ __global__ void k_act_bwd(int64_t n, int F, float *d, const float *a, int act)
     d[i] = d[i] * act_grad(a[i], act);
 }
 
-// Row chunks.  Every reduction over the rows of a matrix (BatchNormalization statistics, bias / weight / gamma / beta gradients)
-// is done per chunk of rows_per_block(n) rows; a chunk leaves a partial result and the partials are added in a fixed order
-// (k_sum_parts, or by the consumer itself): run-to-run identical sums without float atomics.
-// Thread layout of the column reductions: 256 threads = CW columns x (256 / CW) row lanes, CW = 2^cw_shift >= min(F, 32), so that
-// narrow matrices (F = 14, 16) still use the whole block; rows are read four at a time (independent loads in flight).
-inline int column_shift(int F) { int s = 0; while ((1 << s) < F && s < 5) ++s; return s; }
+// (Row chunks and the thread layout of the column reductions, column_shift: gnn_train_dev.h)
 
 // partial sums of x * y and x over the rows of chunk blockIdx.y: out0 / out1 [chunk * ostride + j]
 __global__ void __launch_bounds__(256) k_colreduce2(int64_t n, int F, int cw_shift, const float *__restrict__ x, const float *__restrict__ y, float *out0,
@@ -145,65 +134,13 @@ __global__ void __launch_bounds__(256) k_sum_strided(int parts, int64_t stride, 
 }
 
 // BatchNormalization, training mode, forward statistics of one row chunk: part[chunk][j] = chunk mean, part[chunk][F + j] =
-// sum over the chunk of (x - chunk mean)^2 (two passes over the chunk's rows)
+// sum over the chunk of (x - chunk mean)^2 (bn_chunk_stats)
 __global__ void __launch_bounds__(256) k_bn_stats(int64_t n, int F, int cw_shift, const float *__restrict__ h, float *part, int64_t rows_per_block)
 {
     __shared__ float s0[256];
     __shared__ float mu[32];
-    const int CW = 1 << cw_shift, RL = 256 >> cw_shift;
-    const int c = threadIdx.x & (CW - 1), ry = threadIdx.x >> cw_shift;
-    const int j = blockIdx.x * CW + c;
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
-    float a0 = 0.0f;
-    if (j < F) {
-        int64_t r = r0 + ry;
-        for (; r + 3 * RL < r1; r += 4 * RL) {
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = h[(r + q * RL) * F + j];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a0 += v[q];
-        }
-        for (; r < r1; r += RL) a0 += h[r * F + j];
-    }
-    s0[threadIdx.x] = a0;
-    __syncthreads();
-    if (ry == 0) {
-        for (int t = 1; t < RL; ++t) a0 += s0[t * CW + c];
-        mu[c] = a0 / (float)(r1 - r0);
-    }
-    __syncthreads();
-    const float m = mu[c];
-    a0 = 0.0f;
-    if (j < F) {
-        int64_t r = r0 + ry;
-        for (; r + 3 * RL < r1; r += 4 * RL) {
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = h[(r + q * RL) * F + j] - m;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a0 += v[q] * v[q];
-        }
-        for (; r < r1; r += RL) { const float dv = h[r * F + j] - m; a0 += dv * dv; }
-    }
-    __syncthreads();
-    s0[threadIdx.x] = a0;
-    __syncthreads();
-    if (ry == 0 && j < F) {
-        for (int t = 1; t < RL; ++t) a0 += s0[t * CW + c];
-        part[(size_t)blockIdx.y * 2 * F + j] = m;
-        part[(size_t)blockIdx.y * 2 * F + F + j] = a0;
-    }
-}
-
-// (count, mean, M2) of two disjoint sets of rows -> of their union (exact in real arithmetic; the order of the calls is fixed)
-__device__ __forceinline__ void stats_merge(float &cnt, float &mean, float &m2, float cb, float mb, float qb)
-{
-    if (cb == 0.0f) return;
-    const float delta = mb - mean, tot = cnt + cb;
-    mean = mean + delta * (cb / tot);
-    m2 = m2 + qb + delta * delta * (cnt * cb / tot);
-    cnt = tot;
+    bn_chunk_stats<false>(F, cw_shift, blockIdx.x << cw_shift, r0, r1, [&](int64_t r, int j) { return h[r * F + j]; }, part + (size_t)blockIdx.y * 2 * F, s0, mu);
 }
 
 // batch mean / biased batch variance from the chunk statistics, then xhat = (h - mean) / sqrt(var + eps), y = gamma xhat + beta.
@@ -215,37 +152,12 @@ __global__ void __launch_bounds__(256) k_bn_apply(int64_t n, int F, int cw_shift
     extern __shared__ float bsh[];
     __shared__ float sc[3][256];
     float *sm = bsh, *sinv = bsh + F;
-    const int CW = 1 << cw_shift, ZL = 256 >> cw_shift;
-    const int c = threadIdx.x & (CW - 1), zl = threadIdx.x >> cw_shift;
-    for (int jb = 0; jb < F; jb += CW) {
-        const int j = jb + c;
-        float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
-        if (j < F) {
-#pragma unroll 4
-            for (int z = zl; z < parts; z += ZL) {
-                const int64_t r0 = (int64_t)z * rows_per_block;
-                const float nz = (float)((r0 + rows_per_block < n ? r0 + rows_per_block : n) - r0);
-                stats_merge(cnt, mean, m2, nz, part[(size_t)z * 2 * F + j], part[(size_t)z * 2 * F + F + j]);
-            }
-        }
-        sc[0][threadIdx.x] = cnt; sc[1][threadIdx.x] = mean; sc[2][threadIdx.x] = m2;
-        __syncthreads();
-        if (zl == 0 && j < F) {
-            for (int t = 1; t < ZL; ++t) stats_merge(cnt, mean, m2, sc[0][t * CW + c], sc[1][t * CW + c], sc[2][t * CW + c]);
-            const float var = m2 / (float)n;
-            sm[j] = mean;
-            sinv[j] = 1.0f / sqrtf(var + eps);
-            if (blockIdx.x == 0) { stats[j] = mean; stats[F + j] = var; }
-        }
-        __syncthreads();
-    }
+    bn_merge_chunks<false>(n, F, cw_shift, part, parts, rows_per_block, eps, blockIdx.x == 0 ? stats : nullptr, sm, sinv, sc);
     const int64_t total = n * F, step = (int64_t)gridDim.x * blockDim.x;
     const bool small = total < ((int64_t)1 << 31);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
         const int j = small ? (int)((unsigned)i % (unsigned)F) : (int)(i % F);
-        const float xh = (h[i] - sm[j]) * sinv[j];
-        xhat[i] = xh;
-        y[i] = gamma[j] * xh + beta[j];
+        bn_normalize(h[i], sm[j], sinv[j], gamma[j], beta[j], &xhat[i], &y[i]);
     }
 }
 
@@ -385,57 +297,7 @@ __device__ __forceinline__ void wgrad_block(int bx, int by, int bz, int64_t n, i
     }
 }
 
-// Dense products of the training step, Y[r, j] = sum_k X[r, k] M[k, j] on R rows per block: 256 threads = CW output columns x KG
-// slices of the k range (CW = 2^cshift >= min(columns, 64)); every thread runs the fmaf chain of its slice (one to a few iterations
-// even for narrow layers: the loop over k is a chain of L2 round trips), the KG partial sums of an output are added in slice order
-// through LDS.  xs: R rows of X, padded to a multiple of 4 (zeros); ps: [KG][R][CW] partials.  fin(r, j, value) stores an output.
-template <int R, class Fin>
-__device__ __forceinline__ void dense_rows(int n_k, int n_k_pad, int n_cols, int cshift, const float *__restrict__ M, const float *xs, float *ps, Fin fin)
-{
-    const int CW = 1 << cshift, KG = 256 >> cshift;
-    const int c = threadIdx.x & (CW - 1), kg = threadIdx.x >> cshift;
-    const int slice = ((n_k + KG - 1) / KG + 3) & ~3;
-    const int k0 = kg * slice, k1 = k0 + slice < n_k ? k0 + slice : n_k;
-    for (int jb = 0; jb < n_cols; jb += CW) {
-        const int j = jb + c;
-        float acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-        if (j < n_cols) {
-            int k = k0;
-            for (; k + 4 <= k1; k += 4) {
-                const float w0 = M[(size_t)(k + 0) * n_cols + j], w1 = M[(size_t)(k + 1) * n_cols + j];
-                const float w2 = M[(size_t)(k + 2) * n_cols + j], w3 = M[(size_t)(k + 3) * n_cols + j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const float4 x = *reinterpret_cast<const float4 *>(&xs[r * n_k_pad + k]);
-                    acc[r] = __builtin_fmaf(x.x, w0, acc[r]);
-                    acc[r] = __builtin_fmaf(x.y, w1, acc[r]);
-                    acc[r] = __builtin_fmaf(x.z, w2, acc[r]);
-                    acc[r] = __builtin_fmaf(x.w, w3, acc[r]);
-                }
-            }
-            for (; k < k1; ++k) {
-                const float wk = M[(size_t)k * n_cols + j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) acc[r] = __builtin_fmaf(xs[r * n_k_pad + k], wk, acc[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) ps[(kg * R + r) * CW + c] = acc[r];
-        __syncthreads();
-        if (j < n_cols)
-            for (int r = kg; r < R; r += KG) {
-                float v = ps[r * CW + c];
-                for (int g = 1; g < KG; ++g) v += ps[(g * R + r) * CW + c];
-                fin(r, j, v);
-            }
-        __syncthreads();
-    }
-}
-
-inline int dense_cshift(int cols) { int s = 2; while ((1 << s) < cols && s < 6) ++s; return s; }     // CW = 4 .. 64
-inline size_t dense_lds_bytes(int R, int k_pad) { return sizeof(float) * ((size_t)R * k_pad + (size_t)256 * R); }
+// (dense_rows, dense_cshift, dense_lds_bytes: gnn_train_dev.h)
 
 // d h_in = d z . W^T, then (fused) the way back through what produced h_in: Dropout (keep != NULL) and the previous layer's
 // activation (act >= 0: d <- d * act'(a_prev))
@@ -479,28 +341,7 @@ __global__ void __launch_bounds__(256) k_dense_fwd(int64_t n, int n_in, int n_in
     });
 }
 
-// ALL Dense layers of a Sequential on a row tile in one launch (few rows: a MUTAG-sized step is bound by the number of launches): the
-// tile's activations go from layer to layer through LDS, every layer's output is also written out (the backward pass reads it); the
-// arithmetic per layer is that of k_dense_fwd (same dense_rows chains: identical bits).  No Dropout between the layers, softmax only as
-// the last activation (applied by the caller).  LDS: 2 R maxpad + 256 R floats.
-struct MlpFwd {
-    int64_t n;
-    int L, maxpad;
-    int dims[GNN_FUSED_MAXL + 2], pad[GNN_FUSED_MAXL + 2], cshift[GNN_FUSED_MAXL + 1], act[GNN_FUSED_MAXL + 1];
-    const float *W[GNN_FUSED_MAXL + 1], *b[GNN_FUSED_MAXL + 1];
-    const float *X;
-    float *Y[GNN_FUSED_MAXL + 1];
-    // build != 0 (net_state of a loop body, no Dropout in front of the first layer): the input rows are not read from X but BUILT here -
-    // the concat of k_train_input (GNN.py:223-239: own state | template columns | aggregated neighbour states, the fmaf chain over the
-    // arcs in stored order) - written to X_out for the backward pass, and the body's gate (GNN.py:202-220) is evaluated per row
-    int build, Ds, c_aggs;
-    const float *tmpl, *state, *own, *own_prev;
-    const int32_t *indptr, *adj_src;
-    const float *adj_w;
-    float *X_out;
-    float thr;
-    int *flag;
-};
+// ALL Dense layers of a Sequential on a row tile in one launch (MlpFwd, mlp_build_rows, mlp_layers: gnn_train_dev.h)
 template <int R>
 __global__ void __launch_bounds__(256) k_mlp_fwd(const MlpFwd p)
 {
@@ -508,44 +349,7 @@ __global__ void __launch_bounds__(256) k_mlp_fwd(const MlpFwd p)
     float *in = lds, *out = lds + (size_t)R * p.maxpad, *ps = lds + (size_t)2 * R * p.maxpad;
     const int64_t i0 = (int64_t)blockIdx.x * R;
     if (p.build) {
-        const int in_s = p.dims[0], Ds = p.Ds, c_aggs = p.c_aggs;
-        int moved = 0;
-        for (int t = threadIdx.x; t < R * p.pad[0]; t += blockDim.x) {
-            const int r = t / p.pad[0], c = t - r * p.pad[0];
-            const int64_t row = i0 + r;
-            float v = 0.0f;
-            if (c < in_s && row < p.n) {
-                if (c < Ds) v = p.own[row * Ds + c];
-                else if (c >= c_aggs && c < c_aggs + Ds) {
-                    const int cc = c - c_aggs;
-                    const int32_t e1 = p.indptr[row + 1];
-                    for (int32_t e = p.indptr[row]; e < e1; e += 4) {          // four arcs per step: their loads are in flight together
-                        float w[4], x[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const bool in_ = e + u < e1;
-                            w[u] = in_ ? p.adj_w[e + u] : 0.0f;
-                            x[u] = in_ ? p.state[(int64_t)p.adj_src[e + u] * Ds + cc] : 0.0f;
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) if (e + u < e1) v = __builtin_fmaf(w[u], x[u], v);
-                    }
-                } else
-                    v = p.tmpl[row * in_s + c];
-                p.X_out[row * in_s + c] = v;
-                if (c == 0) {                              // the while-condition of this body for the row (k_train_input's chain)
-                    float dist = 0.0f, nrm = 0.0f;
-                    for (int q = 0; q < Ds; ++q) {
-                        const float o = p.own_prev ? p.own_prev[row * Ds + q] : 1.0f;
-                        const float df = p.own[row * Ds + q] - o;
-                        dist = dist + df * df;
-                        nrm = nrm + o * o;
-                    }
-                    moved |= sqrtf(dist) > p.thr * sqrtf(nrm) ? 1 : 0;
-                }
-            }
-            in[t] = v;
-        }
+        const int moved = mlp_build_rows<R, false, true>(p, i0, in);
         if (__any(moved) && (threadIdx.x & 63) == 0) gnn_flag_raise(p.flag);
     } else {
         for (int t = threadIdx.x; t < R * p.pad[0]; t += blockDim.x) {
@@ -553,21 +357,9 @@ __global__ void __launch_bounds__(256) k_mlp_fwd(const MlpFwd p)
             in[t] = (k < p.dims[0] && i0 + r < p.n) ? p.X[(i0 + r) * p.dims[0] + k] : 0.0f;
         }
     }
-    for (int l = 0; l < p.L; ++l) {
-        const int no = p.dims[l + 1], npad = p.pad[l + 1], act = p.act[l];
-        for (int t = threadIdx.x; t < R * npad; t += blockDim.x) out[t] = 0.0f;          // (the padding columns of the next input)
-        __syncthreads();
-        const float *bl = p.b[l];
-        float *Yl = p.Y[l];
-        dense_rows<R>(p.dims[l], p.pad[l], no, p.cshift[l], p.W[l], in, ps, [&](int r, int j, float v) {
-            v = v + bl[j];
-            if (act != GNN_ACT_SOFTMAX) v = gnn_act(v, act);
-            out[r * npad + j] = v;
-            if (i0 + r < p.n) Yl[(i0 + r) * no + j] = v;
-        });
-        float *t_ = in; in = out; out = t_;          // (dense_rows ends with a barrier)
-    }
+    mlp_layers<R, false>(p, i0, in, out, ps);
 }
+
 
 // One Dense layer of the backward pass in one launch: the blocks of the weight / bias gradient (first wg_blocks ids: the heavier
 // ones) and the blocks of d h_in run side by side; both read d z, neither reads the other's result.
@@ -703,7 +495,7 @@ namespace gnn_train {
 // The form of this step's forward and backward calls on n rows each (Net::small_fused .. wide_bwd).  producer_dropout: the producer of
 // the input rows applies the Dropout in front of the first Dense layer (net_state: k_train_input hands its mask over as keep0) and,
 // where there is none and the rows are few, leaves the rows themselves to k_mlp_fwd.
-static void net_decide_form(Net &net, int64_t n, bool producer_dropout)
+void net_decide_form(Net &net, int64_t n, bool producer_dropout)
 {
     const gnn_mlp *m = net.m;
     const int L = m->n_layers;
@@ -851,11 +643,11 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
                 p.Ds = build->Ds; p.c_aggs = build->c_aggs; p.tmpl = build->tmpl; p.state = build->state; p.own = build->own; p.own_prev = build->own_prev;
                 p.indptr = build->indptr; p.adj_src = build->adj_src; p.adj_w = build->adj_w; p.thr = build->thr; p.flag = build->flag;
             }
-            p.n = n; p.L = L; p.maxpad = net.small_maxpad; p.X = h;
-            for (int q = 0; q <= L; ++q) { p.dims[q] = m->dims[q]; p.pad[q] = (m->dims[q] + 3) & ~3; }
+            p.n = n; p.X = h;
+            mlp_fwd_describe(p, m, net.small_maxpad);
             for (int q = 0; q < L; ++q) {
                 if ((rc = buf.get(&c.a[q], (size_t)n * m->dims[q + 1]))) return rc;
-                p.cshift[q] = dense_cshift(m->dims[q + 1]); p.act[q] = m->acts[q]; p.W[q] = m->W[q]; p.b[q] = m->b[q]; p.Y[q] = c.a[q];
+                p.Y[q] = c.a[q];
                 c.hin[q] = q == 0 ? h : c.a[q - 1];
             }
             hipLaunchKernelGGL((k_mlp_fwd<R>), cdiv(n, R), 256, net.small_lds, st, p);
@@ -1084,5 +876,29 @@ extern "C" int gnn_train_forms(int n_layers, const int *dims, const int *acts, c
     net.rate.assign(rates, rates + n_layers + 1);
     gnn_train::net_decide_form(net, n_rows, producer_dropout != 0);
     gnn_train::net_forms(net, out);
+    return GNN_OK;
+}
+
+// Whether a net_state of this description takes the persistent training forward on n_rows rows and max_iter bodies, as far as the net,
+// the rows and the byte cap decide (include/gnn_hip.h): host code, no device
+extern "C" int gnn_train_persistent_form(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int max_iter, int *out)
+{
+    ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && rates && n_rows >= 0 && max_iter >= 0 && out, "bad arguments");
+    gnn_mlp m;
+    m.n_layers = n_layers;
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.acts.assign(acts, acts + n_layers);
+    for (int l = 0; l <= n_layers; ++l) ARGCHK(m.dims[l] >= 1, "bad layer width");
+    for (int l = 0; l < n_layers; ++l) ARGCHK(m.acts[l] >= GNN_ACT_LINEAR && m.acts[l] <= GNN_ACT_SOFTMAX, "bad activation code");
+    gnn_train::Net net;
+    net.m = &m;
+    net.rate.assign(rates, rates + n_layers + 1);
+    gnn_train::net_decide_form(net, n_rows, true);
+    const gnn_train::SmallTrainForm f = gnn_train::small_train_form(net, max_iter);
+    out[0] = f.ok ? 1 : 0;
+    out[1] = f.ok ? f.grid : 0;
+    out[2] = f.ok ? f.rows : 0;
+    out[3] = f.ok ? (int)f.lds : 0;
+    out[4] = (int)std::min<size_t>(f.cap_body_bytes, 0x7fffffff);
     return GNN_OK;
 }

@@ -393,6 +393,30 @@ int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *b
 enum { GNN_FORM_PER_OP = 0, GNN_FORM_MLP_FWD = 1, GNN_FORM_WIDE = 2, GNN_FORM_CHAIN3 = 3, GNN_FORM_WGRAD_BF = 4, GNN_FORM_WGRAD_F32 = 5 };
 int gnn_train_forms(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int producer_dropout, int *out);
 int gnn_loop_train_forms(const gnn_loop *l, int net, int *out);
+/* Small batches on a single GPU run the training-mode forward of ALL bodies of net_state - the `while` of gnn_loop_train_forward /
+ * gnn_loop_train_step - in ONE persistent launch (one workgroup per BatchNormalization row chunk of 32 to 64 rows, one grid barrier per body,
+ * two with BatchNormalization), bit-identical to one launch per kernel and body: same k, state, outputs, loss, statistics and gradients.  The
+ * backward pass, net_output, the loss and the optimizer are launched as ever.  It is OPT-IN (off until gnn_loop_set_train_persistent(l, 1, ..):
+ * on MUTAG batches of 32 it measured slower than the per-body launches) and then taken when all of this holds:
+ *   - net_state has 2 to 4 Dense layers, fewer than 4,096 rows, no softmax before its last layer and no Dropout anywhere (in front of a
+ *     Dense layer or of BatchNormalization); at least one row, max_iter >= 1;
+ *   - the caches of max_iter bodies fit GNN_TRAIN_PERSISTENT_MAX_BYTES: per body the arrays [rows, width] of the concat, of every Dense
+ *     output and, counted whether or not the net has a BatchNormalization, two more of the state width and [chunks, 2 width], each rounded
+ *     up to 64 floats (the arena holds max_iter bodies then, not k + a few); its row tiles fit a workgroup's LDS;
+ *   - one GPU, not disabled by gnn_loop_set_persistent(l, 0), not profiling, every workgroup resident at once (occupancy query x CUs).
+ * Everything else takes one launch per kernel and body.  A launch whose barrier times out (bounded spins) only sets a status word: the
+ * host resets the step's scratch, repeats the forward launch by launch, counts the event and keeps this loop to per-body launches until
+ * the next gnn_loop_set_train_persistent.  enable = 0 forbids the persistent forward; *used (may be NULL): whether a forward without
+ * Dropout in net_state would take it on this loop now. */
+#define GNN_TRAIN_PERSISTENT_MAX_BYTES (256u << 20)
+int gnn_loop_set_train_persistent(gnn_loop *l, int enable, int *used);
+/* The part of that decision that the net, the rows and the byte cap make - host code, no device; arguments as gnn_train_forms (net_state).
+ * out receives 5 ints: out[0] = 1 taken / 0 not (then out[1 .. 3] are 0); out[1] = workgroups; out[2] = rows per workgroup; out[3] = bytes
+ * of LDS per workgroup; out[4] = bytes one body counts towards the cap. */
+int gnn_train_persistent_form(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int max_iter, int *out);
+/* What the last training forward of this loop did: out[0] = 1 when its bodies ran in the persistent launch, out[1] = workgroups and
+ * out[2] = grid barriers per body of that launch (0 otherwise); out[3] = time-out fall-backs of this loop so far. */
+int gnn_loop_train_info(const gnn_loop *l, int *out);
 /* Introspection for tests: the keep bytes (1 = kept) that the last gnn_loop_train_forward / gnn_loop_train_step of this loop recorded for the
  * Dropout at position pos (0 .. n_layers, the index of dropout_state / dropout_output) of net 0 (net_state, in body `body` < k) or 1
  * (net_output, body ignored) - the mask that was APPLIED, whether injected or drawn.  *count = rows * width of that position (this rank's rows /
