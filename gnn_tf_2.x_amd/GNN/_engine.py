@@ -23,7 +23,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_loop_train_mask', 'gnn_fused_net_form', 'gnn_small_form',
            'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
-           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
+           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
 
@@ -201,6 +201,16 @@ def gather_program(indptr, adj_src, adj_w):
     return hdr, ent.view(np.uint32)
 
 
+def tile_schedule(cost, waves: int, kind: int):
+    """gnn_tile_schedule_build (host code): order [slots] int32, order[slot] = the tile that ticket `slot` of a launch of `waves` waves
+    stands for; cost[t] = real entries (arcs) of tile t; kind 0 the identity, 1 the balanced order."""
+    cost = np.ascontiguousarray(cost, dtype=np.int64)
+    order = np.full(cost.size, -1, np.int32)
+    _check(lib().gnn_tile_schedule_build(C.c_int64(cost.size), cost.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int64(int(waves)), C.c_int(int(kind)),
+                                         _ip(order)))
+    return order
+
+
 def halo_plan(n_nodes: int, world: int, indptr, adj_src):
     """gnn_halo_plan: (slot [n_nodes] int32, counts [world], block) of the boundary exchange for a whole CSR-by-destination graph."""
     indptr = np.ascontiguousarray(indptr, dtype=np.int32)
@@ -336,6 +346,13 @@ class Graph:
         t, b, n, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
         _check(lib().gnn_graph_gather_program_info(self._h, C.byref(t), C.byref(b), C.byref(n), C.byref(ms)))
         return dict(tiles=t.value, batches=b.value, bytes=n.value, build_ms=ms.value)
+
+    def tile_schedule_info(self) -> dict:
+        """gnn_graph_tile_schedule_info: slots of the program kernel's tile schedule, the kind built so far (0 none, 1 ascending only, 2 the
+        balanced order too), body and tail sizes of the balanced order and its host build time."""
+        s, k, b, t, ms = C.c_int64(0), C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
+        _check(lib().gnn_graph_tile_schedule_info(self._h, C.byref(s), C.byref(k), C.byref(b), C.byref(t), C.byref(ms)))
+        return dict(slots=s.value, kind=k.value, body=b.value, tail=t.value, build_ms=ms.value)
 
     def set_arc_order(self, arc_id, arc_labels_orig) -> None:
         arc_id = np.ascontiguousarray(arc_id, dtype=np.int32)
@@ -785,6 +802,14 @@ class Loop:
         cover this loop).  Results are identical bit for bit."""
         used = C.c_int(0)
         _check(lib().gnn_loop_set_gather_form(self._h, C.c_int(int(form)), C.byref(used)))
+        return used.value
+
+    def set_tile_schedule(self, kind: int) -> int:
+        """gnn_loop_set_tile_schedule: the order in which a launch of the program kernel works through its tiles - 1 = ascending, 2 = balanced
+        by gather load (built per graph on first demand), 0 = the library's choice; returns the order the next run takes (0: its launches
+        read no program).  Results are identical bit for bit."""
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_tile_schedule(self._h, C.c_int(int(kind)), C.byref(used)))
         return used.value
 
     def counters(self) -> dict:

@@ -284,13 +284,103 @@ extern "C" int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, c
     return GNN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Tile schedule of the program kernel: the order in which a launch works through its tiles.  Host code.
+//
+// order[slot] = the tile that ticket `slot` stands for.  Kind 0: the identity.  Kind 1, the balanced order, from the tiles sorted by cost
+// descending (ties by tile id ascending, so the result is a function of the arguments alone):
+//   tail  the lightest K = min(2 waves, slots / 2) tiles come last, heaviest first - the launch ends on its cheapest tiles;
+//   body  the rest is cut into S strata of ceil(M / S) consecutive sorted tiles and dealt column-wise: one tile of every stratum, then the
+//         next of every stratum, ... - every stretch of a few times S slots holds the same mix of heavy and light tiles.
+// S = 61: a prime that does not divide a CU count, so that the first tiles of the eight waves of a workgroup (slots wave x grid + block)
+// come from eight different strata.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int gnn_tile_schedule_build(int64_t slots, const int64_t *cost, int64_t waves, int kind, int32_t *order)
+{
+    ARGCHK(slots >= 0 && slots < (int64_t)1 << 31 && order && (cost || kind == 0 || slots == 0), "slots / cost / order are required");
+    ARGCHK(waves > 0 && (kind == 0 || kind == 1), "waves must be positive, kind 0 (identity) or 1 (balanced)");
+    if (kind == 0) {
+        for (int64_t s = 0; s < slots; ++s) order[s] = (int32_t)s;
+        return GNN_OK;
+    }
+    try {
+        std::vector<int32_t> sorted((size_t)slots);
+        for (int64_t s = 0; s < slots; ++s) sorted[s] = (int32_t)s;
+        std::sort(sorted.begin(), sorted.end(), [&](int32_t x, int32_t y) { return cost[x] != cost[y] ? cost[x] > cost[y] : x < y; });
+        const int64_t K = std::min(2 * waves, slots / 2), M = slots - K;
+        const int64_t S = GNN_TILE_SCHEDULE_STRATA, C = (M + S - 1) / S;
+        int64_t p = 0;
+        for (int64_t q = 0; q < C; ++q)
+            for (int64_t r = 0; r < S; ++r)
+                if (r * C + q < M) order[p++] = sorted[r * C + q];
+        for (int64_t t = M; t < slots; ++t) order[p++] = sorted[t];
+    } catch (const std::bad_alloc &) { return gnn_fail(GNN_ERR_HIP, "no host memory for a schedule of %lld tiles", (long long)slots); }
+    return GNN_OK;
+}
+
+// Slot headers of schedule `kind` (0 identity, 1 balanced) of g's program on g's device: gp_slot[kind] [slots][4] = {first batch, batches,
+// tile id, 0}, from the headers and costs gnn_gather_program_ensure kept on the host.  The identity's array is built with the program (a
+// graph without it has no program); the balanced one on first demand, once per graph and device CU count.  false: no such array (no
+// program, or no memory - the launch then keeps the ascending order).
+bool gnn_tile_schedule_ensure(const gnn_graph *g, int kind, int64_t waves)
+{
+    gnn_graph_shared *sh = g->sh;
+    if (!sh->gp_ent || kind < 0 || kind > 1) return false;
+    if (sh->gp_slot[kind]) return kind == 0 || sh->gp_sched_waves == waves;      // (one device per graph: the CU count does not change)
+    if (kind == 1 && sh->gp_sched_tried) return false;
+    if (kind == 1) sh->gp_sched_tried = true;
+    const int64_t slots = (int64_t)sh->gp_cost.size();
+    int dev_before = -1;
+    if (hipGetDevice(&dev_before) != hipSuccess || hipSetDevice(g->device) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const auto t0 = std::chrono::steady_clock::now();
+    int32_t *d_slot = nullptr;
+    bool ok = false;
+    try {
+        std::vector<int32_t> order((size_t)slots), slot((size_t)slots * 4);
+        ok = gnn_tile_schedule_build(slots, sh->gp_cost.data(), waves, kind, order.data()) == GNN_OK;
+        for (int64_t s = 0; ok && s < slots; ++s) {
+            const int32_t t = order[s];
+            slot[4 * s] = sh->gp_hdr_host[2 * (size_t)t]; slot[4 * s + 1] = sh->gp_hdr_host[2 * (size_t)t + 1]; slot[4 * s + 2] = t; slot[4 * s + 3] = 0;
+        }
+        ok = ok && gnn_dev_malloc((void **)&d_slot, sizeof(int32_t) * std::max<size_t>(4, slot.size())) == hipSuccess &&
+             hipMemcpy(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice) == hipSuccess;
+    } catch (const std::bad_alloc &) { ok = false; }
+    if (ok) {
+        sh->gp_slot[kind] = d_slot;
+        if (kind == 1) {
+            sh->gp_sched_waves = waves;
+            sh->gp_sched_tail = std::min(2 * waves, slots / 2);
+            sh->gp_sched_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+    } else {
+        (void)hipFree(d_slot);
+        (void)hipGetLastError();
+    }
+    (void)hipSetDevice(dev_before);
+    return ok;
+}
+
+extern "C" int gnn_graph_tile_schedule_info(const gnn_graph *g, int64_t *slots, int *kind, int64_t *body, int64_t *tail, float *build_ms)
+{
+    ARGCHK(g, "graph is NULL");
+    const gnn_graph_shared *sh = g->sh;
+    const bool have = sh->gp_ent != nullptr, balanced = have && sh->gp_slot[1] != nullptr;
+    const int64_t n = have ? (int64_t)sh->gp_cost.size() : 0;
+    if (slots) *slots = n;
+    if (kind) *kind = balanced ? 2 : (have ? 1 : 0);
+    if (body) *body = balanced ? n - sh->gp_sched_tail : n;
+    if (tail) *tail = balanced ? sh->gp_sched_tail : 0;
+    if (build_ms) *build_ms = balanced ? sh->gp_sched_ms : 0.0f;
+    return GNN_OK;
+}
+
 // The program of g's graph on g's device, built once (with the first fused Loop, or the first gnn_loop_set_gather_form, that takes gather
 // form 2).  Never an error: a graph whose program cannot be built or kept keeps walking the CSR (sh->gp_ent stays nullptr).  The attempt is
 // made ONCE per graph (gp_tried): a graph that failed for want of memory is not tried again when memory has become free.
 // A partial last tile gets a program too: the builder on that tile's 33 row pointers, the rows past the end repeating the last offset - empty
 // rows, one GNN_GP_NOROW | GNN_GP_ROW_END slot each, an exact +0 aggregate as the CSR walk gives them.  Its batches follow the full tiles'
-// in gp_ent; its header stays on the host (gp_last_first, gp_last_nb) and travels in the kernel arguments, so that gp_hdr / gp_tiles keep
-// describing the full tiles only.
+// in gp_ent; its header stays on the host (gp_last_first, gp_last_nb), so that gp_hdr / gp_tiles keep describing the full tiles only, and
+// reaches the kernel as the last slot of the ascending tile schedule (gnn_tile_schedule_ensure), an ordinary slot of the balanced one.
 int gnn_gather_program_ensure(const gnn_graph *g)
 {
     gnn_graph_shared *sh = g->sh;
@@ -305,6 +395,8 @@ int gnn_gather_program_ensure(const gnn_graph *g)
     int32_t *d_hdr = nullptr, *d_ent = nullptr;
     int64_t batches = 0, last_batches = 0;
     int32_t last_hdr[2] = {0, 0};
+    std::vector<int32_t> hdr_host;
+    std::vector<int64_t> cost;
     bool ok = false;
     try {
         std::vector<int32_t> indptr((size_t)g->n_rows + 1), hdr((size_t)tiles * 2), src, ent;
@@ -330,10 +422,23 @@ int gnn_gather_program_ensure(const gnn_graph *g)
              gnn_dev_malloc((void **)&d_ent, sizeof(int32_t) * ent.size()) == hipSuccess &&
              hipMemcpy(d_hdr, hdr.data(), sizeof(int32_t) * hdr.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemcpy(d_ent, ent.data(), sizeof(int32_t) * ent.size(), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) {   // what a tile schedule is built from: header and real entries (arcs) of every slot, the partial last tile an ordinary one
+            hdr_host = hdr;
+            if (rem) { hdr_host.push_back((int32_t)batches); hdr_host.push_back(last_hdr[1]); }
+            cost.resize((size_t)(tiles + (rem ? 1 : 0)));
+            for (size_t t = 0; t < cost.size(); ++t) cost[t] = (int64_t)indptr[(t + 1) * 32] - indptr[t * 32];
+        }
     } catch (const std::bad_alloc &) { ok = false; }
     if (ok) {
         sh->gp_hdr = d_hdr; sh->gp_ent = d_ent; sh->gp_tiles = tiles; sh->gp_batches = batches + last_batches;
         sh->gp_rows = g->n_rows; sh->gp_last_first = (int32_t)batches; sh->gp_last_nb = (int32_t)last_batches;
+        sh->gp_hdr_host.swap(hdr_host); sh->gp_cost.swap(cost);
+        // the kernel finds every tile through a slot header: a program without the ascending schedule's array is no program
+        if (!gnn_tile_schedule_ensure(g, 0, 1)) {
+            (void)hipFree(d_hdr); (void)hipFree(d_ent);
+            sh->gp_hdr = sh->gp_ent = nullptr; sh->gp_tiles = sh->gp_batches = 0;
+            (void)hipGetLastError();
+        }
         sh->gp_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     } else {
         (void)hipFree(d_hdr); (void)hipFree(d_ent);

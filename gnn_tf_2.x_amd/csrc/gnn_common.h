@@ -209,6 +209,16 @@ struct gnn_graph_shared {
     int32_t gp_last_first = 0, gp_last_nb = 0;      // header of the partial last tile's program (no entry of gp_hdr), or gp_last_nb == 0
     bool gp_tried = false;
     float gp_build_ms = 0.0f;               // host time of the build, copies included
+    // Tile schedules of the program kernel (gnn_tile_schedule_build, gnn_tile_schedule_ensure): the kernel finds the tile of a ticket
+    // through gp_slot[kind] [slots][4] = {first batch, batches, tile id, 0}, slots = gp_tiles + (a partial last tile ? 1 : 0).  [0]: the
+    // ascending order, built with the program; [1]: the balanced order for launches of gp_sched_waves waves, built on first demand.
+    // gp_hdr_host / gp_cost: header and real entries (arcs) of every slot's tile in ascending order, kept on the host for that build.
+    int32_t *gp_slot[2] = {nullptr, nullptr};
+    std::vector<int32_t> gp_hdr_host;
+    std::vector<int64_t> gp_cost;
+    int64_t gp_sched_waves = 0, gp_sched_tail = 0;
+    bool gp_sched_tried = false;
+    float gp_sched_ms = 0.0f;               // host time of the balanced schedule's build, copy included
 };
 
 struct gnn_graph {
@@ -348,6 +358,7 @@ struct gnn_loop {
     int impl_req = 1;
     int tile_form = 0;                      // gnn_loop_set_tile_form: 0 library's choice, 1 one wave per tile, 2 wave pair per tile
     int gather_form = 0;                    // gnn_loop_set_gather_form: 0 library's choice, 1 walk the CSR, 2 the graph's gather program
+    int tile_schedule = 0;                  // gnn_loop_set_tile_schedule: 0 library's choice, 1 tiles in ascending order, 2 the balanced order
     LoopForm form;                          // launch form of the current run (gnn_fused.h): decided afresh by every loop_prepare, nothing of it outlives a run
     int32_t *ng_ip = nullptr, *ng_node = nullptr;   // cached NodeGraph^T (graph readout)
     float *ng_w = nullptr, *ng_out = nullptr, *ng_part = nullptr;   // ng_part [world, G, T]: per-rank partial readouts
@@ -422,6 +433,9 @@ int gnn_loop_decide_form(gnn_loop *l);
 inline int gnn_loop_impl_used(const gnn_loop *l) { return l->form.path == GNN_PATH_UNFUSED ? 0 : (l->form.split ? 2 : 1); }
 // gnn_build.hip
 int gnn_gather_program_ensure(const gnn_graph *g);
+// slot headers of schedule kind (0 ascending, 1 balanced for launches of `waves` waves) of g's program on g's device; false: none
+constexpr int GNN_TILE_SCHEDULE_STRATA = 61;
+bool gnn_tile_schedule_ensure(const gnn_graph *g, int kind, int64_t waves);
 int gnn_fused_prepare(gnn_loop *l);
 int gnn_fused_pack(gnn_mlp *m, int nlc);
 int gnn_fused_iteration(gnn_loop *l, int k);

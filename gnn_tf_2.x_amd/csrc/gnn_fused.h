@@ -68,9 +68,12 @@ struct GnnFusedArgs {
     // gather program of the graph (gnn_gather_program_build; gather form 2 of the full-tile kernel), or gp_tiles == 0: walk the CSR.
     // gp_hdr [gp_tiles][2] = {first batch, batches} of every full 32-row tile; gp_ent [batches][64][2] = {source word, weight} of lane
     // 16 g + j: entry j of lane group g in that batch, in the order the group consumes them
-    // gp_last_first / gp_last_nb: the same header for tile gp_tiles, the partial last tile of the graph (gp_last_nb == 0: it has none)
-    const int32_t *gp_hdr, *gp_ent;
-    int gp_tiles, gp_last_first, gp_last_nb;
+    // gp_last_first / gp_last_nb: the same header for tile gp_tiles, the partial last tile of the graph (gp_last_nb == 0: it has none);
+    // host-side record only - the kernel reads every header, this one included, from gp_slot
+    // gp_slot [gp_slots][4] = {first batch, batches, tile id, 0}: the program kernel's tile schedule (gnn_tile_schedule_build) - ticket s of
+    // the launch stands for the tile of slot s, the partial last tile an ordinary slot; the program kernel reads its headers from here
+    const int32_t *gp_hdr, *gp_ent, *gp_slot;
+    int gp_tiles, gp_last_first, gp_last_nb, gp_slots;
     int threads;             // threads per workgroup of the launch (0: GNN_FUSED_THREADS)
     int single_ticket;       // 1: the launch has no more tiles than waves - a wave draws ONE ticket at start (no look-ahead tile)
     // diagnostics only (GNN_FUSED_STAMPS=<file>): s_memtime stamps per wave at the phase boundaries, else nullptr
@@ -148,6 +151,7 @@ struct LoopForm {
     bool split = false;              // split arithmetic (impl 2) rather than the exact f32 MFMA (impl 1)
     int pieces = 3;                  // piece format of the split arithmetic
     bool program = false;            // the full-tile kernel gathers from the graph's program
+    int schedule = 0;                // ... working through its tiles in 1 ascending / 2 the balanced order (0: no program)
     // launch constants of the path's launches
     FusedPlan plan;
     unsigned grid = 0;

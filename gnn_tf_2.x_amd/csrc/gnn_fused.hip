@@ -21,13 +21,22 @@ constexpr int GNN_FUSED_VARIANT_DEFAULT = 1;      // bit 0: raised wave priority
 // start-up spread: every wave waits 0 .. n x 8k cycles before its first tile.  Round 2 / 3 (two tickets per wave drawn at kernel start, which
 // already spread the waves by up to 46 us): 20 rounds, 12 for grids with one to four tiles per wave.  Round 4 (static first two rounds of
 // tiles, no atomics at start; profiles/r04_midsize.txt): 8 and 6.
-constexpr int GNN_FUSED_SPREAD_DEFAULT = 8;
+#ifndef GNN_FUSED_SPREAD_DEFAULT      // (a macro so that an A/B build can turn it)
+#define GNN_FUSED_SPREAD_DEFAULT 8
+#endif
 constexpr int GNN_FUSED_SPREAD_SMALL_DEFAULT = 6;
 // gather form of the full-tile kernel when the loop leaves the choice to the library (gnn_loop_set_gather_form(l, 0)): 1 walks the CSR, 2 reads
 // the graph's gather program.  A macro so that an A/B build (tools/ab_build.sh) can turn it; the measurement behind the shipped value:
 // docs/DESIGN_appendix.md A.1, profiles/r10_gather_program.txt
 #ifndef GNN_GATHER_FORM_DEFAULT
 #define GNN_GATHER_FORM_DEFAULT 2
+#endif
+// tile schedule of the program kernel when the loop leaves the choice to the library (gnn_loop_set_tile_schedule(l, 0)): 1 tiles in ascending
+// order, 2 the balanced order (gnn_tile_schedule_build) - taken only by launches of at least four tiles per wave; below that, the latency
+// regime, nothing about it has been measured and the order stays ascending.  The measurement behind the shipped value:
+// profiles/tile_schedule.txt
+#ifndef GNN_TILE_SCHEDULE_DEFAULT
+#define GNN_TILE_SCHEDULE_DEFAULT 2
 #endif
 constexpr int S_SLACK = 2;      // zero chunks after the layer-0 block of the split image (layer0_split looks two chunks ahead)
 
@@ -492,6 +501,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
         if (f.program) {
             a.gp_hdr = g->sh->gp_hdr; a.gp_ent = g->sh->gp_ent; a.gp_tiles = (int)g->sh->gp_tiles;
             a.gp_last_first = g->sh->gp_last_first; a.gp_last_nb = g->sh->gp_last_nb;
+            a.gp_slot = g->sh->gp_slot[f.schedule == 2 ? 1 : 0]; a.gp_slots = (int)g->sh->gp_cost.size();
         }
     }
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
@@ -611,6 +621,13 @@ int gnn_loop_decide_form(gnn_loop *l)
         // of its graph from tile 0 (tile_base stays 0), so it can only end inside the graph's last tile when it has the rows the program was
         // built for - a graph that shares the arrays but not the row count keeps form 1.
         f.program = g->sh->gp_ent != nullptr && g->sh->gp_rows == g->n_rows;
+    if (f.program) {
+        // tile schedule (gnn_loop_set_tile_schedule): the balanced order where it is asked for, or where the choice is the library's and
+        // every wave of a launch on this device has four tiles or more; its slot headers are built here, on first demand
+        const int64_t waves = (int64_t)GNN_FUSED_WAVES * n_cu;
+        const int want = l->tile_schedule ? l->tile_schedule : (n_tiles >= 4 * waves ? GNN_TILE_SCHEDULE_DEFAULT : 1);
+        f.schedule = want == 2 && gnn_tile_schedule_ensure(g, 1, waves) ? 2 : 1;
+    }
     // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
     // 32-feature tile per layer) or, up to 4,096 rows, with hidden layers up to 64 wide (small_form), layer-0 weights kept in registers,
     // every tile resident at once (one wave each) with a wide margin

@@ -1110,12 +1110,14 @@ __device__ __forceinline__ void prog_consume_all(int words, const float (&w)[GB]
     (prog_consume<AL16, J>(words, w[J], x[J], acc01, acc23, xo, KP), ...);
 }
 typedef int v2i __attribute__((ext_vector_type(2)));
-// header {first batch, batches} of a tile's program: the same 8 bytes for every lane.  The partial last tile's header (tile gp_tiles) comes
-// with the arguments; zero batches mean "no such tile" (a ticket past the end, the look-ahead of a wave's last tile).
-__device__ __forceinline__ v2i prog_header_request(const GnnFusedArgs &a, int tile)
+// slot header {first batch, batches, tile id, 0} of the launch's tile schedule (a.gp_slot; gnn_tile_schedule_build): the tile that ticket
+// `slot` stands for and the header of its program - the same 16 bytes for every lane, one load.  The partial last tile of the graph is an
+// ordinary slot.  A slot at or past gp_slots is "no such tile" (a ticket past the end, the look-ahead of a wave's last tile): zero batches and
+// a tile id whose first row is at or past n_rows.
+__device__ __forceinline__ v4i prog_header_request(const GnnFusedArgs &a, int slot)
 {
-    v2i h = {a.gp_last_first, tile == a.gp_tiles ? a.gp_last_nb : 0};
-    if (tile < a.gp_tiles) h = *reinterpret_cast<const GNN_GLOBAL v2i *>(gptr(a.gp_hdr) + 2 * (int64_t)tile);
+    v4i h = {0, 0, a.gp_slots, 0};
+    if (slot < a.gp_slots) h = *reinterpret_cast<const GNN_GLOBAL v4i *>(gptr(a.gp_slot) + 4 * (int64_t)slot);
     return h;
 }
 // this lane's entry of batch b of the program
@@ -1178,12 +1180,12 @@ __device__ __forceinline__ void prog_first_batch_request(const GnnFusedArgs &a, 
     prog_rows_request<16>(ent0.x, rsrc, (lane & 15) * 16, x0, std::make_integer_sequence<int, 16>{});
 }
 // The loader that starts by consuming that batch.  ent0 / x0: entry and rows of batch 0; ent: entry of batch 1 (nb > 1).  hdr_next_raw: the
-// next tile's header, requested at the top of this tile; with the last batch of this tile it is read (first_next, nb_next) and the entry of
+// next tile's slot header, requested at the top of this tile; with the last batch of this tile it is read (first_next, nb_next, tid_next) and the entry of
 // the next tile's batch 0 requested (ent_next; {GNN_GP_NOROW, 0} when there is no such tile).  A one-batch tile waits for the header.
 template <bool AL16>
 __device__ __forceinline__ void load_tile_prog64_ahead(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs, int first, int nb,
-                                                       v2i ent0, const v4f (&x0)[16], v2i ent, v2i hdr_next_raw, int &first_next, int &nb_next,
-                                                       v2i &ent_next)
+                                                       v2i ent0, const v4f (&x0)[16], v2i ent, v4i hdr_next_raw, int &first_next, int &nb_next,
+                                                       int &tid_next, v2i &ent_next)
 {
     constexpr int GB = 16;
     const int gl = lane & 15;
@@ -1197,6 +1199,7 @@ __device__ __forceinline__ void load_tile_prog64_ahead(const GnnFusedArgs &a, fl
     // one made the compiler copy it inside the loop, behind a wait for the batch's rows)
     auto request_next = [&]() {
         first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
+        tid_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.z);
         ent = v2i{(int)GNN_GP_NOROW, 0};
         if (nb_next > 0) ent = prog_entry(a, first_next, lane);             // (wave-uniform)
     };
@@ -1490,7 +1493,7 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N])
 // template parameter, not a branch: a wave-uniform branch in the tile loop of the full-tile kernel cost 3 % (0.700 -> 0.721 ms).
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
 // PROG (with FULL, not GIVEN): every tile is gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the partial
-// last tile of the graph too (its header comes with the arguments): no CSR walk is compiled in.  A template parameter for the same reason as
+// last tile of the graph too (an ordinary slot of the tile schedule, prog_header_request): no CSR walk is compiled in.  A template parameter for the same reason as
 // GIVEN.  With GNN_FIRST_BATCH_AHEAD a tile's first batch is requested during the previous tile (load_tile_prog64_ahead).
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
 template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3, bool PROG = false, int ACTL = ACT>
@@ -1522,9 +1525,10 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     const int W_launch = (int)gridDim.x * (int)(blockDim.x >> 6);
     const int w_launch = wave * (int)gridDim.x + (int)blockIdx.x;
     const bool third_round = (int64_t)2 * W_launch * 32 < a.n_rows;          // wave-uniform: tickets are only drawn when tiles beyond 2 W exist
+    // PROG: tile / next_tile / the tickets are SLOTS of the launch's tile schedule; the tile a slot stands for comes with its header (tid)
     int tile = w_launch + a.tile_base, next_tile = w_launch + W_launch + a.tile_base;
     int ip_first_raw = 0;
-    v2i hdr_first_raw = {0, 0};
+    v4i hdr_first_raw = {0, 0, 0, 0};
     if constexpr (PROG) hdr_first_raw = prog_header_request(a, tile);
     else ip_first_raw = tile_rowptr_request(a, tile, lane);           // on its way while the workgroup stages its vectors below
     // last-layer bias and BatchNormalization scale / shift: staged once per workgroup behind the row-pointer slots
@@ -1554,11 +1558,12 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     // the second too
     // (not the bf16-piece format on 128-wide hidden layers: those instantiations stand at 254 - 255 registers without it and spill with it)
     constexpr bool AHEAD = PROG && GNN_FIRST_BATCH_AHEAD && !(SPLIT && PC == 3 && NT == 4);
-    int hdr_first = 0, hdr_nb = 0;
+    int hdr_first = 0, hdr_nb = 0, tid = 0;
     v2i ent_cur = {AHEAD ? (int)GNN_GP_NOROW : 0, 0}, ent_second = {0, 0};
     v4f x_first[16];
     if constexpr (PROG) {
         hdr_first = __builtin_amdgcn_readfirstlane(hdr_first_raw.x); hdr_nb = __builtin_amdgcn_readfirstlane(hdr_first_raw.y);
+        tid = __builtin_amdgcn_readfirstlane(hdr_first_raw.z);
         if (hdr_nb > 0) ent_cur = prog_entry(a, hdr_first, lane);
         if constexpr (AHEAD) prog_first_batch_request(a, hdr_first, hdr_nb, ent_cur, lane, x_first, ent_second);
     } else {
@@ -1567,8 +1572,8 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     }
     if constexpr (FULL) zero_pad_columns(a, X, lane, KP);             // once: no tile ever writes the padding columns
   for (;;) {
-    const int64_t i0 = (int64_t)tile * 32;
-    if (i0 >= a.n_rows) break;                        // wave-uniform; no workgroup barrier anywhere in the kernel
+    const int64_t i0 = (int64_t)(PROG ? tid : tile) * 32;
+    if (PROG ? tile >= a.gp_slots : i0 >= a.n_rows) break;        // wave-uniform; no workgroup barrier anywhere in the kernel
     const int nvalid = (int)((a0.n_rows - i0) < 32 ? (a0.n_rows - i0) : 32);
     // Fresh, compiler-opaque copies of the pointers for every tile: without this the loop-invariant address arithmetic of
     // the unrolled layers is hoisted out of the tile loop and spills (256 VGPRs + scratch instead of ~190).
@@ -1578,7 +1583,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
 #ifndef GNN_DIAG
 #define GNN_STAMP(slot) do { } while (0)
 #else
-    unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)tile << 3) : nullptr;
+    unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)(PROG ? tid : tile) << 3) : nullptr;      // (by tile id, whatever the schedule)
 #define GNN_STAMP(slot)                                                                      \
     do {                                                                                     \
         if (stamp) {                                                                         \
@@ -1595,9 +1600,9 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     // broadcast from lanes of another group would not be safe
     [[maybe_unused]] int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
     int ip_next_raw = 0;
-    int hdr_first_next = 0, hdr_nb_next = 0;
+    int hdr_first_next = 0, hdr_nb_next = 0, tid_next = 0;
     v2i ent_next = {0, 0};
-    v2i hdr_next_raw = {0, 0};
+    v4i hdr_next_raw = {0, 0, 0, 0};
     if constexpr (PROG) hdr_next_raw = prog_header_request(a, next_tile);     // program header of the NEXT tile: on its way during the gather
     else {
         if (lane <= 32) ipt[lane] = ip_cur;           // requested during the previous tile
@@ -1609,8 +1614,14 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
     if constexpr (FULL && GIVEN) load_tile_given64<SPLIT>(a, X, i0, lane, KP, c_aggs);      // feature-sliced exchange: no gather (a.agg_in)
     else if constexpr (AHEAD)
-        load_tile_prog64_ahead<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, x_first, ent_second, hdr_next_raw, hdr_first_next, hdr_nb_next, ent_next);
-    else if constexpr (PROG) load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur);      // (every tile of the launch has a program)
+        load_tile_prog64_ahead<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, x_first, ent_second, hdr_next_raw, hdr_first_next, hdr_nb_next, tid_next, ent_next);
+    else if constexpr (PROG) {
+        load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur);      // (every tile of the launch has a program)
+        // the next tile's slot header came back in front of the gather's rows: read here, it crosses the dense layers in scalar registers
+        // (these instantiations have no vector register to spare: the bf16-piece format on 128-wide hidden layers)
+        hdr_first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); hdr_nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
+        tid_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.z);
+    }
     else if constexpr (FULL) load_tile_fast64<SPLIT, true>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
     else {
         if (fast64) load_tile_fast64<SPLIT>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
@@ -1694,8 +1705,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     float w_next = 0.0f;
     if constexpr (AHEAD) { }                                  // (header and batch-0 entry of the next tile: read with this tile's last gather batch)
     else if constexpr (PROG) {
-        hdr_first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); hdr_nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
-        if (hdr_nb_next > 0) ent_next = prog_entry(a, hdr_first_next, lane);
+        if (hdr_nb_next > 0) ent_next = prog_entry(a, hdr_first_next, lane);      // (header of the next tile: read behind the gather)
     } else {
         ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
         if (FULL || Ds == 64) tile_first_ids(a, ip_next, lane, src_next, w_next);
@@ -1754,7 +1764,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + (third_round ? 2 * W_launch : 0) + a0.tile_base;
     } else next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + a0.tile_base;
     ip_cur = ip_next; src_cur = src_next; w_cur = w_next;
-    hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; ent_cur = ent_next;
+    hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; tid = tid_next; ent_cur = ent_next;
   }
 }
 

@@ -124,7 +124,7 @@ static void graph_release_shared(gnn_graph_shared *sh)
     (void)hipFree(sh->src_indptr); (void)hipFree(sh->src_dst); (void)hipFree(sh->src_w);
     (void)hipFree(sh->arc_id); (void)hipFree(sh->arc_labels_orig);
     (void)hipFree(sh->full_indptr); (void)hipFree(sh->full_src); (void)hipFree(sh->full_w);
-    (void)hipFree(sh->gp_hdr); (void)hipFree(sh->gp_ent);
+    (void)hipFree(sh->gp_hdr); (void)hipFree(sh->gp_ent); (void)hipFree(sh->gp_slot[0]); (void)hipFree(sh->gp_slot[1]);
     delete sh;
 }
 

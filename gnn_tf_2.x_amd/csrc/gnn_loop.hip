@@ -398,6 +398,15 @@ extern "C" int gnn_loop_set_gather_form(gnn_loop *l, int form, int *used)
     return rc;
 }
 
+extern "C" int gnn_loop_set_tile_schedule(gnn_loop *l, int kind, int *used)
+{
+    ARGCHK(l && kind >= 0 && kind <= 2, "kind must be 0 (library's choice), 1 (ascending tile order) or 2 (balanced tile order)");
+    l->tile_schedule = kind;
+    const int rc = gnn_loop_decide_form(l);
+    if (used) *used = l->form.path != GNN_PATH_UNFUSED && l->form.program ? l->form.schedule : 0;
+    return rc;
+}
+
 extern "C" int gnn_loop_set_profiling(gnn_loop *l, int enable)
 {
     ARGCHK(l, "loop is NULL");

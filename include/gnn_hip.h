@@ -366,6 +366,15 @@ int gnn_loop_set_tile_form(gnn_loop *l, int form, int *used);
  * Every row's fmaf chain is the same in both forms: states, outputs and k are identical bit for bit.  *used (may be NULL) = the form the
  * next run will take (0 when the fused path does not cover the loop at all); asking for the form builds the program if it is needed. */
 int gnn_loop_set_gather_form(gnn_loop *l, int form, int *used);
+/* The order in which a launch of the program kernel (gather form 2) works through its tiles.  Waves take tiles by ticket; the schedule says
+ * which tile a ticket stands for:
+ *   kind 1  ascending: ticket s is tile s;
+ *   kind 2  balanced by gather load (gnn_tile_schedule_build, kind 1 there): every stretch of the launch holds the same mix of heavy and
+ *           light tiles, and the lightest tiles come last.  Built once per graph, on first demand, from the program's own figures;
+ *   kind 0  the library's choice (default): GNN_TILE_SCHEDULE_DEFAULT for launches of at least four tiles per wave, ascending below.
+ * A node's arithmetic does not depend on when its tile runs: states, outputs and k are identical bit for bit.  *used (may be NULL) = the
+ * order the next run will take; 0 where its launches read no program. */
+int gnn_loop_set_tile_schedule(gnn_loop *l, int kind, int *used);
 /* ---- Test and diagnostic entry points of gather form 2: not part of the supported interface, they may change with the program's layout. ----
  * The gather program of rows [0, n_rows) of a CSR graph (host code; tests/test_gather_program.py).  Per full 32-row tile t: hdr[2 t] = first
  * 64-entry batch, hdr[2 t + 1] = batches; ent[(64 b + 16 g + j) 2 + {0, 1}] = {source word, weight bits} of entry j of lane group g in
@@ -376,6 +385,14 @@ int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, const int32_
                              int64_t *n_batches);
 /* Size and host build time of the program of g's graph: 0 tiles when it has none (yet).  Any pointer may be NULL. */
 int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *batches, int64_t *bytes, float *build_ms);
+/* A tile schedule (host code; tests/test_tile_schedule_host.py): order[slot] = the tile that ticket `slot` stands for, for `slots` tiles of
+ * cost[t] real entries (arcs) each and launches of `waves` waves.  kind 0: the identity.  kind 1: tiles sorted by cost descending (ties by
+ * id ascending); the lightest min(2 waves, slots / 2) last, heaviest of them first; the rest dealt column-wise over 61 strata of the sorted
+ * order, so that every window of `waves` slots has about the mean cost and the first tiles of a workgroup's waves differ. */
+int gnn_tile_schedule_build(int64_t slots, const int64_t *cost, int64_t waves, int kind, int32_t *order);
+/* Schedules of g's program: slots (0 without a program), kind built so far (1 ascending only, 2 the balanced order too), body and tail
+ * sizes of the balanced order and its host build time.  Any pointer may be NULL. */
+int gnn_graph_tile_schedule_info(const gnn_graph *g, int64_t *slots, int *kind, int64_t *body, int64_t *tail, float *build_ms);
 /* ---- Test entry points of the training step: read-only, not part of the supported interface. ----
  * Which kernels the Dense layers of a net take in a training-mode forward / backward pass on n_rows rows per call (the decision of
  * gnn_loop_train_forward; few rows: the per-op kernels or one launch for all layers, 4,096 rows and more: wide layers on the matrix cores).
