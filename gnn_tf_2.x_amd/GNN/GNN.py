@@ -40,18 +40,44 @@ class GNNnodeBased(BaseClass):
         self.seed = 0
         self.device = 0
         self.impl = 2           # 2: fused kernel, fp16-split MFMA (fastest, fp32-accurate); 1: fused, bit-exact f32 MFMA; 0: one kernel per TF op
+        self.gradient_mode = 'unrolled'     # set_gradient_mode
+        self.adjoint_max_iteration = None
+        self.adjoint_threshold = None
+
+    def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
+        """How train() differentiates the state loop.  'unrolled' (default): back-propagation through every executed body.
+        'fixed_point': the gradient at the converged state (Almeida-Pineda; Scarselli et al. 2009, section III) - the inference Loop
+        finds the state, ONE body is recorded there, the adjoint iteration z <- g + J^T z runs until no node's z moves by more than
+        ``threshold`` (relative L2, default: the model's state threshold) or ``max_iteration`` iterations (default: the model's), and one
+        weight-gradient pass with the final z gives net_state's gradients.  These are not a sum over bodies: ``mean`` does NOT divide them
+        by the iteration count.  Needs a net_state without Dropout and BatchNormalization (NotImplementedError); net_output is free.
+        Kept by copy() (so by LKO) and by save() / load()."""
+        if mode not in ('unrolled', 'fixed_point'): raise ValueError("param <mode> not in ['unrolled', 'fixed_point']")
+        if mode == 'fixed_point' and (self.net_state.batch_normalization or any(float(r) != 0.0 for r in self.net_state.dropout_rates())):
+            raise NotImplementedError('fixed_point gradients need a net_state without Dropout and BatchNormalization: its training-mode '
+                                      'forward must be the inference forward')
+        if max_iteration is not None and int(max_iteration) < 1: raise ValueError('param <max_iteration> must be >= 1 or None')
+        if threshold is not None and not float(threshold) >= 0.0: raise ValueError('param <threshold> must be >= 0 or None')
+        self.gradient_mode = mode
+        self.adjoint_max_iteration = None if max_iteration is None else int(max_iteration)
+        self.adjoint_threshold = None if threshold is None else float(threshold)
+
+    def _gradient_config(self) -> dict:
+        return {'mode': self.gradient_mode, 'max_iteration': self.adjoint_max_iteration, 'threshold': self.adjoint_threshold}
 
     # ---- copies, weights ---------------------------------------------------------------------------------------------
     def copy(self, *, path_writer: str = '', namespace: str = '', copy_weights: bool = True):
         optimizer = self.optimizer
         if hasattr(optimizer, 'get_config'):
             optimizer = optimizer.__class__(**optimizer.get_config())
-        return self.__class__(net_state=clone_model(self.net_state, copy_weights), net_output=clone_model(self.net_output, copy_weights),
-                              optimizer=optimizer, loss_function=self.loss_function, loss_arguments=self.loss_args,
-                              max_iteration=self.max_iteration, threshold=self.state_threshold,
-                              addressed_problem=self.addressed_problem, extra_metrics=self.extra_metrics,
-                              extra_metrics_arguments=self.mt_args, state_vect_dim=self.state_vect_dim,
-                              path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
+        new = self.__class__(net_state=clone_model(self.net_state, copy_weights), net_output=clone_model(self.net_output, copy_weights),
+                             optimizer=optimizer, loss_function=self.loss_function, loss_arguments=self.loss_args,
+                             max_iteration=self.max_iteration, threshold=self.state_threshold,
+                             addressed_problem=self.addressed_problem, extra_metrics=self.extra_metrics,
+                             extra_metrics_arguments=self.mt_args, state_vect_dim=self.state_vect_dim,
+                             path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
+        new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
+        return new
 
     def save(self, path: str):
         """Save the model to folder <path>, without extra_metrics (reference GNN.py:93-111; the reference writes two Keras
@@ -69,7 +95,8 @@ class GNNnodeBased(BaseClass):
         with open(f'{path}config.json', 'w') as f:
             json.dump({'loss_function': loss_name if hasattr(losses, str(loss_name)) else None, 'loss_arguments': self.loss_args,
                        'optimizer': optimizers.serialize(self.optimizer), 'max_iteration': self.max_iteration, 'threshold': self.state_threshold,
-                       'addressed_problem': self.addressed_problem, 'state_vect_dim': self.state_vect_dim}, f)
+                       'addressed_problem': self.addressed_problem, 'state_vect_dim': self.state_vect_dim,
+                       'gradient_mode': self._gradient_config()}, f)
 
     @classmethod
     def load(cls, path: str, path_writer=None, namespace: str = 'GNN', extra_metrics=None, extra_metrics_arguments=None):
@@ -84,6 +111,7 @@ class GNNnodeBased(BaseClass):
         optz = optimizers.deserialize(config.pop('optimizer', None))
         loss_name = config.pop('loss_function', None)
         loss = getattr(losses, loss_name) if loss_name else None
+        gradient = config.pop('gradient_mode', None) or {'mode': 'unrolled'}      # (a model saved before the mode existed: unrolled)
         nets = []
         for name in ('net_state', 'net_output'):
             with open(f'{path}{name}.json') as f:
@@ -91,8 +119,10 @@ class GNNnodeBased(BaseClass):
             with np.load(f'{path}{name}.npz') as z:
                 weights = [z[f'arr_{i}'] for i in range(len(z.files))]
             nets.append(sequential_from_config(arch, weights))
-        return cls(net_state=nets[0], net_output=nets[1], optimizer=optz, loss_function=loss, extra_metrics=extra_metrics,
-                   extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
+        model = cls(net_state=nets[0], net_output=nets[1], optimizer=optz, loss_function=loss, extra_metrics=extra_metrics,
+                    extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
+        model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'))
+        return model
 
     def get_dense_layers(self):
         return self.net_state.dense_layers + self.net_output.dense_layers
@@ -136,6 +166,10 @@ class GNNnodeBased(BaseClass):
         if getattr(loop, '_impl_set', None) != self.impl:      # (gnn_loop_set_impl checks the fused path, which re-packs the weight images when the weights
             loop.set_impl(self.impl)                          #  have changed - 0.17 ms after every optimizer step; the next inference Loop packs them anyway)
             loop._impl_set = self.impl
+        gradient = (self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
+        if getattr(loop, '_gradient_set', ('unrolled', None, None)) != gradient:
+            loop.set_gradient_mode(*gradient)
+            loop._gradient_set = gradient
         return loop
 
     def _prerun(self, graphs) -> list:
@@ -183,7 +217,7 @@ class GNNnodeBased(BaseClass):
 
     def training_step(self, g: GraphTensor, mean: bool, *, state0=None, masks_state=None, masks_output=None) -> dict:
         """One batch: device gradients (gnn_loop_train_step), net_state gradients divided by the iteration count when
-        ``mean`` (reference GNN_BaseClass.py:241), optimizer update, BatchNormalization moving statistics.  L1L2 kernel / bias
+        ``mean`` (reference GNN_BaseClass.py:241; not in gradient mode 'fixed_point', whose gradients are no sum over bodies), optimizer update, BatchNormalization moving statistics.  L1L2 kernel / bias
         regularizers, the optimizer's clipvalue / clipnorm / global_clipnorm and the loss with its label_smoothing / delta
         (``loss_arguments``) are part of the device step.  Returns the raw
         result of the device step (loss with the penalty, k, gradients with the regularizer terms) for inspection."""
@@ -239,7 +273,8 @@ class GNNnodeBased(BaseClass):
             for li, (gk, gb) in enumerate(rg):
                 if gk is not None: res[key][2 * li] = res[key][2 * li] + gk
                 if gb is not None: res[key][2 * li + 1] = res[key][2 * li + 1] + gb
-        gs = [a / k for a in res['grads_state']] if (mean and k) else res['grads_state']
+        # (fixed-point mode: net_state's gradients are one pass at the converged state, not a sum over k bodies - nothing to average)
+        gs = [a / k for a in res['grads_state']] if (mean and k and self.gradient_mode == 'unrolled') else res['grads_state']
         ws, wo = self.net_state.trainable_variables, self.net_output.trainable_variables
         new = self.optimizer.apply_gradients(zip(gs + res['grads_output'], ws + wo))
         self.net_state.set_trainable(new[:len(ws)])

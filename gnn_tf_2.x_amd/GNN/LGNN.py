@@ -35,6 +35,12 @@ class LGNN(BaseClass):
             gnn.namespace = [name]
             gnn.path_writer = f'{self.path_writer}{name}/'
 
+    def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
+        """GNNnodeBased.set_gradient_mode for every layer.  'serial' training runs the layers' own steps and works in both modes; the joint
+        steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' does not return:
+        they raise NotImplementedError while any layer is in that mode."""
+        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold)
+
     def copy(self, *, path_writer: str = '', namespace: str = '', copy_weights: bool = True) -> 'LGNN':
         optimizer = self.optimizer
         if hasattr(optimizer, 'get_config'):
@@ -221,6 +227,9 @@ class LGNN(BaseClass):
         edge_based = self.GNNS_TYPE == GNNedgeBased
         if self.training_mode not in ('parallel', 'residual'):
             raise ValueError("training_step is the joint step of training_mode 'parallel' / 'residual'")
+        if any(gnn.gradient_mode != 'unrolled' for gnn in self.gnns):
+            raise NotImplementedError(f"training_mode '{self.training_mode}' needs the unrolled gradient: a layer in gradient mode 'fixed_point' "
+                                      f"returns no gradient for its labels (use training_mode 'serial', or set_gradient_mode('unrolled'))")
         if isinstance(g, GraphObject): g = GraphTensor.fromGraphObject(g)
         if self.optimizer is None or not hasattr(self.optimizer, 'apply_gradients'):
             raise TypeError('train() needs an optimizer with apply_gradients, e.g. GNN.optimizers.Adam()')

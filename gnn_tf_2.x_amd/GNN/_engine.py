@@ -22,6 +22,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
            'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_loop_train_mask', 'gnn_fused_net_form', 'gnn_small_form',
            'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
+           'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -60,7 +61,7 @@ def loss_grad(loss_kind: int, targets, out, sample_weights, label_smoothing: flo
     return float(loss.value), d
 
 
-FORM_NAMES = {0: 'per_op', 1: 'mlp_fwd', 2: 'wide', 3: 'chain3', 4: 'wgrad_bf', 5: 'wgrad_f32'}      # GNN_FORM_* of include/gnn_hip.h
+FORM_NAMES = {0: 'per_op', 1: 'mlp_fwd', 2: 'wide', 3: 'chain3', 4: 'wgrad_bf', 5: 'wgrad_f32', 6: 'adjoint_narrow'}      # GNN_FORM_* of include/gnn_hip.h
 
 
 def _forms_dict(out):
@@ -129,6 +130,27 @@ def train_persistent_form(dims, activations, n_rows, max_iter, rates=None) -> di
     out = np.zeros(5, np.int32)
     _check(lib().gnn_train_persistent_form(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int64(int(n_rows)), C.c_int(int(max_iter)), _ip(out)))
     return dict(persistent=bool(out[0]), workgroups=int(out[1]), rows=int(out[2]), lds=int(out[3]), body_bytes=int(out[4]))
+
+
+GATHER_NAMES = {0: 'generic', 1: 'rows', 2: 'rows_aligned', 3: 'narrow'}       # gather form of gnn_loop_adjoint_info / gnn_adjoint_form
+ADJOINT_REFUSALS = {0: None, 1: 'batch_normalization', 2: 'dropout'}
+NARROW_REFUSALS = {0: None, 3: 'layers', 4: 'width', 5: 'concat', 6: 'rows', 7: 'softmax'}      # why the one-launch iteration of narrow nets is not taken
+
+
+def adjoint_form(dims, activations, n_rows, rates=None, batch_normalization=False) -> dict:
+    """gnn_adjoint_form (host code, no device): what an adjoint iteration of the fixed-point gradient launches for a net_state of this
+    description on n_rows rows - dict(eligible; reason: None, 'batch_normalization' or 'dropout'; gather: a name of GATHER_NAMES;
+    backward: one name of FORM_NAMES per Dense layer; narrow_refusal: None when an iteration is ONE launch (k_adjoint_narrow), else why
+    not: 'layers' (> 3), 'width' (> 64), 'concat' (> 96), 'rows' (>= 4,096 or none), 'softmax').  The state width is dims[-1]."""
+    L = len(dims) - 1
+    if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
+    d = np.ascontiguousarray(dims, np.int32)
+    a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
+    r = _f32(rates if rates is not None else np.zeros(L + 1), (L + 1,))
+    out = np.zeros(4 + L, np.int32)
+    _check(lib().gnn_adjoint_form(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int(bool(batch_normalization)), C.c_int64(int(n_rows)), _ip(out)))
+    return dict(eligible=bool(out[0]), reason=ADJOINT_REFUSALS[int(out[1])], gather=GATHER_NAMES[int(out[2])],
+                backward=[FORM_NAMES[int(v)] for v in out[3:3 + L]], narrow_refusal=NARROW_REFUSALS[int(out[3 + L])])
 
 
 def split_f16(values, exponent=None):
@@ -610,8 +632,12 @@ class Loop:
             return out
 
         kk = int(k.value)
-        return dict(loss=float(loss.value), k=float(k.value), grads_state=split(gs, shp_s), grads_output=split(go, shp_o),
-                    bn_batch_state=bns[:kk], bn_batch_output=bno)
+        res = dict(loss=float(loss.value), k=float(k.value), grads_state=split(gs, shp_s), grads_output=split(go, shp_o),
+                   bn_batch_state=bns[:kk], bn_batch_output=bno)
+        if getattr(self, '_gradient_mode', 0) != 0:
+            info = self.adjoint_info()
+            res.update(adjoint_iterations=info['iterations'], adjoint_converged=info['converged'])
+        return res
 
     def set_slice_exchange(self, on=True, form=None):
         """gnn_loop_set_slice_exchange: feature-sliced all-to-all instead of the all-gather of state rows.  on: any truthy value (True, 1,
@@ -780,6 +806,32 @@ class Loop:
         used = C.c_int(0)
         _check(lib().gnn_loop_set_train_persistent(self._h, C.c_int(bool(enable)), C.byref(used)))
         return bool(used.value)
+
+    def set_gradient_mode(self, mode, max_iteration=None, threshold=None) -> int:
+        """gnn_loop_set_gradient_mode: 'unrolled' / 0 (default: back-propagation through the executed bodies) or 'fixed_point' / 1 (the
+        gradient at the converged state: inference Loop, one recorded body, adjoint iteration z <- g + J^T z, one weight-gradient pass).
+        max_iteration / threshold of the adjoint iteration: None = the loop's own.  In fixed-point mode grads_state is NOT a sum over bodies
+        (never divide it by k), train_step() reports adjoint_iterations / adjoint_converged, and net_state must have neither Dropout nor
+        BatchNormalization (NotImplementedError).  'fixed_point_chain' / 2: fixed point without the one-launch iteration of narrow nets (A/B runs, tests)."""
+        code = {'unrolled': 0, 'fixed_point': 1, 'fixed_point_chain': 2, 0: 0, 1: 1, 2: 2}.get(mode)
+        if code is None: raise ValueError("gradient mode must be 'unrolled' or 'fixed_point'")
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_gradient_mode(self._h, C.c_int(code), C.c_int(int(max_iteration) if max_iteration else 0),
+                                                C.c_float(-1.0 if threshold is None else float(threshold)), C.byref(used)))
+        self._gradient_mode = used.value
+        return used.value
+
+    def adjoint_info(self) -> dict:
+        """gnn_loop_adjoint_info: dict(iterations, converged, gather) of the last backward pass in fixed-point mode."""
+        it, cv, fm = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().gnn_loop_adjoint_info(self._h, C.byref(it), C.byref(cv), C.byref(fm)))
+        return dict(iterations=int(it.value), converged=bool(cv.value), gather=GATHER_NAMES[int(fm.value)])
+
+    def train_arena_bytes(self) -> int:
+        """gnn_loop_train_arena_bytes (test entry point): bytes of device scratch the last training forward / backward of this loop used."""
+        b = C.c_int64(0)
+        _check(lib().gnn_loop_train_arena_bytes(self._h, C.byref(b)))
+        return int(b.value)
 
     def train_info(self) -> dict:
         """gnn_loop_train_info: dict(persistent: the last train_forward() / train_step() ran its bodies in the persistent launch;

@@ -315,6 +315,9 @@ struct gnn_train_settings {
     // is set again); how often that happened
     struct { bool allowed = false, failed = false; int timeouts = 0; } persistent;
     int k_hint = 0;               // bodies the last training forward of this loop ran (the next one enqueues that many + 1 before it looks at the gates)
+    // gradient mode (gnn_loop_set_gradient_mode): 0 the unrolled gradient, 1 the gradient at the fixed point (gnn_train_adjoint.hip); max_iter 0 /
+    // thr < 0: the loop's own; iterations, converged, gather: what the last backward pass of mode 1 ran (gnn_loop_adjoint_info)
+    struct { int mode = 0, max_iter = 0; float thr = -1.0f; int iterations = 0, converged = 0, gather = 0; } adjoint;
 };
 #define GNN_INTERNAL __attribute__((visibility("hidden")))      // the library's own: kept out of its dynamic symbol table
 struct GNN_INTERNAL gnn_train_ctx;                // gnn_train.h

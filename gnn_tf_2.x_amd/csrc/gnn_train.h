@@ -15,7 +15,14 @@ struct GNN_INTERNAL gnn_train_arena {
     struct Slab { char *p; size_t size; };
     std::vector<Slab> slabs;
     size_t cur = 0, off = 0;
-    void reset() { cur = 0; off = 0; }
+    void reset() { cur = 0; off = 0; peak = 0; }
+    // scratch that is needed again and again (the adjoint iterations of gnn_train_adjoint.hip): everything allocated after mark() is handed out
+    // again after rewind() - the work that used it runs earlier on the same stream.  INVARIANT: nothing allocated between mark() and rewind()
+    // may be remembered beyond it (a pointer cached on a Net, such as Net::part, would then alias later allocations): net_backward with
+    // wgrad = false allocates per-call scratch only
+    struct Mark { size_t cur, off; };
+    Mark mark() const { return Mark{cur, off}; }
+    void rewind(const Mark &m) { cur = m.cur; off = m.off; }
     void *alloc(size_t bytes)
     {
         bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
@@ -23,6 +30,7 @@ struct GNN_INTERNAL gnn_train_arena {
             if (off + bytes <= slabs[cur].size) {
                 void *r = slabs[cur].p + off;
                 off += bytes;
+                note_peak();
                 return r;
             }
         Slab s{nullptr, std::max<size_t>(bytes, (size_t)32 << 20)};
@@ -30,7 +38,15 @@ struct GNN_INTERNAL gnn_train_arena {
         slabs.push_back(s);
         cur = slabs.size() - 1;
         off = bytes;
+        note_peak();
         return s.p;
+    }
+    size_t peak = 0;              // most bytes in use since the last reset(): the slabs in front of the current one and its filled part
+    void note_peak()
+    {
+        size_t used = off;
+        for (size_t i = 0; i < cur; ++i) used += slabs[i].size;
+        peak = std::max(peak, used);
     }
     struct Pinned {               // grow-only pinned host buffer
         void *p = nullptr;
@@ -48,6 +64,7 @@ struct GNN_INTERNAL gnn_train_arena {
         ~Pinned() { if (p) (void)hipHostFree(p); }
     };
     Pinned host;                  // pinned host words for the results the host waits for (iteration gates, loss partials)
+    Pinned gates;                 // pinned words for the gates of the adjoint iterations (the backward pass of gradient mode 1 waits for them while `host` holds the step's loss partials)
     Pinned stage;                 // pinned staging for the small per-step uploads (targets, sample weights, NodeGraph CSR): packed by the host, one transfer
     ~gnn_train_arena() { for (Slab &s : slabs) (void)hipFree(s.p); }
 };
@@ -197,6 +214,15 @@ struct StateGradJob {
     const int32_t *sip, *sdst;
     const float *sw;
     float *d_state;               // out: d loss / d state of the body's input
+    // adjoint iteration of the fixed-point gradient (g != NULL; gnn_train_adjoint.hip) instead: z_next[r] = g[r] + that sum, also written to
+    // `work` (the next net_backward call consumes its incoming gradient in place), with the gate of the iteration against z_prev:
+    // gate_prev closed (NULL: open) = the iteration has converged before, z_next = z_prev and no word is raised
+    const float *g = nullptr, *z_prev = nullptr;
+    float *z_next = nullptr, *work = nullptr;
+    float thr = 0.0f;
+    const int *gate_prev = nullptr;
+    int *gate = nullptr;
+    int *form_out = nullptr;      // receives the ADJ_GATHER_* form the gather took
 };
 
 // floats of a net's trainable arrays = of its gradient vector: dW1, db1, ..., dgamma, dbeta
@@ -294,12 +320,56 @@ int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float 
               int64_t rows, bool producer_dropout);
 int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, const MaskStream &rng, NetCache &c, float **y_out,
                 gnn_comm *comm = nullptr, const InputBuild *build = nullptr);
+// wgrad = false: d x alone (no weight-gradient tiles or kernels, no sum of the chunk partials; net.grads and net.part are not touched)
 int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job = nullptr,
-                 gnn_comm *comm = nullptr, int64_t n_global = 0);
+                 gnn_comm *comm = nullptr, int64_t n_global = 0, bool wgrad = true);
 // the form net_setup decided, as the ints of gnn_train_forms (include/gnn_hip.h): out[3 + 3 n_layers]
 void net_forms(const Net &net, int *out);
 // out[t] += part[0][t] + ... + part[parts - 1][t], t < count (k_sum_parts)
 int net_sum_parts(hipStream_t st, int parts, int64_t count, const float *part, float *out);
+
+// gnn_train_adjoint.hip: the gradient at the fixed point (include/gnn_hip.h, gnn_loop_set_gradient_mode)
+enum { ADJ_GATHER_GENERIC = 0, ADJ_GATHER_ROWS = 1, ADJ_GATHER_ROWS_ALIGNED = 2, ADJ_GATHER_NARROW = 3 };
+// state rows of whole 16-byte pieces, at most 16 of them: 16 lanes per row take four columns each (else: every 16th column)
+inline bool adjoint_rows16(int Ds) { return (Ds & 3) == 0 && Ds <= 64; }
+// why a net_state cannot take gradient mode 1 (0: it can): 1 BatchNormalization, 2 a Dropout rate != 0
+inline int adjoint_refusal(const gnn_mlp *m, const float *rates)
+{
+    if (m->has_bn) return 1;
+    for (int l = 0; l <= m->n_layers; ++l) if (rates[l] != 0.0f) return 2;
+    return 0;
+}
+// the gather of one adjoint iteration (job.g != NULL) from u = d inp [n, in_s], or (aligned) from the dsg rows [n, 2 Ds] k_bwd3_split left;
+// returns the ADJ_GATHER_* form it took through *form (may be NULL)
+int launch_adjoint_gather(hipStream_t st, const StateGradJob &job, const float *u, bool aligned, int *form);
+
+// One launch per adjoint iteration for narrow nets (k_adjoint_narrow): a block owns ADJ_NARROW_ROWS rows, forms z_L of them by the gather from the
+// PREVIOUS launch's u (with the gate of iteration L - 1), then runs the whole chain d z -> . W^T (.) act'(a) -> ... down to the own-state and
+// aggregated-state columns of d concat, u_L [n, 2 Ds].  Why a net does not take it (0: it does): 3 more than three Dense layers, 4 a layer wider
+// than 64, 5 a concat wider than 96, 6 4,096 rows or more (or none), 7 a softmax in net_state.
+constexpr int ADJ_NARROW_ROWS = 16, ADJ_NARROW_MAXW = 64, ADJ_NARROW_MAXIN = 96;
+inline int adjoint_narrow_why(const gnn_mlp *m, int64_t n)
+{
+    if (m->n_layers > 3) return 3;
+    for (int l = 1; l <= m->n_layers; ++l) if (m->dims[l] > ADJ_NARROW_MAXW) return 4;
+    if (m->dims[0] > ADJ_NARROW_MAXIN) return 5;
+    if (n < 1 || !(n < 4096)) return 6;
+    for (int l = 0; l < m->n_layers; ++l) if (m->acts[l] == GNN_ACT_SOFTMAX) return 7;
+    return 0;
+}
+struct AdjNarrow {
+    int64_t n;
+    int Ds, c_aggs, L, gather;    // gather: form z_L from u_prev / z_prev / g and evaluate the gate (else z_L is read from z_cur)
+    int dims[4], acts[3];
+    const float *WT[3], *a[3];
+    const int32_t *sip, *sdst;
+    const float *sw, *g, *z_prev, *u_prev;
+    float *z_cur, *u_out;
+    float thr;
+    const int *gate_prev;
+    int *gate;
+};
+int launch_adjoint_narrow(hipStream_t st, const AdjNarrow &p);
 
 }   // namespace gnn_train
 
@@ -313,6 +383,7 @@ struct GNN_INTERNAL gnn_train_ctx {
     float *d_sw = nullptr;
     float *state = nullptr, *out_nodes = nullptr;
     int k = 0;
+    bool fixed_point = false;     // gradient mode 1: `caches` holds ONE recorded body at the converged state `state` (k bodies of the inference Loop led there)
     bool persistent = false;      // the bodies ran in the persistent launch (k_train_small) ...
     int workgroups = 0, barriers = 0;     // ... of that many workgroups, with that many grid barriers per body
     int64_t N = 0, M = 0;

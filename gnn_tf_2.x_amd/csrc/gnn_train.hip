@@ -798,6 +798,17 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     int rc;
     HIPCHK(hipSetDevice(l->device));
     hipStream_t st = l->stream;
+    // Gradient mode 1 (the gradient at the fixed point, include/gnn_hip.h): the bodies are those of the INFERENCE Loop, with the loop's own
+    // arithmetic and launch form; what follows records one training-mode body at the state it converged to.
+    const bool fixed_point = l->train.adjoint.mode != 0;
+    float k_inference = 0.0f;
+    if (fixed_point) {
+        if (sharded) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient is single-GPU");
+        const int why = adjoint_refusal(l->st, dropout_state);
+        if (why) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient needs a net_state whose training-mode forward is the inference forward: this one has %s",
+                                 why == 1 ? "a BatchNormalization" : "a Dropout rate != 0");
+        if ((rc = gnn_loop_run(l, 0, &k_inference))) return rc;
+    }
     if (!l->graph_ready_seen) {      // creation-time fills of a derived graph's labels come before their first read (gnn_graph_wait_ready)
         if ((rc = gnn_graph_wait_ready(g, st))) return rc;
         l->graph_ready_seen = true;
@@ -812,7 +823,8 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     Forward f{l, cx, st, sharded, sharded ? l->comm : nullptr, N, M, sharded ? (size_t)l->own_off : 0, dropout_state, seed};
     // everything the step needs zeroed, in one block and one memset: gradients and BatchNormalization statistics of both nets, the
     // iteration gates, the template of the concat
-    const int max_iter = l->max_iter;
+    // (mode 1 records ONE body whatever max_iter is: one gate block - never read - and one call of net_state)
+    const int max_iter = fixed_point ? 1 : l->max_iter;
     f.flag_words = (size_t)(max_iter + 1) * GNN_FLAG_WORDS;
     const size_t z_s = net_zero_floats(l->st, max_iter), z_o = net_zero_floats(l->ou, 1), z_f = (f.flag_words + 63) & ~(size_t)63;
     const size_t z_total = z_s + z_o + z_f + (size_t)N * l->in_s;
@@ -829,7 +841,7 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     // ---- while condition: state <- net_state(concat), training mode (GNN.py:271 with training=True) ----------------------
     // small batches: every body in ONE persistent launch (decided once per forward, here beside net_setup); else launch by launch
     SmallTrainForm pf;
-    if (allow_persistent && !sharded && (rc = train_persistent_decide(l, cx->ns, &pf))) return rc;
+    if (allow_persistent && !sharded && !fixed_point && (rc = train_persistent_decide(l, cx->ns, &pf))) return rc;
     f.hflags = static_cast<int *>(arena->host.get(std::max<size_t>(sizeof(int) * f.flag_words, 4096)));
     if (!f.hflags) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
     if (sharded && l->D) {
@@ -839,15 +851,28 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     } else
         f.states.push_back(const_cast<float *>(l->D ? l->state_init : g->nodes));      // (D == 0: the node labels, a replica already)
     int k = 0;
-    if (pf.ok) {
-        if ((rc = f.bodies_persistent(pf, &k, gave_up))) return rc;
-        if (*gave_up) return GNN_OK;
-    } else if ((rc = f.bodies_by_launch(&k)))
-        return rc;
-    cx->state = f.states[(size_t)k];
+    if (fixed_point) {
+        // p = the state after the k bodies of the inference Loop, copied out of the loop's tables (publish() below rewrites them); the recorded
+        // body reads p, its gate block and its output state are not used
+        float *p = nullptr;
+        if ((rc = buf.get(&p, (size_t)std::max<int64_t>(N, 1) * l->Ds))) return rc;
+        k = (int)k_inference;
+        if (N) HIPCHK(hipMemcpyAsync(p, gnn_loop_state_after(l, l->kfinal, 0), sizeof(float) * (size_t)N * l->Ds, hipMemcpyDeviceToDevice, st));
+        f.states[0] = p;
+        if ((rc = f.enqueue_body(0))) return rc;
+        cx->fixed_point = true;
+        cx->state = p;
+    } else {
+        if (pf.ok) {
+            if ((rc = f.bodies_persistent(pf, &k, gave_up))) return rc;
+            if (*gave_up) return GNN_OK;
+        } else if ((rc = f.bodies_by_launch(&k)))
+            return rc;
+        cx->state = f.states[(size_t)k];
+        l->train.k_hint = k;
+    }
     if ((rc = f.output(cx->state))) return rc;
     cx->k = k;
-    l->train.k_hint = k;
     if ((rc = f.publish(cx->state, out_nodes_host, final_sync))) return rc;
     *k_out = (float)k;
     return GNN_OK;
@@ -914,6 +939,96 @@ extern "C" int gnn_loop_train_forward(gnn_loop *l, const int32_t *src_indptr, co
                          out_nodes_host, true);
 }
 
+// Gradient mode 1 behind net_output's backward pass: g = d loss / d p (d_state, left intact) -> z_final by the adjoint iteration
+// z_0 = g, z_{t+1} = g + J^T z_t on the ONE recorded body (cx->caches[0]), then that body's weight gradients for the incoming gradient z_final.
+// An iteration = net_backward without weight gradients + the gather of gnn_train_adjoint.hip, which writes z_{t+1} twice (z buffer (t + 1) & 1
+// and `work`, which the next net_backward consumes in place) and raises gate t when a node moved.  The iterations are enqueued TRAIN_CHUNK at
+// a time on scratch that every iteration reuses; the host then reads the chunk's gates in one wait.  Iteration t finds gate t - 1 of its
+// chunk on the device: behind a closed gate it hands z on unchanged and raises nothing, so the first closed gate gives the count and the
+// last buffer written holds z of that count - nothing is recomputed.
+static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, float *g_state)
+{
+    gnn_train_arena *arena = cx->buf.arena;
+    Buf &buf = cx->buf;
+    Net &ns = cx->ns;
+    auto &adj = l->train.adjoint;
+    const int64_t N = cx->N;
+    const int Ds = l->Ds;
+    const int t_max = adj.max_iter > 0 ? adj.max_iter : l->max_iter;
+    const float thr = adj.thr >= 0.0f ? adj.thr : l->thr;
+    const size_t zf = (size_t)std::max<int64_t>(N, 1) * Ds;
+    int rc;
+    // the first look at the gates comes behind as many iterations as the loop's last step ran, plus one (as k_hint for the forward's bodies:
+    // a batch's count moves slowly from step to step, and every look is a wait for the device)
+    const int first_chunk = adj.iterations >= TRAIN_CHUNK ? std::min(t_max, adj.iterations + 1) : TRAIN_CHUNK;
+    const size_t gate_blocks = (size_t)std::max(first_chunk, (int)TRAIN_CHUNK);
+    adj.iterations = 0; adj.converged = 1;
+    adj.gather = adjoint_rows16(Ds) ? ADJ_GATHER_ROWS : ADJ_GATHER_GENERIC;       // (without an iteration; else what the launches report)
+    // narrow nets: one launch per iteration (k_adjoint_narrow), decided once per step; mode 2 keeps to the per-kernel chain
+    const bool narrow = adj.mode == 1 && adjoint_narrow_why(ns.m, N) == 0;
+    if (cx->caches.size() != 1) return gnn_fail(GNN_ERR_STATE, "internal: the fixed-point gradient needs one recorded body, not %zu", cx->caches.size());
+    float *zb[2] = {nullptr, nullptr}, *work = nullptr;
+    int *gates = nullptr;
+    if ((rc = buf.get(&zb[0], zf)) || (rc = buf.get(&zb[1], zf)) || (rc = buf.get(&work, zf)) || (rc = buf.get(&gates, gate_blocks * GNN_FLAG_WORDS))) return rc;
+    // (not arena->host: gnn_loop_train_step has this step's loss partials on their way into it)
+    int *hgates = static_cast<int *>(arena->gates.get(sizeof(int) * gate_blocks * GNN_FLAG_WORDS));
+    if (!hgates) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
+    if (N) HIPCHK(hipMemcpyAsync(work, g_state, sizeof(float) * (size_t)N * Ds, hipMemcpyDeviceToDevice, st));
+    if (N > 0 && t_max > 0) adj.converged = 0;
+    float *ub[2] = {nullptr, nullptr};             // narrow form: u of launch L, [N, 2 Ds] = [own-state columns | aggregated-state columns] of d concat
+    if (narrow && ((rc = buf.get(&ub[0], 2 * zf)) || (rc = buf.get(&ub[1], 2 * zf)))) return rc;
+    const gnn_train_arena::Mark mark = arena->mark();
+    for (int t = 0; N > 0 && t < t_max && !adj.converged;) {
+        const int t0 = t, t1 = std::min(t_max, t0 + (t0 == 0 ? first_chunk : (int)TRAIN_CHUNK));
+        HIPCHK(hipMemsetAsync(gates, 0, sizeof(int) * (size_t)(t1 - t0) * GNN_FLAG_WORDS, st));
+        auto gate_of = [&](int it) { return it >= t0 ? gates + (size_t)(it - t0) * GNN_FLAG_WORDS : (int *)nullptr; };     // gate of iteration `it` (z_{it+1} against z_it) of this chunk
+        auto z_of = [&](int it) { return it == 0 ? g_state : zb[it & 1]; };
+        if (narrow) {
+            // Launch L forms z_L from launch L - 1's u (gate L - 1) and leaves u_L; the chunk's first launch finds z_{t0} formed (g, or the gather
+            // that closed the chunk before), and one gather of the ordinary kind closes the chunk: z_{t1}, gate t1 - 1, `work`.
+            const gnn_mlp *m = ns.m;
+            const NetCache &c = cx->caches[0];
+            for (; t < t1; ++t) {
+                AdjNarrow p{};
+                p.n = N; p.Ds = Ds; p.c_aggs = Ds + l->NLc; p.L = m->n_layers; p.gather = t > t0;
+                for (int q = 0; q <= m->n_layers; ++q) p.dims[q] = m->dims[q];
+                for (int q = 0; q < m->n_layers; ++q) { p.acts[q] = m->acts[q]; p.WT[q] = ns.WT[q]; p.a[q] = c.a[q]; }
+                p.sip = cx->d_sip; p.sdst = cx->d_sdst; p.sw = cx->d_sw;
+                p.g = g_state; p.z_prev = t > 0 ? z_of(t - 1) : nullptr; p.u_prev = ub[(t + 1) & 1]; p.z_cur = z_of(t); p.u_out = ub[t & 1];
+                p.thr = thr; p.gate_prev = gate_of(t - 2); p.gate = gate_of(t - 1);
+                if ((rc = launch_adjoint_narrow(st, p))) return rc;
+            }
+            StateGradJob job{N, Ds, 2 * Ds, Ds, cx->d_sip, cx->d_sdst, cx->d_sw, nullptr};
+            job.g = g_state; job.z_prev = z_of(t1 - 1); job.z_next = zb[t1 & 1]; job.work = work; job.thr = thr;
+            job.gate_prev = gate_of(t1 - 2); job.gate = gate_of(t1 - 1);
+            if ((rc = launch_adjoint_gather(st, job, ub[(t1 - 1) & 1], false, nullptr))) return rc;
+            adj.gather = ADJ_GATHER_NARROW;
+        }
+        for (; t < t1; ++t) {
+            arena->rewind(mark);
+            StateGradJob job{N, Ds, l->in_s, Ds + l->NLc, cx->d_sip, cx->d_sdst, cx->d_sw, nullptr};
+            job.g = g_state; job.z_prev = t == 0 ? g_state : zb[t & 1]; job.z_next = zb[(t + 1) & 1]; job.work = work; job.thr = thr;
+            job.gate_prev = t > t0 ? gates + (size_t)(t - t0 - 1) * GNN_FLAG_WORDS : nullptr;
+            job.gate = gates + (size_t)(t - t0) * GNN_FLAG_WORDS;
+            job.form_out = &adj.gather;
+            float *u = nullptr;
+            if ((rc = net_backward(st, buf, ns, cx->caches[0], work, &u, &job, nullptr, 0, false))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(hgates, gates, sizeof(int) * (size_t)(t1 - t0) * GNN_FLAG_WORDS, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        adj.iterations = t1;
+        for (int i = 0; i < t1 - t0; ++i) {
+            int any = 0;
+            for (int w = 0; w < GNN_FLAG_WORDS; w += GNN_FLAG_STRIDE) any |= hgates[(size_t)i * GNN_FLAG_WORDS + w];
+            if (!any) { adj.iterations = t0 + i + 1; adj.converged = 1; break; }
+        }
+    }
+    arena->rewind(mark);
+    // `work` holds z_final (the last gather wrote it beside its z buffer; without an iteration it is the copy of g)
+    float *u = nullptr;
+    return net_backward(st, buf, ns, cx->caches[0], work, &u, nullptr, nullptr, 0, true);
+}
+
 // d_out_dev: d loss / d out_nodes already on the device (gnn_loop_train_step), else d_out_host is uploaded
 static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host, const float *d_state_extra, float *grads_state,
                           float *grads_output, float *bn_batch_state, float *bn_batch_output, float *d_nodes_host, float *d_arcs_host, bool sync)
@@ -931,9 +1046,12 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
         ARGCHK(cx->d_sip, "backward on shards: gnn_loop_train_forward needs the by-source adjacency of the owned rows (src_indptr / src_dst / src_w)");
         ARGCHK(!d_state_extra && !d_nodes_host && !d_arcs_host && !l->edge_mode, "backward on shards: no extra state gradient, label or arc-label gradients, node- or graph-based only");
     }
+    if (cx->fixed_point && (d_nodes_host || d_arcs_host))
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient returns no d_nodes / d_arc_labels (the joint LGNN modes need the unrolled gradient)");
     gnn_graph *g = l->g;
     const int64_t N = g->n_rows, M = l->edge_mode ? l->n_edge_masked : g->n_masked;
-    const int Ds = l->Ds, NLc = l->NLc, in_s = l->in_s, T = l->T, wf = l->ou->dims[0], NL = g->NL, k = cx->k;
+    // (mode 1: cx->k bodies of the inference Loop led to the state; the backward pass below walks none of them)
+    const int Ds = l->Ds, NLc = l->NLc, in_s = l->in_s, T = l->T, wf = l->ou->dims[0], NL = g->NL, k = cx->fixed_point ? 0 : cx->k;
     ARGCHK(M == 0 || d_out_dev || d_out_host, "d_out_nodes is NULL");
     HIPCHK(hipSetDevice(l->device));
     hipStream_t st = l->stream;
@@ -983,6 +1101,7 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
             HIPCHK(hipGetLastError());
         }
     }
+    if (cx->fixed_point && (rc = adjoint_backward(l, cx, st, d_state))) return rc;
     for (int it = k - 1; it >= 0; --it) {
         // net_backward consumes d_state (d loss / d state_{it+1}) in place; its last launch also writes d loss / d state_it into a new buffer
         float *d_inp = nullptr, *d_prev = nullptr;
@@ -1158,7 +1277,8 @@ extern "C" int gnn_loop_train_step(gnn_loop *l, const int32_t *src_indptr, const
     if (l->train.opt.armed) {                      // gnn_loop_arm_optimizer: the update rides on this step's stream work
         const auto &opt = l->train.opt;
         l->train.opt.armed = false;
-        const float gscale = (opt.mean && cx->k > 0) ? 1.0f / (float)cx->k : 1.0f;
+        // (mode 1: net_state's gradients are no sum over bodies, `mean` has nothing to average)
+        const float gscale = (opt.mean && cx->k > 0 && !cx->fixed_point) ? 1.0f / (float)cx->k : 1.0f;
         if ((rc = update_both(l, cx, st, opt.kind, opt.h, gscale, opt.mom_s, opt.mom_o, true, 1.0))) return rc;
         cx->applied = true;
     }

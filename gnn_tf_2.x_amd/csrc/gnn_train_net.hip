@@ -726,8 +726,10 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
 // d loss / d x ([n, dims[0]]); weight gradients are ADDED into net.grads (one sum over the call's chunk partials)
 // comm != NULL (sharded backward, one process per rank): the sums of BatchNormalization's backward pass are those of the rows of ALL
 // ranks (n_global of them); the weight gradients stay this rank's share (train_backward adds the shares up at the end).
+// wgrad = false (an adjoint iteration of the fixed-point gradient, gnn_train_adjoint.hip): d x alone - after the chain no weight-gradient
+// kernel, of a wide layer only the product with W^T, of k_layer_bwd only its row blocks, and no sum of the chunk partials.
 int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job,
-                 gnn_comm *comm, int64_t n_global)
+                 gnn_comm *comm, int64_t n_global, bool wgrad)
 {
     const gnn_mlp *m = net.m;
     const int L = m->n_layers;
@@ -746,7 +748,8 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
     }
     const int64_t rpb = rows_per_block(n);
     const int parts = (int)cdiv(n, rpb);
-    if (net.part_rows != n) {
+    if (!wgrad && m->has_bn) return gnn_fail(GNN_ERR_STATE, "internal: an input-gradient-only backward pass through BatchNormalization");
+    if (wgrad && net.part_rows != n) {
         if ((rc = buf.get(&net.part, (size_t)parts * net.g_total))) return rc;
         net.part_rows = n;
     }
@@ -799,7 +802,7 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
         if (job && job->N == n && state_rows16(job->Ds, job->N) && job->in_s == m->dims[0] && (rc = buf.get(&dsg, (size_t)n * 2 * job->Ds))) return rc;
         if ((rc = launch_bwd3(st, buf, m, net.WT.data(), n, d, c.a[1], c.a[0], dz1, dz0, dinp, dsg, job ? job->Ds : 0, job ? job->c_aggs : 0))) return rc;
         const float *dzs[3] = {dz0, dz1, d};
-        for (int l = 2; l >= 0; --l)
+        for (int l = 2; l >= 0 && wgrad; --l)
             if ((rc = launch_wgrad_f32(st, n, rpb, parts, ps, m->dims[l], m->dims[l + 1], c.hin[l], dzs[l], net.part + net.g_off[2 * l]))) return rc;
         d = dinp;
     }
@@ -811,7 +814,7 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
         const int act_prev = l > 0 ? m->acts[l - 1] : -1;
         const bool prev_sm = act_prev == GNN_ACT_SOFTMAX;
         if (net.wide_bwd[l]) {                     // both products of a wide layer on the matrix cores
-            if ((rc = launch_wgrad_f32(st, n, rpb, parts, ps, ni, no, c.hin[l], d, net.part + net.g_off[2 * l]))) return rc;
+            if (wgrad && (rc = launch_wgrad_f32(st, n, rpb, parts, ps, ni, no, c.hin[l], d, net.part + net.g_off[2 * l]))) return rc;
             if ((rc = launch_gemm_f32(st, buf, n, no, ni, d, net.WT[l], nullptr, act_prev, 1, net.rate[l] != 0.0f ? c.keep[l] : nullptr, net.rate[l],
                                       l > 0 ? c.a[l - 1] : nullptr, dprev))) return rc;
             d = dprev;
@@ -821,11 +824,11 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
         LayerBwd p;
         p.n = n; p.rows_per_block = rpb; p.pstride = ps;
         p.n_in = ni; p.n_out = no; p.n_out_pad = (no + 3) & ~3; p.act = prev_sm ? -1 : act_prev;
-        p.wg_bx = (int)cdiv(ni + 1, GNN_WG_TILE); p.wg_by = (int)cdiv(no, GNN_WG_TILE); p.wg_blocks = p.wg_bx * p.wg_by * parts;
+        p.wg_bx = (int)cdiv(ni + 1, GNN_WG_TILE); p.wg_by = (int)cdiv(no, GNN_WG_TILE); p.wg_blocks = wgrad ? p.wg_bx * p.wg_by * parts : 0;
         p.rate = net.rate[l];
         p.H = c.hin[l]; p.DZ = d; p.WT = net.WT[l]; p.a_prev = l > 0 ? c.a[l - 1] : nullptr;
         p.keep = net.rate[l] != 0.0f ? c.keep[l] : nullptr;
-        p.part = net.part + net.g_off[2 * l]; p.dprev = dprev;
+        p.part = wgrad ? net.part + net.g_off[2 * l] : nullptr; p.dprev = dprev;
         p.cshift = dense_cshift(ni);
         const size_t lds = std::max(dense_lds_bytes(R, p.n_out_pad), sizeof(float) * 2 * 64 * GNN_WG_LD);
         if (lds > 64 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "layer width %d too large", no);
@@ -835,7 +838,12 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
         d = dprev;
     }
     const unsigned sum_blocks = cdiv((int64_t)net.g_total, 64);
-    if (job && dsg) {
+    if (job && job->g) {                           // an adjoint iteration: z_next = g + the state gradient, with the iteration's gate
+        if (wgrad) return gnn_fail(GNN_ERR_STATE, "internal: an adjoint iteration takes no weight gradients");
+        if ((rc = launch_adjoint_gather(st, *job, dsg ? dsg : d, dsg != nullptr, job->form_out))) return rc;
+    } else if (!wgrad) {
+        if (job) return gnn_fail(GNN_ERR_STATE, "internal: a state gradient without weight gradients is an adjoint iteration");
+    } else if (job && dsg) {
         hipLaunchKernelGGL(k_state_grad_rows_al, cdiv(job->N * 16, 256), 256, 0, st, job->N, job->Ds, dsg, job->sip, job->sdst, job->sw, job->d_state);
         hipLaunchKernelGGL(k_sum_parts, sum_blocks, 256, 0, st, parts, (int64_t)net.g_total, net.part, net.grads);
     } else if (job && state_rows16(job->Ds, job->N)) {

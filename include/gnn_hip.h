@@ -220,6 +220,50 @@ int gnn_loop_train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t
 int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, const float *d_state_extra, float *grads_state,
                             float *grads_output, float *bn_batch_state, float *bn_batch_output, float *d_nodes,
                             float *d_arc_labels);
+/* Gradient mode of a loop's training step.  mode 0 (default): back-propagation through the unrolled loop, as described above.
+ * mode 1 ("fixed point"): the gradient at the converged state (Almeida-Pineda; Scarselli et al. 2009, section III).  With Ds the state width:
+ *   Forward        the INFERENCE Loop runs with the loop's own settings (arithmetic, persistent or per-body form, certified gate) and gives
+ *                  k and p = x_k, the state after k bodies.
+ *   Recorded body  ONE training-mode body of net_state at p (the concat and the forward of mode 0); its output state is discarded.  The
+ *                  step's scratch holds one body's activations whatever max_iter is.
+ *   Outputs, loss  unchanged: training-mode net_output on the rows of p (Dropout, BatchNormalization, moving statistics, graph and edge
+ *                  readouts), published as the loop's result like those of mode 0.
+ *   g              d loss / d p as mode 0 builds it (d_state_extra included).
+ *   Adjoint        z_0 = g, z_{t+1} = g + J^T z_t; J = d body / d state at p over the own-state columns of the concat AND the aggregated-
+ *                  state columns through the adjacency by source:  z_{t+1}[r] = g[r] + (u[r, :Ds] + sum over the arcs r -> dst, in stored
+ *                  order, of w u[dst, c_aggs : c_aggs + Ds]),  u = d concat of the recorded body for the incoming gradient z_t.  It stops after
+ *                  iteration t + 1 when NO node has |z_{t+1}[r] - z_t[r]| > theta_adj |z_t[r]| (L2 over the row, strict '>': the rule of the
+ *                  forward condition; a zero row that stays zero does not move), or after adjoint_max_iter iterations.  Not converging is not
+ *                  an error: the truncated sum is returned, and gnn_loop_adjoint_info reports it.  The host reads the gates once per five
+ *                  iterations; an iteration queued behind a closed gate sees that gate on the device, hands z on unchanged and raises
+ *                  nothing, so the count - the first closed gate - decides what is returned, and nothing is computed twice.
+ *   net_state gradients   ONE weight-gradient pass of the recorded body with incoming gradient z_final.  They are NOT a sum over bodies:
+ *                  a caller that averages (`mean`) must NOT divide them by k, and a step armed with mean != 0 applies them with scale 1.
+ *   Everything behind the gradients (regularizers, clipping, optimizer kinds, net_output's moving statistics) is untouched.
+ * Refused with GNN_ERR_UNSUPPORTED by the training forward / step / backward of a loop in mode 1: a net_state with BatchNormalization or any
+ * Dropout rate != 0 (its training-mode forward is then not the inference forward), world > 1, and requests for d_nodes / d_arc_labels.
+ * No float atomics: two identical steps return identical bits.
+ * Narrow nets (net_state of 1 - 3 Dense layers of at most 64 outputs, no softmax, a concat of at most 96 columns, fewer than 4,096 rows - the regime where
+ * a step is bound by its launch count) run an adjoint iteration as ONE launch: a block owns 16 rows, forms their z from the previous launch's u with
+ * the gate of the previous iteration, and runs the whole chain through W^T with the weights staged in LDS (same sums, float32 fmaf).  mode 2 is mode 1
+ * without that form (the per-kernel chain everywhere): for A/B runs and tests.
+ * adjoint_max_iter = 0 / adjoint_threshold < 0: the loop's own max_iter / threshold.  *used (may be NULL) = the mode now set.
+ * gnn_loop_adjoint_info: iterations and converged (0 / 1) of the last backward pass of mode 1, and the form of its gather (0: any Ds, every
+ * 16th column per lane; 1: 16-byte pieces, Ds % 4 == 0 and Ds <= 64; 2: the same from the aligned rows the three-layer chain leaves; 3: inside the
+ * one-launch iteration of narrow nets);
+ * any pointer may be NULL. */
+int gnn_loop_set_gradient_mode(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int *used);
+int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *converged, int *form);
+/* What an adjoint iteration of mode 1 launches for a net_state of this description (arguments as gnn_train_forms; the state width is
+ * the net's last width) on n_rows rows - host code, no device, the decision the step itself takes.  out receives 4 + n_layers ints: out[0] = 1
+ * eligible / 0 refused; out[1] = reason of a refusal (1 BatchNormalization - pass has_bn, 2 a Dropout rate != 0; 0 otherwise);
+ * out[2] = gather form as gnn_loop_adjoint_info; out[3 + l] = backward form of Dense layer l (GNN_FORM_PER_OP: the row blocks of
+ * k_layer_bwd alone, GNN_FORM_WIDE, GNN_FORM_CHAIN3, or GNN_FORM_ADJ_NARROW for every layer); no weight-gradient kernel runs in an iteration;
+ * out[3 + n_layers] = why the one-launch iteration of narrow nets is NOT taken (0: it is; 3 more than three layers, 4 a layer wider than 64, 5 a concat
+ * wider than 96, 6 4,096 rows or more, or none, 7 a softmax in net_state). */
+int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int64_t n_rows, int *out);
+/* Bytes handed out from the step's scratch by the last training forward / backward of this loop (test entry point). */
+int gnn_loop_train_arena_bytes(const gnn_loop *l, int64_t *bytes);
 /* Optimizer step on the device (reference GNN_BaseClass.py:243-247, optimizer.apply_gradients on the trainable variables of
  * both nets, and the moving statistics Keras BatchNormalization updates in training mode): weights, optimizer slots (kept with
  * the gnn_mlp) and gradients stay in HBM.  hyper is always four floats; per entry, in float32, on the gradient g after the
@@ -407,7 +451,8 @@ int gnn_graph_tile_schedule_info(const gnn_graph *g, int64_t *slots, int *kind, 
  * rates [n_layers + 1] in front of every Dense layer and of BatchNormalization; producer_dropout != 0: net_state (the concat kernel applies
  * the Dropout in front of the first layer), 0: net_output.  gnn_loop_train_forms: what the last gnn_loop_train_forward / gnn_loop_train_step
  * of this loop decided for net 0 (net_state) or 1 (net_output); GNN_ERR_STATE before the first one. */
-enum { GNN_FORM_PER_OP = 0, GNN_FORM_MLP_FWD = 1, GNN_FORM_WIDE = 2, GNN_FORM_CHAIN3 = 3, GNN_FORM_WGRAD_BF = 4, GNN_FORM_WGRAD_F32 = 5 };
+enum { GNN_FORM_PER_OP = 0, GNN_FORM_MLP_FWD = 1, GNN_FORM_WIDE = 2, GNN_FORM_CHAIN3 = 3, GNN_FORM_WGRAD_BF = 4, GNN_FORM_WGRAD_F32 = 5,
+       GNN_FORM_ADJ_NARROW = 6 /* gnn_adjoint_form only: inside the one-launch adjoint iteration of narrow nets */ };
 int gnn_train_forms(int n_layers, const int *dims, const int *acts, const float *rates, int64_t n_rows, int producer_dropout, int *out);
 int gnn_loop_train_forms(const gnn_loop *l, int net, int *out);
 /* Small batches on a single GPU run the training-mode forward of ALL bodies of net_state - the `while` of gnn_loop_train_forward /
