@@ -162,18 +162,18 @@ struct LoopForm {
     // persistent path: 16- or 32-node tiles, the instantiated layer-0 K-step count (kk_small of k_small_loop / s0 of k_small16), and
     // whether the output stage and the graph readout run inside the launch; ctl holds everything but the run-parity gate words
     int small_tile = 0, kk_small = 0, s0 = 0;
-    bool small_wide = false;         // 16-node tiles with hidden layers up to 64 wide (k_small16w) rather than k_small16
+    bool small_wide = false;         // 16-node tiles with hidden layers up to 64 wide (k_small16 with WIDE)
     bool fold_output = false, fold_readout = false;
     GnnSmallCtl ctl;
 };
 
 // LDS layout of the persistent small-graph loop (gnn_small_common.h), in 4-byte words, for ROWS = 32 (k_small_loop) or 16 (k_small16, and
-// with WIDE k_small16w: hidden layers up to 64 wide) rows per tile: the tile [ROWS][KP] at the start of the dynamic allocation, everything
+// with WIDE its form for hidden layers up to 64 wide) rows per tile: the tile [ROWS][KP] at the start of the dynamic allocation, everything
 // else at the constant offsets below from the tile's end.  The kernels carve their pointers from it; the host sizes the allocation with
 // bytes(KP).
 constexpr int GNN_SMALL_ECACHE = 1024;             // arcs of a tile whose ids / weights are kept in LDS
 constexpr int GNN_SMALL16_HP = 36;                 // row stride of k_small16's hidden-activation copy (floats): 16-byte rows, (4 n + g) banks
-// Row stride of k_small16w's 64-feature hidden-activation copy (floats).  Lane (n = lane % 16, g = lane / 16) reads its B operand of K-step
+// Row stride of the wide k_small16's 64-feature hidden-activation copy (floats).  Lane (n = lane % 16, g = lane / 16) reads its B operand of K-step
 // s from word 66 n + g + 4 s with ds_read_b32, whose bank is the word address mod 32 and whose conflict groups are the two 32-lane halves
 // (g in {0, 1} and g in {2, 3}): 66 n + g = 2 n + g (mod 32) takes every value 0 .. 31 (2 .. 33) exactly once over the 32 lanes of a half,
 // so a column read costs one LDS cycle per half.  64 + 4 would put nodes n and n + 8 on one bank.  Rows are 8-byte aligned: the copy is
@@ -183,7 +183,7 @@ template <int ROWS, bool WIDE = false>
 struct GnnSmallLds {
     static_assert(ROWS == 16 || ROWS == 32, "16- or 32-node tiles");
     static_assert(!WIDE || ROWS == 16, "the wide form works on 16-node tiles");
-    static constexpr int H = 0;                                         // k_small16 / k_small16w: hidden activations [16][GNN_SMALL16_HP / GNN_SMALL16W_HP]
+    static constexpr int H = 0;                                         // k_small16: hidden activations [16][GNN_SMALL16_HP / GNN_SMALL16W_HP]
     static constexpr int IPT = ROWS == 16 ? 16 * (WIDE ? GNN_SMALL16W_HP : GNN_SMALL16_HP) : 32;   // row pointers [ROWS + 1] (+3); k_small_loop: behind 32 words of slack
     static constexpr int EP = IPT + ROWS + 4;                           // last-layer bias, BatchNormalization scale / shift [3][32]
     static constexpr int HBW = WIDE ? 64 : 32;                          // floats per hidden layer's bias
@@ -200,19 +200,13 @@ struct GnnSmallLds {
 // Instantiated K-step counts of layer 0 (the host picks the smallest that covers the concat width, the launcher dispatches on the same list)
 template <int... V> struct GnnSteps { static constexpr int values[] = {V...}; };
 using GnnSmallKK0 = GnnSteps<8, 12, 16, 24, 32, 36, 40, 48>;     // k_small_loop: K-steps of 2 (v_mfma_f32_32x32x2_f32)
-using GnnSmall16S0 = GnnSteps<4, 8, 12, 16, 20, 24>;             // k_small16, k_small16w: K-steps of 4 (v_mfma_f32_16x16x4_f32)
+using GnnSmall16S0 = GnnSteps<4, 8, 12, 16, 20, 24>;             // k_small16: K-steps of 4 (v_mfma_f32_16x16x4_f32)
 
-// false = no instantiation for (layers, act, kk0 / s0)
-bool gnn_small_launch(int layers, int act, int kk0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes,
-                      hipStream_t st);
-bool gnn_small16_launch(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
-// the same kernels for a net whose last layer has its own activation (a.act_last): gnn_small_m.hip, gnn_small16_m.hip; layers 2 or 3
-bool gnn_small_launch_mixed(int layers, int act, int kk0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes,
-                            hipStream_t st);
-bool gnn_small16_launch_mixed(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
-// 16-node tiles, hidden layers up to 64 wide (gnn_small16w_kernel.h; layers 2 or 3): gnn_small16w.hip, gnn_small16w_m.hip
-bool gnn_small16w_launch(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_small16w_launch_mixed(int layers, int act, int s0, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
+// One launcher per translation unit gnn_small{,16,16w}{,_m}.hip: 32-node tiles, 16-node tiles, 16-node tiles with hidden layers up to 64
+// wide (k_small16 with WIDE; layers 2 or 3); _mixed: the same kernels for a net whose last layer has its own activation (a.act_last;
+// layers 2 or 3).  steps: kk0 of k_small_loop / s0 of k_small16.  false = no instantiation for (layers, act, steps)
+typedef bool GnnSmallLaunch(int layers, int act, int steps, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
+GnnSmallLaunch gnn_small_launch, gnn_small_launch_mixed, gnn_small16_launch, gnn_small16_launch_mixed, gnn_small16w_launch, gnn_small16w_launch_mixed;
 
 // one per translation unit gnn_fused_l{1,2,3}.hip; false = no instantiation for (act, nt, ntl)
 bool gnn_fused_launch_l1(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);

@@ -128,7 +128,7 @@ size_t pair_lds_bytes(const FusedPlan &p)
 // The persistent small-graph launch (gnn_small_common.h) a net takes on n_rows owned rows, as far as the net and the row count decide it
 // (gnn_loop_decide_form adds what depends on the loop and the device: single GPU, not disabled, not profiling); m is covered by p.
 //   narrow: every layer one 32-feature tile - 16-node tiles (k_small16) up to 4,096 rows, 32-node tiles (k_small_loop) up to 8,192;
-//   wide:   two or three layers, every hidden layer <= 64 and at least one > 32, state <= 32 - 16-node tiles (k_small16w) up to 4,096 rows
+//   wide:   two or three layers, every hidden layer <= 64 and at least one > 32, state <= 32 - 16-node tiles (k_small16, WIDE) up to 4,096 rows
 //           (256 one-wave workgroups); there is no 32-node wide form, so a wide net on more rows takes one launch per body.
 // Both need the concat (layer-0 K) within 96 columns: the largest instantiated step count, 24 x 4 = 48 x 2.  From the net's real widths:
 // make_plan turns the tiles (NT, NTL) = (2, 1) of a wide net into (2, 2).
@@ -507,8 +507,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
 
-// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h,
-// gnn_small16w_kernel.h)
+// geometry and control block of the persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h)
 static int decide_persistent(gnn_loop *l, LoopForm &f, const SmallForm &sf)
 {
     const gnn_graph *g = l->g;
@@ -694,7 +693,7 @@ int gnn_fused_iteration(gnn_loop *l, int k)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h, gnn_small16w_kernel.h)
+// persistent small-graph loop (device code: gnn_small_common.h, gnn_small_kernel.h, gnn_small16_kernel.h)
 // ---------------------------------------------------------------------------------------------------------------------
 int gnn_small_run(gnn_loop *l)
 {
@@ -726,16 +725,11 @@ int gnn_small_run(gnn_loop *l)
         a.stamps = small_stamp_buf;
     }
 #endif
-    bool launched;
-    if (p.act_last != p.act)
-        launched = f.small_wide       ? gnn_small16w_launch_mixed(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                   : f.small_tile == 16 ? gnn_small16_launch_mixed(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                                        : gnn_small_launch_mixed(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
-    else
-        launched = f.small_wide       ? gnn_small16w_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                   : f.small_tile == 16 ? gnn_small16_launch(p.layers, p.act, f.s0, a, c, f.grid, f.lds, l->stream)
-                                        : gnn_small_launch(p.layers, p.act, f.kk_small, a, c, f.grid, f.lds, l->stream);
-    if (!launched)
+    static GnnSmallLaunch *const launchers[3][2] = {{gnn_small_launch, gnn_small_launch_mixed},            // [32 / 16 / 16 wide][mixed]
+                                                    {gnn_small16_launch, gnn_small16_launch_mixed},
+                                                    {gnn_small16w_launch, gnn_small16w_launch_mixed}};
+    const int tile_form = f.small_wide ? 2 : f.small_tile == 16 ? 1 : 0;
+    if (!launchers[tile_form][p.act_last != p.act](p.layers, p.act, tile_form ? f.s0 : f.kk_small, a, c, f.grid, f.lds, l->stream))
         return gnn_fail(GNN_ERR_UNSUPPORTED, "no persistent-loop instantiation for %d layers, activations %d / %d", p.layers, p.act, p.act_last);
     HIPCHK(hipGetLastError());
 #ifdef GNN_DIAG

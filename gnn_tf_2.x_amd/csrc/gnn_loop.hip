@@ -848,7 +848,7 @@ extern "C" int gnn_loop_run_many(gnn_loop **loops, int n, float *k_out /* [n] */
     // resident at once.  A launch's workgroup is one wave with 10 - 40 KB of LDS: at least four fit on a CU; launches are queued side by
     // side only while their workgroups sum to no more than three per CU, then the queued ones are collected before the next is queued
     // (the barrier's spin time-out stays as the safety net, it is no longer the mechanism).
-    // The wide form (k_small16w) keeps the rule: its largest instantiations allocate 256 VGPRs + up to 72 AGPRs of the SIMD's 512, so such
+    // The wide form of k_small16 keeps the rule: its largest instantiations allocate 256 VGPRs + up to 72 AGPRs of the SIMD's 512, so such
     // a wave is alone on its SIMD and a CU holds four of them - one more than the cap - and even if every narrow workgroup in flight took a
     // SIMD of its own, 3 x CUs workgroups leave each of them one of the 4 x CUs SIMDs.  LDS: at most 16 x 100 + 4,920 words = 26 KB per
     // wide workgroup, six per 160 KB.

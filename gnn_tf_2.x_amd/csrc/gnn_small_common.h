@@ -1,10 +1,9 @@
 // Shared phases of the persistent small-graph loop: ONE launch runs every body of a GNN.Loop (reference GNN/GNN.py:271, tf.while_loop
 // of condition :202-220 and convergence :223-242) when the batch is small enough for all of its tiles to be resident at once (BASELINE
-// configs[0] / [1]: a few hundred to a few thousand nodes, nets no wider than 32).  It has three forms that differ in the gather and the
-// dense layers only: k_small_loop on 32-node tiles (gnn_small_kernel.h), k_small16 on 16-node tiles (gnn_small16_kernel.h) and k_small16w on
-// 16-node tiles for hidden layers up to 64 wide (gnn_small16w_kernel.h); everything else is
-// here, templated on the rows per tile (ROWS = 32 or 16) where it depends on it, with the LDS layout (GnnSmallLds) and the instantiation
-// lists in gnn_fused.h.
+// configs[0] / [1]: a few hundred to a few thousand nodes, nets no wider than 32).  It has two kernels that differ in the
+// set-up of the tile and the dense layers only: k_small_loop on 32-node tiles (gnn_small_kernel.h) and k_small16 on 16-node tiles
+// (gnn_small16_kernel.h), the latter with a WIDE form for hidden layers up to 64 wide; everything else is here, templated on the rows
+// per tile (ROWS = 32 or 16) where it depends on it, with the LDS layout (GnnSmallLds) and the instantiation lists in gnn_fused.h.
 //
 // Such loops are latency bound: a body is one short chain of dependent loads and narrow MFMAs per tile, and as one launch per body it is
 // mostly launch gap, cold caches and host gating.  Here every tile is a one-wave workgroup that keeps its row pointers in LDS, its weights
@@ -82,7 +81,7 @@ __device__ __forceinline__ int arrive_and_gate(const GnnSmallCtl &c, int b, int 
 }
 
 // Start of the launch: the last-layer bias and BatchNormalization scale / shift (ep [3][32]), the biases of the hidden layers (hb [2][HBW],
-// HBW = 32 or, for k_small16w, 64 floats of the bias image, which is zero behind the layer's width) and, with the output stage folded in,
+// HBW = 32 or, for the wide k_small16, 64 floats of the bias image, which is zero behind the layer's width) and, with the output stage folded in,
 // the net_output head (hw: W [wf * T <= 512], then b | BN scale | BN shift [3][8]) into LDS
 template <int LAYERS, int HBW = 32>
 __device__ __forceinline__ void small_stage_vectors(const GnnFusedArgs &a0, const GnnSmallCtl &c, float *ep, float *hb, float *hw, int lane)
@@ -248,6 +247,40 @@ __device__ __forceinline__ void small_gather(__amdgpu_buffer_rsrc_t rs, float *X
         for (int c = 0; c < HW; ++c)
             if (part * HW + c < Ds) x[c] = acc[c];
     }
+}
+
+// the two exchange buffers xs[2][tiles * ROWS][DP] as buffer resources (16-byte sc1 loads / stores): body k gathers from rs[k & 1] and
+// publishes to the other
+template <int ROWS>
+__device__ __forceinline__ void small_exchange_rsrc(const GnnSmallCtl &c, __amdgpu_buffer_rsrc_t (&rs)[2])
+{
+    const int xs_bytes = (int)gridDim.x * ROWS * c.DP * 4;
+    rs[0] = __builtin_amdgcn_make_buffer_rsrc(c.xs, 0, xs_bytes, 0x00020000);
+    rs[1] = __builtin_amdgcn_make_buffer_rsrc(c.xs + (size_t)gridDim.x * ROWS * c.DP, 0, xs_bytes, 0x00020000);
+}
+
+// The gather instantiation of (c.DP, c.rnd), per tile size: HW = DP * ROWS / 64 floats per lane, c.rnd = 8 or 4 arcs per round (a 32-node
+// tile with 128-byte rows takes 4).  ec_src / ec_w: the tile's arcs in LDS when they are cached (small_cache_arcs), else nullptr - chosen
+// by the kernel, not here: with the choice inside this function the compiler tests it per arc instead of once per gather.
+__device__ __forceinline__ void small_gather16(const GnnFusedArgs &a0, const GnnSmallCtl &c, __amdgpu_buffer_rsrc_t rs, float *X, const int *ipt, int lane,
+                                               int nvalid, int KP, const int *ec_src, const float *ec_w, int e_base)
+{
+    const int c_aggs = a0.c_aggs, Ds = a0.Ds;
+    if (c.DP == 32) {
+        if (c.rnd == 8) small_gather<16, 8, 8>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
+        else small_gather<16, 8, 4>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
+    } else {
+        if (c.rnd == 8) small_gather<16, 4, 8>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
+        else small_gather<16, 4, 4>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
+    }
+}
+__device__ __forceinline__ void small_gather32(const GnnFusedArgs &a0, const GnnSmallCtl &c, __amdgpu_buffer_rsrc_t rs, float *X, const int *ipt, int lane,
+                                               int nvalid, int KP, const int *ec_src, const float *ec_w, int e_base)
+{
+    const int c_aggs = a0.c_aggs, Ds = a0.Ds;
+    if (c.DP == 32) small_gather<32, 16, 4>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
+    else if (c.rnd == 8) small_gather<32, 8, 8>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
+    else small_gather<32, 8, 4>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, ec_src, ec_w, e_base);
 }
 
 // The initial rows (staged in LDS as rows[nvalid][Ds]) -> exchange buffer 0, which body 0 gathers from behind gate 0; then the first

@@ -75,10 +75,8 @@ __global__ void __launch_bounds__(64) k_small_loop(const GnnFusedArgs a0, const 
     small_clear_next_words(c, lane);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     SMALL_STAMP();                                                   // 1: set-up loads issued (weights, row pointers)
-    // the two padded exchange buffers (see small_gather), as buffer resources: 16-byte sc1 loads / stores
-    const int xs_bytes = (int)gridDim.x * 32 * c.DP * 4;
-    const __amdgpu_buffer_rsrc_t xs_rs[2] = {__builtin_amdgcn_make_buffer_rsrc(c.xs, 0, xs_bytes, 0x00020000),
-                                             __builtin_amdgcn_make_buffer_rsrc(c.xs + (size_t)gridDim.x * 32 * c.DP, 0, xs_bytes, 0x00020000)};
+    __amdgpu_buffer_rsrc_t xs_rs[2];
+    small_exchange_rsrc<32>(c, xs_rs);
     // ---- state <- initial state (GNN.py:262 / :265) for the owned rows, then the first condition -------------------------------------
     int go;
     {
@@ -100,14 +98,7 @@ __global__ void __launch_bounds__(64) k_small_loop(const GnnFusedArgs a0, const 
         a.state_cur = c.init - a0.row_begin * Ds;                    // (body 0 builds the tile skeleton: own rows from the read-only initial state)
         a.state_nxt = nullptr;
         load_tile_generic<false, 4>(a, X, ipt, i0, lane, nvalid, KP, c_aggs, k > 0, nullptr, nullptr, 0, true);     // k > 0: the tile skeleton is still in LDS; no gather here
-        {
-            const __amdgpu_buffer_rsrc_t rs = xs_rs[k & 1];
-            const int *es = ecached ? ec_src : nullptr;
-            const float *ew = ecached ? ec_w : nullptr;
-            if (c.DP == 32) small_gather<32, 16, 4>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, es, ew, e_base);
-            else if (c.rnd == 8) small_gather<32, 8, 8>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, es, ew, e_base);
-            else small_gather<32, 8, 4>(rs, X, ipt, lane, nvalid, KP, c_aggs, Ds, a0.adj_src, a0.adj_w, es, ew, e_base);
-        }
+        small_gather32(a0, c, xs_rs[k & 1], X, ipt, lane, nvalid, KP, ecached ? ec_src : nullptr, ecached ? ec_w : nullptr, e_base);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         SMALL_STAMP();                                               // body + 0: tile loaded (gather)
         const float *xb = X + (lane & 31) * KP + half;

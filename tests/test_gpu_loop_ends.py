@@ -2,7 +2,7 @@
 
 1. OUTPUT STAGE.  apply_filters + net_output (reference GNN/GNN.py:275-279) exists four times: k_out1 (csrc/gnn_loop.hip: one-layer head,
    T <= 8, at most 64 KiB of LDS), small_output_stage (csrc/gnn_small_common.h: the same head folded into the persistent launch, in the
-   families k_small / k_small16 / k_small16w and their "mixed" variants), k_feats + launch_mlp (everything else) and the edge-based
+   families k_small_loop / k_small16 / wide k_small16 and their "mixed" variants), k_feats + launch_mlp (everything else) and the edge-based
    k_feats_edge.  Every other test builds the head as [2] with softmax; here T = 1, 3, 5, 8, 9 and a two-layer head, every head
    activation, with and without BatchNormalization, odd state widths, a saturating softmax, and masks that end on a row-block or tile edge.
 2. GRAPH READOUT (GNN.py:331-332): k_readout and the copy folded into the persistent launch (small_graph_readout: eight entries at a time

@@ -1,4 +1,4 @@
-"""The persistent small-graph launch for net_state hidden layers up to 64 wide (k_small16w, csrc/gnn_small16w_kernel.h): one launch runs
+"""The persistent small-graph launch for net_state hidden layers up to 64 wide (k_small16 with WIDE, csrc/gnn_small16_kernel.h): one launch runs
 the initial state, the first condition, every body and the output stage of a Loop on up to 4,096 nodes when net_state has two or three
 layers, hidden layers <= 64 (one of them > 32), a state <= 32 and a concat <= 96 wide.  The arithmetic is the exact f32-MFMA chain under
 impl 1 and 2: k, states and outputs are bit-identical to the C oracle and to one launch per body.  The shapes are the smallest that reach
