@@ -143,7 +143,17 @@ struct FusedPlan {
 // exchange layout, profiling, "the persistent loop gave up", the weights, the graph's labels) may all have changed since the last run, so
 // nothing of it is kept from run to run - and by the setters, which answer `used` from it.
 enum GnnLoopPath { GNN_PATH_UNFUSED = 0, GNN_PATH_BODIES = 1, GNN_PATH_PERSISTENT = 2 };      // one kernel per TF op / one launch per body / all bodies in one launch
-enum GnnBodyKernel { GNN_BODY_GENERIC = 0, GNN_BODY_FULL_TILE = 1, GNN_BODY_PAIR = 2 };       // k_fused / its full-tile specialisation / k_fused_pair
+enum GnnBodyKernel { GNN_BODY_GENERIC = 0, GNN_BODY_FULL_TILE = 1, GNN_BODY_PAIR = 2 };       // k_fused_generic / k_fused_full / k_fused_pair
+// What the launchers of gnn_fused_kernel.h pick an instantiation by, beyond the net's shape.  Host side only: no kernel sees it.
+// (GnnFusedArgs still carries full_tiles, gp_tiles and pieces, which no kernel and no launcher reads, beside seven more unread fields:
+// taking fields out moves every kernel's argument offsets, and with them the register allocation of instantiations that stand at 256
+// registers - three of them spilled, one k_small16 lost a wave of occupancy; profiles/fused_two_kernels.txt.)
+struct GnnFusedLaunch {
+    bool full = false;               // k_fused_full (state width 64) rather than k_fused_generic
+    bool given = false;              // ... whose aggregate is given (GnnFusedArgs::agg_in: feature-sliced exchange): no gather
+    bool program = false;            // ... or which gathers from the graph's program (gp_ent / gp_slot) rather than walking the CSR
+    int pieces = 3;                  // piece format of the split arithmetic
+};
 struct LoopForm {
     int path = GNN_PATH_UNFUSED;
     // the per-body kernel of a fused loop (on the persistent path: what a run with one launch per body would take; the setters report it)
@@ -156,6 +166,7 @@ struct LoopForm {
     FusedPlan plan;
     unsigned grid = 0;
     size_t lds = 0;                  // dynamic LDS bytes
+    GnnFusedLaunch launch;           // one launch per body, k_fused_generic / k_fused_full: the instantiation's form
     // every field that is constant for the run; a body sets state_cur, state_nxt, gate, flag_out and tile_ctr (the start-up spread and
     // single_ticket are in it).  Persistent path: the arguments of that launch (exact arithmetic, unpadded tile, no gates)
     GnnFusedArgs args;
@@ -208,20 +219,20 @@ using GnnSmall16S0 = GnnSteps<4, 8, 12, 16, 20, 24>;             // k_small16: K
 typedef bool GnnSmallLaunch(int layers, int act, int steps, const GnnFusedArgs &a, const GnnSmallCtl &c, unsigned grid, size_t lds_bytes, hipStream_t st);
 GnnSmallLaunch gnn_small_launch, gnn_small_launch_mixed, gnn_small16_launch, gnn_small16_launch_mixed, gnn_small16w_launch, gnn_small16w_launch_mixed;
 
-// one per translation unit gnn_fused_l{1,2,3}.hip; false = no instantiation for (act, nt, ntl)
-bool gnn_fused_launch_l1(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+// k_fused_generic / k_fused_full (how.full), one launcher per translation unit gnn_fused_l{1,2,3}.hip; false = no instantiation for (act, nt, ntl)
+bool gnn_fused_launch_l1(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
 // split-arithmetic instantiations: gnn_fused_s{1,2,3}.hip
-bool gnn_fused_launch_s1(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_s2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_s3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_s1(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_s2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_s3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
 // wave-pair form (gnn_fused_pair_kernel.h: split arithmetic, state width 64, 128-wide hidden layers, 9 layer-0 chunks): gnn_fused_p{2,3}.hip
-bool gnn_fused_launch_p2(int act, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_p3(int act, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_l2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_l3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-// k_fused for a net whose last layer has its own activation (act: the hidden layers'; a.act_last): gnn_fused_ml{2,3}.hip (exact),
+bool gnn_fused_launch_p2(int act, int pieces, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_p3(int act, int pieces, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_l2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_l3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+// the same two kernels for a net whose last layer has its own activation (act: the hidden layers'; a.act_last): gnn_fused_ml{2,3}.hip (exact),
 // gnn_fused_ms{2,3}.hip (split)
-bool gnn_fused_launch_ml2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_ml3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_ms2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
-bool gnn_fused_launch_ms3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ml2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ml3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ms2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ms3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);

@@ -495,7 +495,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
         a.stagger = n_tiles64 >= (int64_t)4 * 4 * f.grid ? stagger_rounds : (n_tiles64 > (int64_t)4 * f.grid ? GNN_FUSED_SPREAD_SMALL_DEFAULT : 0);
         f.lds = pair_lds_bytes(p);
     } else if (f.kernel == GNN_BODY_FULL_TILE) {
-        // the full-tile specialisation (no generic paths compiled in) on every tile; a partial last tile takes a wave-uniform
+        // k_fused_full (none of the generic paths compiled in) on every tile; a partial last tile takes a wave-uniform
         // branch with masked row stores / condition votes (the row buffers are padded to whole tiles, rows past n_rows have no arcs)
         a.full_tiles = 1;
         if (f.program) {
@@ -504,6 +504,11 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
             a.gp_slot = g->sh->gp_slot[f.schedule == 2 ? 1 : 0]; a.gp_slots = (int)g->sh->gp_cost.size();
         }
     }
+    // the instantiation's form.  A program without a full tile (a graph of fewer than 32 rows) is not gathered from: the launch walks the CSR
+    f.launch.full = f.kernel == GNN_BODY_FULL_TILE;
+    f.launch.given = f.launch.full && a.agg_in != nullptr;
+    f.launch.program = f.launch.full && f.program && g->sh->gp_tiles > 0;
+    f.launch.pieces = f.pieces;
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
 
@@ -594,7 +599,7 @@ static int decide_persistent(gnn_loop *l, LoopForm &f, const SmallForm &sf)
 // 7 - 11 % less time per iteration), one wave per tile beyond (N = 41 k: +13 %, BASELINE size: 0.78 against 0.68 ms - the seven meetings of
 // a pair per tile cost more than its shorter matrix phases return; profiles/r05_midsize_forms.txt, r05_pair_stamps.txt).  The pair exists for
 // nets with one activation for all layers (pair_covers): a net whose last layer has its own takes one wave per tile there too.
-// Gather form (gnn_loop_set_gather_form): the bodies read the graph's program when the launch is the full-tile form of k_fused that gathers
+// Gather form (gnn_loop_set_gather_form): the bodies read the graph's program when the launch is k_fused_full and gathers
 // (state width 64, a net with a 64-wide last layer, no feature-sliced exchange, not the wave pair) and the graph has a program - it is
 // built here, on first demand.
 int gnn_loop_decide_form(gnn_loop *l)
@@ -646,19 +651,19 @@ static bool launch_body(const LoopForm &f, const GnnFusedArgs &a, hipStream_t st
     const FusedPlan &p = f.plan;
     if (p.act_last != p.act) {                                        // the last layer's own activation: a.act_last (never the wave pair)
         if (f.kernel == GNN_BODY_PAIR || p.layers < 2) return false;
-        if (f.split) return p.layers == 2 ? gnn_fused_launch_ms2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st) : gnn_fused_launch_ms3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
-        return p.layers == 2 ? gnn_fused_launch_ml2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st) : gnn_fused_launch_ml3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+        if (f.split) return p.layers == 2 ? gnn_fused_launch_ms2(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st) : gnn_fused_launch_ms3(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
+        return p.layers == 2 ? gnn_fused_launch_ml2(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st) : gnn_fused_launch_ml3(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
     }
     if (f.kernel == GNN_BODY_PAIR)
-        return p.layers == 2 ? gnn_fused_launch_p2(p.act, a, f.grid, f.lds, st) : gnn_fused_launch_p3(p.act, a, f.grid, f.lds, st);
+        return p.layers == 2 ? gnn_fused_launch_p2(p.act, f.pieces, a, f.grid, f.lds, st) : gnn_fused_launch_p3(p.act, f.pieces, a, f.grid, f.lds, st);
     if (f.split) {
-        if (p.layers == 1) return gnn_fused_launch_s1(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
-        if (p.layers == 2) return gnn_fused_launch_s2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
-        return gnn_fused_launch_s3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+        if (p.layers == 1) return gnn_fused_launch_s1(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
+        if (p.layers == 2) return gnn_fused_launch_s2(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
+        return gnn_fused_launch_s3(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
     }
-    if (p.layers == 1) return gnn_fused_launch_l1(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
-    if (p.layers == 2) return gnn_fused_launch_l2(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
-    return gnn_fused_launch_l3(p.act, p.NT, p.NTL, a, f.grid, f.lds, st);
+    if (p.layers == 1) return gnn_fused_launch_l1(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
+    if (p.layers == 2) return gnn_fused_launch_l2(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
+    return gnn_fused_launch_l3(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
 }
 
 // body k of a run whose form is one launch per body

@@ -1,4 +1,5 @@
-// Fused iteration kernel for gfx950 (device code).  Included by gnn_fused_{l,s}{1,2,3}.hip and gnn_fused_m{l,s}{2,3}.hip, one translation
+// Fused iteration kernels for gfx950 (device code): k_fused_full (state width 64) and k_fused_generic (every other width).  Where a comment
+// elsewhere says k_fused it means the two together.  Included by gnn_fused_{l,s}{1,2,3}.hip and gnn_fused_m{l,s}{2,3}.hip, one translation
 // unit per layer count, arithmetic mode and "the last layer has its own activation", so that the instantiations compile in parallel.
 //
 // One launch = one iteration of GNN.Loop (reference GNN/GNN.py:223-242 + :202-220):
@@ -33,7 +34,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace gnn_fused_dev {
 
-// The tile loop launders its pointers through empty asm statements (see k_fused); that hides from the compiler that they
+// The tile loop launders its pointers through empty asm statements (fused_opaque_pointers); that hides from the compiler that they
 // are global-memory pointers, and it would fall back to flat_load/flat_store (which also tie up the LDS counter).  All
 // memory accesses below therefore go through explicit address_space(1) pointers.
 #define GNN_GLOBAL __attribute__((address_space(1)))
@@ -534,7 +535,7 @@ __device__ __forceinline__ void split8_f16(const float (&v)[8], v4i &p0, v4i &p1
 }
 // Range guard of a hidden layer's operand: max |accumulator| x us x 2^GNN_F16_EX bounds every scaled activation the cut will see (every
 // activation has |act(v)| <= max(|v|, 2.5): the folded SELU's negative branch stays above -2.42), so it is taken once over the accumulators
-// instead of inside the cut, by k_fused between the layers (a running maximum threaded through the pipelined cuts, or this check at the top
+// instead of inside the cut, by the kernels between the layers (a running maximum threaded through the pipelined cuts, or this check at the top
 // of layer_split_from_regs, raised the register peak of the headline instantiation past 256: 180 - 272 bytes of scratch).
 template <int NI>
 __device__ __forceinline__ float hidden_range(const f32x16 (&h)[NI], float us)
@@ -961,8 +962,8 @@ __device__ __forceinline__ void gather_batch(int my_src, float my_w, __amdgpu_bu
 // first is consumed (GB x 4 groups x 256 B = 16 KiB in flight per wave), and the fmaf chain runs in stored order,
 // flushing to LDS at every row boundary.
 // AL16: rows of the tile and the aggregated-state block are 16-byte aligned (split arithmetic): one ds_write_b128 per row piece
-// PADDED: the zero padding of the tile (columns behind the concat, alignment hole) is already in place: nothing in a tile's life
-// writes those columns, so the full-tile kernel zeroes them once per wave instead of once per tile
+// The zero padding of the tile (columns behind the concat, alignment hole) is already in place: nothing in a tile's life writes those
+// columns, so the kernel zeroes them once per wave instead of once per tile
 // (Two batches of GB rows in flight per lane group were measured in round 2: 4 % slower, DESIGN.md appendix.)
 // Own state rows and label columns of a full Ds == 64 tile: 8 x 16 B + 4 floats per lane requested in front of the gather, written to
 // LDS behind it (their latency hides behind the gather)
@@ -1007,7 +1008,7 @@ struct TileOwn64 {
     }
 };
 
-template <bool AL16, bool PADDED = false>
+template <bool AL16>
 __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X, const int *ipt, int64_t i0, int lane,
                                                  int KP, int c_aggs, int my_src, float my_w)
 {
@@ -1015,7 +1016,6 @@ __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X
     const int gl = lane & 15, grp = lane >> 4;
     TileOwn64<AL16> own;
     own.request(a, i0, lane);
-    if constexpr (!PADDED) zero_pad_columns(a, X, lane, KP);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                   // ipt visible to the whole wave
 
     int node = grp * 8;
@@ -1487,18 +1487,267 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N])
         for (int r = 0; r < 16; ++r) acc[jt][r] = 0.0f;
 }
 
-// FULL: state width 64, the tuned 32-node tile paths only (a partial last tile takes their masked branch): the guarded generic paths
-// are not compiled in at all, which frees registers and scalar registers for the tuned ones.
-// GIVEN (with FULL): the aggregated states come from a.agg_in (feature-sliced exchange) - row copies instead of the gather.  A
-// template parameter, not a branch: a wave-uniform branch in the tile loop of the full-tile kernel cost 3 % (0.700 -> 0.721 ms).
+// ---------------------------------------------------------------------------------------------------------------------
+// The fused body is two kernels: k_fused_full (state width 64: program or CSR gather, 16-byte tile accesses, the first batch a tile ahead)
+// and k_fused_generic (every other width).  The phases below are the same in both; they are forced inline, so each kernel's instruction
+// stream is the one of the phases written out in place.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// diagnostics only (GNN_FUSED_STAMPS): s_memtime of lane 0 into slot `slot` of the tile's stamps; `stamp` and `lane` are the caller's
+#ifndef GNN_DIAG
+#define GNN_STAMP(slot) do { } while (0)
+#else
+#define GNN_STAMP(slot)                                                                      \
+    do {                                                                                     \
+        if (stamp) {                                                                         \
+            __builtin_amdgcn_sched_barrier(0);                                               \
+            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
+            if (lane == 0) stamp[slot] = t_;                                                 \
+            __builtin_amdgcn_sched_barrier(0);                                               \
+        }                                                                                    \
+    } while (0)
+#endif
+
+// GNN_POISON=1 (diagnostic build): NaN over the whole LDS allocation (tiles, alignment holes, look-ahead slack, staged vectors) before anything is staged
+__device__ __forceinline__ void fused_poison_lds([[maybe_unused]] const GnnFusedArgs &a, [[maybe_unused]] float *lds)
+{
+#ifdef GNN_DIAG
+    if (a.lds_floats) {
+        for (int t = threadIdx.x; t < a.lds_floats; t += blockDim.x) lds[t] = __builtin_nanf("");
+        __syncthreads();
+    }
+#endif
+}
+
+// last-layer bias and BatchNormalization scale / shift (ep, behind the row-pointer slots) and the hidden layers' biases (hb, split path:
+// [LAYERS - 1][32 NT]): staged once per workgroup
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT>
+__device__ __forceinline__ void fused_stage_vectors(const GnnFusedArgs &a, float *ep, float *hb)
+{
+    for (int t = threadIdx.x; t < 3 * 32 * NTL; t += blockDim.x) {
+        const int which = t / (32 * NTL), f = t - which * 32 * NTL;
+        ep[t] = which == 0 ? a.bias[LAYERS - 1][f] * (SPLIT ? a.bsc[LAYERS - 1] : 1.0f) : (a.bn_scale ? (which == 1 ? a.bn_scale[f] : a.bn_shift[f]) : 0.0f);
+    }
+    if constexpr (SPLIT && LAYERS > 1)                // (x 2^(e_w + e_x) of the layer in the fp16-piece format: bsc)
+        for (int t = threadIdx.x; t < (LAYERS - 1) * 32 * NT; t += blockDim.x)
+            hb[t] = a.bias[t / (32 * NT)][t % (32 * NT)] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f) * a.bsc[t / (32 * NT)];   // folded SELU: see GNN_S1_E
+    __syncthreads();
+}
+
+// Start-up spread.  All waves of the chip run the same phases on tiles of similar cost: started together they gather together
+// (HBM saturated, 3-4 us per round trip) and compute together (HBM idle).  Every wave therefore waits a different fraction of
+// one tile period before its first tile; the dynamic tickets keep the load balanced.  variant bit 2: the old two-cluster
+// stagger (waves 4-7 delayed by a fixed amount).
+__device__ __forceinline__ void fused_startup_spread(const GnnFusedArgs &a, int wave)
+{
+    if (a.stagger > 0) {
+        int rounds = 0;
+        if (a.variant & 4) rounds = wave >= GNN_FUSED_WAVES / 2 ? a.stagger : 0;
+        else rounds = (int)((((unsigned)blockIdx.x * GNN_FUSED_WAVES + (unsigned)wave) * 0x9E3779B1u) >> 16) % (unsigned)(a.stagger + 1);
+        for (int i = 0; i < rounds; ++i) __builtin_amdgcn_s_sleep(127);
+    }
+}
+
+// Fresh, compiler-opaque copies of the pointers for every tile (a: the tile's own copy of the arguments): without this the loop-invariant
+// address arithmetic of the unrolled layers is hoisted out of the tile loop and spills (256 VGPRs + scratch instead of ~190).
+__device__ __forceinline__ void fused_opaque_pointers(GnnFusedArgs &a)
+{
+    asm volatile("" : "+s"(a.Wp[0]), "+s"(a.Wp[1]), "+s"(a.Wp[2]), "+s"(a.bias[0]), "+s"(a.bias[1]), "+s"(a.bias[2]));
+    asm volatile("" : "+s"(a.bn_scale), "+s"(a.bn_shift), "+s"(a.state_cur), "+s"(a.state_nxt), "+s"(a.inv), "+s"(a.adj_src), "+s"(a.adj_w));
+}
+
+// ---- B: net_state.  H^T[feature][node] = W^T . X^T on MFMA f32 32x32x2 (exact) or on the piece products (SPLIT, format PC) ----
+// Declares half, out (the last layer's raw accumulators) and mx in the kernel's tile loop; a, X, KP, lane, ep, hb and stamp are the kernel's.
+// AL16: layer 0 of a net with hidden layers reads the tile in 16-byte pieces (the full-tile kernel's tile layout).
+// WAIT: 12 wait states behind layer 0 of the split arithmetic.  Its chunk loop ends in a branch, what follows reads its accumulators, and
+// hipcc (ROCm 7.2) pads nothing across a basic-block edge (persistent small-graph loop): k_fused_generic, where a one-tile layer
+// leaves 11 instructions between the two.  k_fused_full's listings pass the Makefile's scan (tools/scan_mfma_hazard.py) without.
+// A macro, not a function like the other phases: as a forced-inline function the same text gave every full-tile instantiation another
+// register allocation (16 of 648 with one vector register more or less, code sizes - 1.3 .. + 0.5 KB; profiles/fused_two_kernels.txt).
+#define GNN_FUSED_DENSE_LAYERS(AL16, WAIT) \
+    const int half = lane >> 5;                                                                                                                                 \
+    const float *xb = X + (lane & 31) * KP + half;                                                                                                              \
+    f32x16 out[NTL];                                                                                                                                            \
+    float mx = 0.0f;                                  /* range guard of the fp16-piece format: max |scaled operand| of this tile's cuts */                      \
+    if constexpr (SPLIT) {                                                                                                                                      \
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(a.Ws_base), 0, a.ws_bytes, 0x00020000);                          \
+        const int wv = lane * 16;                                                                                                                               \
+        const float *xr = X + (lane & 31) * KP + 8 * half;                                                                                                      \
+        if constexpr (LAYERS == 1) {                                                                                                                            \
+            layer0_split<NTL, false, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, out, ep, half, mx);                                                               \
+        } else {                                                                                                                                                \
+            f32x16 h1[NT];                                                                                                                                      \
+            layer0_split<NT, AL16, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);                                                                  \
+            if constexpr (WAIT) { asm volatile("s_nop 7\n\ts_nop 3" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }                                         \
+            GNN_STAMP(3);                                                                                                                                       \
+            GNN_STAMP(4);                                                                                                                                       \
+            if constexpr (PC == 2) { asm volatile("" : "+v"(mx)); mx = __builtin_fmaxf(mx, hidden_range<NT>(h1, a.usc[0])); asm volatile("" : "+v"(mx)); }      \
+            if constexpr (LAYERS == 2) {                                                                                                                        \
+                layer_split_from_regs<NT, NTL, ACT, PC>(h1, ep, half, out, wrs, wv, a.ws_off[1], a.usc[0], mx);                                                 \
+            } else {                                                                                                                                            \
+                f32x16 h2[NT];                                                                                                                                  \
+                layer_split_from_regs<NT, NT, ACT, PC>(h1, hb + 32 * NT, half, h2, wrs, wv, a.ws_off[1], a.usc[0], mx);                                         \
+                if constexpr (PC == 2) { asm volatile("" : "+v"(mx)); mx = __builtin_fmaxf(mx, hidden_range<NT>(h2, a.usc[1])); asm volatile("" : "+v"(mx)); }  \
+                layer_split_from_regs<NT, NTL, ACT, PC>(h2, ep, half, out, wrs, wv, a.ws_off[2], a.usc[1], mx);                                                 \
+            }                                                                                                                                                   \
+        }                                                                                                                                                       \
+    } else if constexpr (LAYERS == 1) {                                                                                                                         \
+        zero_acc<NTL>(out);                                                                                                                                     \
+        layer_from_lds<NTL>(xb, a.Wp[0] + (size_t)lane * NTL, a.kk0, out, a.wstride);                                                                           \
+    } else {                                                                                                                                                    \
+        f32x16 h1[NT];                                                                                                                                          \
+        zero_acc<NT>(h1);                                                                                                                                       \
+        layer_from_lds<NT>(xb, a.Wp[0] + (size_t)lane * NT, a.kk0, h1, a.wstride);                                                                              \
+        GNN_STAMP(3);                                                                                                                                           \
+        GNN_STAMP(4);                                                                                                                                           \
+        if constexpr (LAYERS == 2) {                                                                                                                            \
+            zero_acc<NTL>(out);                                                                                                                                 \
+            layer_from_regs<NT, NTL, ACT>(h1, a.bias[0], half, out, a.Wp[1] + (size_t)lane * NTL, a.wstride);                                                   \
+        } else {                                                                                                                                                \
+            f32x16 h2[NT];                                                                                                                                      \
+            zero_acc<NT>(h2);                                                                                                                                   \
+            layer_from_regs<NT, NT, ACT>(h1, a.bias[0], half, h2, a.Wp[1] + (size_t)lane * NT, a.wstride);                                                      \
+            zero_acc<NTL>(out);                                                                                                                                 \
+            layer_from_regs<NT, NTL, ACT>(h2, a.bias[1], half, out, a.Wp[2] + (size_t)lane * NTL, a.wstride);                                                   \
+        }                                                                                                                                                       \
+    }
+
+// Tiles: the first TWO rounds are assigned statically - wave w of the launch (wave-major over the workgroups, so that a partial round
+// spreads over all CUs) takes tiles w and w + W, W = waves of the launch - and only from the third round on does a wave draw tickets
+// from the iteration's counter, one tile ahead (at the end of the previous tile's dense layers), early enough to have that tile's row
+// pointers and first gather ids requested.  (Until round 4 every wave drew its first two tickets at kernel start: 4,096 atomic adds on
+// ONE word, which the memory side serves at about 88 per microsecond - up to 46 us before the last wave knew its first tile, a third
+// of an iteration at 125 k nodes.  Serving the tickets heaviest-tile-first was measured in round 2: 1 % slower on the BASELINE graph.)
+// third_round (wave-uniform): tiles beyond 2 W exist - no draw without them, two static tiles per wave cover the launch.
+// fused_draw_ticket: lane 0's ticket for the tile after next (0x3fffffff: none); fused_next_tile: the wave's first look at it, at the end
+// of the tile.
+// AHEAD (a tile's first batch is requested during the previous tile): the counter's address through a vector register.  An atomic at a
+// wave-uniform address inside divergent code is rewritten by the compiler into "one lane adds, v_readfirstlane hands the result round" -
+// and that read waits for the ticket on the spot, with the rows requested behind it queued behind the wait.  The only read of the ticket is
+// fused_next_tile's, which also adds the 2 W.
+template <bool AHEAD>
+__device__ __forceinline__ int fused_draw_ticket(const GnnFusedArgs &a0, bool third_round, int W_launch, int lane)
+{
+    int next2_tile = 0x3fffffff;
+    if (third_round) {
+        int64_t ctr_off = 0;
+        if constexpr (AHEAD) asm volatile("" : "+v"(ctr_off));
+        if constexpr (AHEAD) { if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr + ctr_off, 1); }      // (+ 2 W where it is read)
+        else if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr, 1) + 2 * W_launch;
+    }
+    return next2_tile;
+}
+template <bool AHEAD>
+__device__ __forceinline__ int fused_next_tile(const GnnFusedArgs &a0, int next2_tile, bool third_round, int W_launch)
+{
+    if constexpr (AHEAD) {
+        asm volatile("" : "+v"(next2_tile));                    // first look at the ticket: here
+        return __builtin_amdgcn_readfirstlane(next2_tile) + (third_round ? 2 * W_launch : 0) + a0.tile_base;
+    } else return __builtin_amdgcn_readfirstlane(next2_tile) + a0.tile_base;
+}
+
+// The fused body for every state width but 64.  Persistent workgroup of 8 waves (one per CU): every wave pulls 32-node tiles from a
+// device-wide counter until none is left; the waves never synchronise with each other after the staging.  The tile load is
+// load_tile_generic (any width, partial tiles, a given aggregate a.agg_in), the epilogue writes the new state to the tile and
+// check_store_generic tests and stores it.
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
-// PROG (with FULL, not GIVEN): every tile is gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the partial
+// ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int PC, int ACTL>
+__global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const GnnFusedArgs a0)
+{
+    const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (!gnn_gate_open(a.gate, a.world)) return;
+    fused_poison_lds(a, lds);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int KP = a.KP, Ds = a.Ds;
+    float *X = lds + (size_t)wave * 32 * KP;
+    const int c_aggs = a.c_aggs;                      // column of the aggregated state block (Ds + NLc + alignment hole)
+    const int W_launch = (int)gridDim.x * (int)(blockDim.x >> 6);            // (tiles and tickets: fused_draw_ticket)
+    const int w_launch = wave * (int)gridDim.x + (int)blockIdx.x;
+    const bool third_round = (int64_t)2 * W_launch * 32 < a.n_rows;
+    int tile = w_launch + a.tile_base, next_tile = w_launch + W_launch + a.tile_base;
+    const int ip_first_raw = tile_rowptr_request(a, tile, lane);      // on its way while the workgroup stages its vectors below
+    float *ep = lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32 + GNN_FUSED_WAVES * 36;
+    float *hb = ep + 3 * 32 * NTL;
+    fused_stage_vectors<LAYERS, NT, NTL, ACT, SPLIT>(a, ep, hb);
+    fused_startup_spread(a, wave);
+    int ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
+  for (;;) {
+    const int64_t i0 = (int64_t)tile * 32;
+    if (i0 >= a.n_rows) break;                        // wave-uniform; no workgroup barrier anywhere in the tile loop
+    const int nvalid = (int)((a0.n_rows - i0) < 32 ? (a0.n_rows - i0) : 32);
+    GnnFusedArgs a = a0;
+    fused_opaque_pointers(a);
+#ifdef GNN_DIAG
+    unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)tile << 3) : nullptr;
+#endif
+    GNN_STAMP(0);
+
+    // the tile's 33 row pointers go through LDS: the gather re-reads them inside divergent code, where a cross-lane
+    // broadcast from lanes of another group would not be safe
+    int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
+    if (lane <= 32) ipt[lane] = ip_cur;               // requested during the previous tile
+    const int ip_next_raw = tile_rowptr_request(a, next_tile, lane);      // row pointers of the NEXT tile: on their way during the gather
+    // the gather is a chain of few instructions and long memory waits: with a raised priority its loads are issued ahead of the
+    // SIMD partner's dense VALU / MFMA stream instead of behind it
+    if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
+    load_tile_generic(a, X, ipt, i0, lane, nvalid, KP, c_aggs);
+    if (a.variant & 1) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    GNN_STAMP(2);
+
+    GNN_FUSED_DENSE_LAYERS(false, true)
+    // The epilogue reads the last MFMA's result a few instructions on, across the basic-block edges of the ticket draw, and hipcc (ROCm 7.2)
+    // pads no wait states across an edge (persistent small-graph loop; small16_layer): the 19 that the 16-pass
+    // v_mfma_f32_32x32x2_f32 needs are issued here.  The Makefile's scan of every listing (tools/scan_mfma_hazard.py) is the guard.
+    asm volatile("s_nop 15\n\ts_nop 2" ::: "memory");
+    // ---- C: last-layer epilogue, new state to LDS (over the aggregated-state columns, no longer needed) ---------------
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    GNN_STAMP(5);
+    // Requests for the tile after next (ticket) and for the next tile (its row pointers): issued HERE, behind the last weight loads,
+    // because vector-memory results return in issue order - in front of the dense layers these HBM-latency loads would hold up every
+    // weight wait - and the epilogue / norm / stores below cover their latency.
+    const int next2_tile = fused_draw_ticket<false>(a0, third_round, W_launch, lane);
+    const int ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
+    if constexpr (SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
+#pragma unroll
+    for (int jt = 0; jt < NTL; ++jt) {
+        const float us = SPLIT ? a.usc[LAYERS - 1] : 1.0f;
+        if (a.bn_scale) tile_epilogue_last<ACTL, true, SPLIT, true, SPLIT>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, us);
+        else tile_epilogue_last<ACTL, false, SPLIT, true, SPLIT>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, us);
+        float *x = X + (lane & 31) * KP + c_aggs;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int f = 32 * jt + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (f < Ds) x[f] = out[jt][r];
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    GNN_STAMP(6);
+    check_store_generic(a, X, i0, lane, nvalid, KP, c_aggs);
+    GNN_STAMP(7);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next tile re-uses this wave's LDS region
+    tile = next_tile;
+    next_tile = fused_next_tile<false>(a0, next2_tile, third_round, W_launch);
+    ip_cur = ip_next;
+  }
+}
+
+// The fused body for state width 64 (two feature tiles in the last layer): the tuned 32-node tile paths only - 16-byte accesses to a tile
+// whose padding is zeroed once per wave, unguarded row copies; a partial last tile takes their masked branch.  None of the guarded paths
+// of k_fused_generic is compiled in, which frees registers and scalar registers for the tuned ones.
+// GIVEN: the aggregated states come from a.agg_in (feature-sliced exchange) - row copies instead of the gather.  A template parameter,
+// not a branch: a wave-uniform branch in the tile loop of this kernel cost 3 % (0.700 -> 0.721 ms).
+// PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
+// PROG (not GIVEN): every tile is gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the partial
 // last tile of the graph too (an ordinary slot of the tile schedule, prog_header_request): no CSR walk is compiled in.  A template parameter for the same reason as
 // GIVEN.  With GNN_FIRST_BATCH_AHEAD a tile's first batch is requested during the previous tile (load_tile_prog64_ahead).
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, bool FULL = false, bool GIVEN = false, int PC = 3, bool PROG = false, int ACTL = ACT>
-__global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedArgs a0)
+template <int LAYERS, int NT, int ACT, bool SPLIT, bool GIVEN, int PC, bool PROG, int ACTL>
+__global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFusedArgs a0)
 {
+    constexpr int NTL = 2;
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
     // Persistent workgroup of 8 waves (one per CU): every wave pulls 32-node tiles from a device-wide counter until none
     // is left.  Waves w and w + 4 share a SIMD; the second half starts late so that, in steady state, one partner streams
@@ -1506,52 +1755,24 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
     // gather at once and then compute at once: HBM idles during compute, the matrix pipe during the gather).
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (!gnn_gate_open(a.gate, a.world)) return;
-#ifdef GNN_DIAG      // GNN_POISON=1: NaN over the whole LDS allocation (tiles, alignment holes, look-ahead slack, staged vectors) before anything is staged
-    if (a.lds_floats) {
-        for (int t = threadIdx.x; t < a.lds_floats; t += blockDim.x) lds[t] = __builtin_nanf("");
-        __syncthreads();
-    }
-#endif
+    fused_poison_lds(a, lds);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int KP = a.KP, Ds = a.Ds;
+    const int KP = a.KP, Ds = a.Ds;                   // (Ds: 64)
     float *X = lds + (size_t)wave * 32 * KP;
     const int c_aggs = a.c_aggs;                      // column of the aggregated state block (Ds + NLc + alignment hole)
-    // Tiles: the first TWO rounds are assigned statically - wave w of the launch (wave-major over the workgroups, so that a partial round
-    // spreads over all CUs) takes tiles w and w + W, W = waves of the launch - and only from the third round on does a wave draw tickets
-    // from the iteration's counter, one tile ahead (at the end of the previous tile's dense layers), early enough to have that tile's row
-    // pointers and first gather ids requested.  (Until round 4 every wave drew its first two tickets at kernel start: 4,096 atomic adds on
-    // ONE word, which the memory side serves at about 88 per microsecond - up to 46 us before the last wave knew its first tile, a third
-    // of an iteration at 125 k nodes.  Serving the tickets heaviest-tile-first was measured in round 2: 1 % slower on the BASELINE graph.)
-    const int W_launch = (int)gridDim.x * (int)(blockDim.x >> 6);
+    const int W_launch = (int)gridDim.x * (int)(blockDim.x >> 6);            // (tiles and tickets: fused_draw_ticket)
     const int w_launch = wave * (int)gridDim.x + (int)blockIdx.x;
-    const bool third_round = (int64_t)2 * W_launch * 32 < a.n_rows;          // wave-uniform: tickets are only drawn when tiles beyond 2 W exist
+    const bool third_round = (int64_t)2 * W_launch * 32 < a.n_rows;
     // PROG: tile / next_tile / the tickets are SLOTS of the launch's tile schedule; the tile a slot stands for comes with its header (tid)
     int tile = w_launch + a.tile_base, next_tile = w_launch + W_launch + a.tile_base;
     int ip_first_raw = 0;
     v4i hdr_first_raw = {0, 0, 0, 0};
     if constexpr (PROG) hdr_first_raw = prog_header_request(a, tile);
     else ip_first_raw = tile_rowptr_request(a, tile, lane);           // on its way while the workgroup stages its vectors below
-    // last-layer bias and BatchNormalization scale / shift: staged once per workgroup behind the row-pointer slots
     float *ep = lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32 + GNN_FUSED_WAVES * 36;
-    for (int t = threadIdx.x; t < 3 * 32 * NTL; t += blockDim.x) {
-        const int which = t / (32 * NTL), f = t - which * 32 * NTL;
-        ep[t] = which == 0 ? a.bias[LAYERS - 1][f] * (SPLIT ? a.bsc[LAYERS - 1] : 1.0f) : (a.bn_scale ? (which == 1 ? a.bn_scale[f] : a.bn_shift[f]) : 0.0f);
-    }
-    float *hb = ep + 3 * 32 * NTL;                    // hidden-layer biases (split path): [LAYERS - 1][32 NT]
-    if constexpr (SPLIT && LAYERS > 1)                // (x 2^(e_w + e_x) of the layer in the fp16-piece format: bsc)
-        for (int t = threadIdx.x; t < (LAYERS - 1) * 32 * NT; t += blockDim.x)
-            hb[t] = a.bias[t / (32 * NT)][t % (32 * NT)] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f) * a.bsc[t / (32 * NT)];   // folded SELU: see GNN_S1_E
-    __syncthreads();
-    // Start-up spread.  All waves of the chip run the same phases on tiles of similar cost: started together they gather together
-    // (HBM saturated, 3-4 us per round trip) and compute together (HBM idle).  Every wave therefore waits a different fraction of
-    // one tile period before its first tile; the dynamic tickets keep the load balanced.  variant bit 2: the old two-cluster
-    // stagger (waves 4-7 delayed by a fixed amount).
-    if (a.stagger > 0) {
-        int rounds = 0;
-        if (a.variant & 4) rounds = wave >= GNN_FUSED_WAVES / 2 ? a.stagger : 0;
-        else rounds = (int)((((unsigned)blockIdx.x * GNN_FUSED_WAVES + (unsigned)wave) * 0x9E3779B1u) >> 16) % (unsigned)(a.stagger + 1);
-        for (int i = 0; i < rounds; ++i) __builtin_amdgcn_s_sleep(127);
-    }
+    float *hb = ep + 3 * 32 * NTL;
+    fused_stage_vectors<LAYERS, NT, NTL, ACT, SPLIT>(a, ep, hb);
+    fused_startup_spread(a, wave);
     int ip_cur = 0, src_cur = 0;
     float w_cur = 0.0f;
     // PROG: header of the current tile (wave-uniform) and this lane's entry of its first batch; AHEAD: the rows of that batch and the entry of
@@ -1568,31 +1789,17 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         if constexpr (AHEAD) prog_first_batch_request(a, hdr_first, hdr_nb, ent_cur, lane, x_first, ent_second);
     } else {
         ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
-        if (FULL || Ds == 64) tile_first_ids(a, ip_cur, lane, src_cur, w_cur);
+        tile_first_ids(a, ip_cur, lane, src_cur, w_cur);
     }
-    if constexpr (FULL) zero_pad_columns(a, X, lane, KP);             // once: no tile ever writes the padding columns
+    zero_pad_columns(a, X, lane, KP);                 // once: no tile ever writes the padding columns
   for (;;) {
     const int64_t i0 = (int64_t)(PROG ? tid : tile) * 32;
-    if (PROG ? tile >= a.gp_slots : i0 >= a.n_rows) break;        // wave-uniform; no workgroup barrier anywhere in the kernel
+    if (PROG ? tile >= a.gp_slots : i0 >= a.n_rows) break;        // wave-uniform; no workgroup barrier anywhere in the tile loop
     const int nvalid = (int)((a0.n_rows - i0) < 32 ? (a0.n_rows - i0) : 32);
-    // Fresh, compiler-opaque copies of the pointers for every tile: without this the loop-invariant address arithmetic of
-    // the unrolled layers is hoisted out of the tile loop and spills (256 VGPRs + scratch instead of ~190).
     GnnFusedArgs a = a0;
-    asm volatile("" : "+s"(a.Wp[0]), "+s"(a.Wp[1]), "+s"(a.Wp[2]), "+s"(a.bias[0]), "+s"(a.bias[1]), "+s"(a.bias[2]));
-    asm volatile("" : "+s"(a.bn_scale), "+s"(a.bn_shift), "+s"(a.state_cur), "+s"(a.state_nxt), "+s"(a.inv), "+s"(a.adj_src), "+s"(a.adj_w));
-#ifndef GNN_DIAG
-#define GNN_STAMP(slot) do { } while (0)
-#else
+    fused_opaque_pointers(a);
+#ifdef GNN_DIAG
     unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)(PROG ? tid : tile) << 3) : nullptr;      // (by tile id, whatever the schedule)
-#define GNN_STAMP(slot)                                                                      \
-    do {                                                                                     \
-        if (stamp) {                                                                         \
-            __builtin_amdgcn_sched_barrier(0);                                               \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
-            if (lane == 0) stamp[slot] = t_;                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                               \
-        }                                                                                    \
-    } while (0)
 #endif
     GNN_STAMP(0);
 
@@ -1608,11 +1815,10 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         if (lane <= 32) ipt[lane] = ip_cur;           // requested during the previous tile
         ip_next_raw = tile_rowptr_request(a, next_tile, lane);            // row pointers of the NEXT tile: on their way during the gather
     }
-    const bool fast64 = FULL || ((Ds == 64) && (nvalid == 32) && !a.agg_in);     // wave-uniform: the BASELINE shape takes the unguarded paths
     // the gather is a chain of few instructions and long memory waits: with a raised priority its loads are issued ahead of the
     // SIMD partner's dense VALU / MFMA stream instead of behind it
     if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
-    if constexpr (FULL && GIVEN) load_tile_given64<SPLIT>(a, X, i0, lane, KP, c_aggs);      // feature-sliced exchange: no gather (a.agg_in)
+    if constexpr (GIVEN) load_tile_given64<SPLIT>(a, X, i0, lane, KP, c_aggs);      // feature-sliced exchange: no gather (a.agg_in)
     else if constexpr (AHEAD)
         load_tile_prog64_ahead<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, x_first, ent_second, hdr_next_raw, hdr_first_next, hdr_nb_next, tid_next, ent_next);
     else if constexpr (PROG) {
@@ -1622,85 +1828,22 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         hdr_first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); hdr_nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
         tid_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.z);
     }
-    else if constexpr (FULL) load_tile_fast64<SPLIT, true>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
-    else {
-        if (fast64) load_tile_fast64<SPLIT>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
-        else load_tile_generic(a, X, ipt, i0, lane, nvalid, KP, c_aggs);
-    }
+    else load_tile_fast64<SPLIT>(a, X, ipt, i0, lane, KP, c_aggs, src_cur, w_cur);
     if (a.variant & 1) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     GNN_STAMP(2);
 
-    // ---- B: net_state.  H^T[feature][node] = W^T . X^T on MFMA f32 32x32x2 -------------------------------------------
-    const int half = lane >> 5;
-    const float *xb = X + (lane & 31) * KP + half;
-    f32x16 out[NTL];
-    float mx = 0.0f;                                  // range guard of the fp16-piece format: max |scaled operand| of this tile's cuts
-    if constexpr (SPLIT) {
-        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(a.Ws_base), 0, a.ws_bytes, 0x00020000);
-        const int wv = lane * 16;
-        const float *xr = X + (lane & 31) * KP + 8 * half;
-        if constexpr (LAYERS == 1) {
-            layer0_split<NTL, false, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, out, ep, half, mx);
-        } else {
-            f32x16 h1[NT];
-            if constexpr (FULL) layer0_split<NT, true, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);
-            else {
-                if (Ds == 64) layer0_split<NT, true, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);    // 16-byte aligned tile layout
-                else layer0_split<NT, false, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);
-            }
-            GNN_STAMP(3);
-            GNN_STAMP(4);
-            if constexpr (PC == 2) { asm volatile("" : "+v"(mx)); mx = __builtin_fmaxf(mx, hidden_range<NT>(h1, a.usc[0])); asm volatile("" : "+v"(mx)); }
-            if constexpr (LAYERS == 2) {
-                layer_split_from_regs<NT, NTL, ACT, PC>(h1, ep, half, out, wrs, wv, a.ws_off[1], a.usc[0], mx);
-            } else {
-                f32x16 h2[NT];
-                layer_split_from_regs<NT, NT, ACT, PC>(h1, hb + 32 * NT, half, h2, wrs, wv, a.ws_off[1], a.usc[0], mx);
-                if constexpr (PC == 2) { asm volatile("" : "+v"(mx)); mx = __builtin_fmaxf(mx, hidden_range<NT>(h2, a.usc[1])); asm volatile("" : "+v"(mx)); }
-                layer_split_from_regs<NT, NTL, ACT, PC>(h2, ep, half, out, wrs, wv, a.ws_off[2], a.usc[1], mx);
-            }
-        }
-    } else if constexpr (LAYERS == 1) {
-        zero_acc<NTL>(out);
-        layer_from_lds<NTL>(xb, a.Wp[0] + (size_t)lane * NTL, a.kk0, out, a.wstride);
-    } else {
-        f32x16 h1[NT];
-        zero_acc<NT>(h1);
-        layer_from_lds<NT>(xb, a.Wp[0] + (size_t)lane * NT, a.kk0, h1, a.wstride);
-        GNN_STAMP(3);
-        GNN_STAMP(4);
-        if constexpr (LAYERS == 2) {
-            zero_acc<NTL>(out);
-            layer_from_regs<NT, NTL, ACT>(h1, a.bias[0], half, out, a.Wp[1] + (size_t)lane * NTL, a.wstride);
-        } else {
-            f32x16 h2[NT];
-            zero_acc<NT>(h2);
-            layer_from_regs<NT, NT, ACT>(h1, a.bias[0], half, h2, a.Wp[1] + (size_t)lane * NT, a.wstride);
-            zero_acc<NTL>(out);
-            layer_from_regs<NT, NTL, ACT>(h2, a.bias[1], half, out, a.Wp[2] + (size_t)lane * NTL, a.wstride);
-        }
-    }
+    GNN_FUSED_DENSE_LAYERS(true, false)
     // ---- C: last-layer epilogue, new state to LDS (over the aggregated-state columns, no longer needed) ---------------
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     GNN_STAMP(5);
     // Requests for the tile after next (ticket) and for the next tile (ids / weights of its first gather batch): issued HERE,
     // behind the last weight loads, because vector-memory results return in issue order - in front of the dense layers these
     // HBM-latency loads would hold up every weight wait - and the epilogue / norm / stores below cover their latency.
-    // (no draw when the launch has no third round: two static tiles per wave cover it)
     // AHEAD: the range flag first (it waits for its word when it is raised), then the ticket and the gate words, and only behind them the
     // next tile's second entry and first batch: what is read first is requested first, so that no wait in the epilogue reaches the sixteen rows.
     if constexpr (AHEAD && SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
-    // (AHEAD: the counter's address through a vector register.  An atomic at a wave-uniform address inside divergent code is rewritten by the
-    // compiler into "one lane adds, v_readfirstlane hands the result round" - and that read waits for the ticket on the spot, with the rows
-    // below queued behind it.  The only read of the ticket is the one at the end of the tile.)
-    int next2_tile = 0x3fffffff;
-    if (third_round) {
-        int64_t ctr_off = 0;
-        if constexpr (AHEAD) asm volatile("" : "+v"(ctr_off));
-        if constexpr (AHEAD) { if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr + ctr_off, 1); }      // (+ 2 W where it is read)
-        else if (lane == 0) next2_tile = atomicAdd(a0.tile_ctr, 1) + 2 * W_launch;
-    }
+    int next2_tile = fused_draw_ticket<AHEAD>(a0, third_round, W_launch, lane);
     int ip_next = 0, src_next = 0;
     float w_next = 0.0f;
     if constexpr (AHEAD) { }                                  // (header and batch-0 entry of the next tile: read with this tile's last gather batch)
@@ -1708,36 +1851,30 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         if (hdr_nb_next > 0) ent_next = prog_entry(a, hdr_first_next, lane);      // (header of the next tile: read behind the gather)
     } else {
         ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
-        if (FULL || Ds == 64) tile_first_ids(a, ip_next, lane, src_next, w_next);
+        tile_first_ids(a, ip_next, lane, src_next, w_next);
     }
     if constexpr (!AHEAD && SPLIT && PC == 2) gnn_flag_raise_range(a.flag_out, mx);
     GnnFlagPeek peek = {0, 0, 0};                             // the gate words of this wave's slot: on their way across the epilogue arithmetic
-    if (SPLIT && NTL == 2 && lane == 0) peek = gnn_flag_peek(a.flag_out);
+    if (SPLIT && lane == 0) peek = gnn_flag_peek(a.flag_out);
     if constexpr (AHEAD) {
         __builtin_amdgcn_sched_barrier(0);                    // (the scheduler is free to move a load in front of an earlier one)
         prog_first_batch_request(a, hdr_first_next, hdr_nb_next, ent_next, lane, x_first, ent_second);
         __builtin_amdgcn_sched_barrier(0);
     }
-    bool finished = false;
-    if constexpr (SPLIT && NTL == 2) {
-        if (fast64) {                                         // registers -> norms, LDS (16-byte pieces), row stores
-#pragma unroll
-            for (int jt = 0; jt < NTL; ++jt) {
-                if (a.bn_scale) tile_epilogue_last<ACTL, true, true, true, true>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, a.usc[LAYERS - 1]);
-                else tile_epilogue_last<ACTL, false, true, true, true>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, a.usc[LAYERS - 1]);
-            }
-            GNN_STAMP(6);
-            if (nvalid == 32) finish_fast64_aligned<AHEAD>(a, X, out, i0, lane, KP, c_aggs, peek);
-            else finish_fast64_partial(a, X, out, i0, lane, KP, c_aggs, nvalid);       // (full-tile kernel on the range's last, partial tile)
-            finished = true;
-        }
-    }
-    if (!(FULL && SPLIT && NTL == 2) && !finished) {
+    if constexpr (SPLIT) {                                    // registers -> norms, LDS (16-byte pieces), row stores
 #pragma unroll
         for (int jt = 0; jt < NTL; ++jt) {
-            const float us = SPLIT ? a.usc[LAYERS - 1] : 1.0f;
-            if (a.bn_scale) tile_epilogue_last<ACTL, true, SPLIT, true, SPLIT>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, us);
-            else tile_epilogue_last<ACTL, false, SPLIT, true, SPLIT>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, us);
+            if (a.bn_scale) tile_epilogue_last<ACTL, true, true, true, true>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, a.usc[LAYERS - 1]);
+            else tile_epilogue_last<ACTL, false, true, true, true>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, a.usc[LAYERS - 1]);
+        }
+        GNN_STAMP(6);
+        if (nvalid == 32) finish_fast64_aligned<AHEAD>(a, X, out, i0, lane, KP, c_aggs, peek);
+        else finish_fast64_partial(a, X, out, i0, lane, KP, c_aggs, nvalid);       // (the range's last, partial tile)
+    } else {
+#pragma unroll
+        for (int jt = 0; jt < NTL; ++jt) {
+            if (a.bn_scale) tile_epilogue_last<ACTL, true, false, true, false>(a.act_last, out[jt], ep, ep + 32 * NTL, ep + 64 * NTL, jt, half, 1 << 30, 1.0f);
+            else tile_epilogue_last<ACTL, false, false, true, false>(a.act_last, out[jt], ep, nullptr, nullptr, jt, half, 1 << 30, 1.0f);
             float *x = X + (lane & 31) * KP + c_aggs;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1747,71 +1884,80 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused(const GnnFusedAr
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         GNN_STAMP(6);
-        if constexpr (FULL) {
-            if (nvalid == 32) check_store_fast64(a, X, i0, lane, KP, c_aggs);
-            else check_store_fast64_partial(a, X, i0, lane, KP, c_aggs, nvalid);
-        } else {
-            if (fast64) check_store_fast64(a, X, i0, lane, KP, c_aggs);
-            else check_store_generic(a, X, i0, lane, nvalid, KP, c_aggs);
-        }
+        if (nvalid == 32) check_store_fast64(a, X, i0, lane, KP, c_aggs);
+        else check_store_fast64_partial(a, X, i0, lane, KP, c_aggs, nvalid);
     }
     GNN_STAMP(7);
-#undef GNN_STAMP
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next tile re-uses this wave's LDS region
     tile = next_tile;
-    if constexpr (AHEAD) {
-        asm volatile("" : "+v"(next2_tile));                    // first look at the ticket: here
-        next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + (third_round ? 2 * W_launch : 0) + a0.tile_base;
-    } else next_tile = __builtin_amdgcn_readfirstlane(next2_tile) + a0.tile_base;
+    next_tile = fused_next_tile<AHEAD>(a0, next2_tile, third_round, W_launch);
     ip_cur = ip_next; src_cur = src_next; w_cur = w_next;
     hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; tid = tid_next; ent_cur = ent_next;
   }
 }
+#undef GNN_STAMP
+#undef GNN_FUSED_DENSE_LAYERS
 
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL, bool FULL, bool GIVEN = false, int PC = 3, bool PROG = false>
-inline void launch_one_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+// ---- launchers: one short chain per kernel, dispatching on the form of the launch (GnnFusedLaunch, gnn_fused.h) ----
+template <auto KERNEL>
+inline void launch_kernel(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    // the full-tile gathering kernel exists in both gather forms; the launch carries a program (gp_tiles > 0) when form 2 was chosen for it
-    if constexpr (FULL && !GIVEN && !PROG) {
-        if (a.gp_tiles > 0) { launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, ACTL, FULL, GIVEN, PC, true>(a, grid, lds_bytes, st); return; }
-    }
     static bool lds_raised[64] = {false};   // (one table per instantiation)
-    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG, ACTL>), 160 * 1024, lds_raised);
-    hipLaunchKernelGGL((k_fused<LAYERS, NT, NTL, ACT, SPLIT, FULL, GIVEN, PC, PROG, ACTL>), grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);
-}
-// the split arithmetic in the piece format of the launch (a.pieces); the exact path has one
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL, bool FULL, bool GIVEN = false>
-inline void launch_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
-{
-    if (SPLIT && a.pieces == 2) launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, ACTL, FULL, GIVEN, 2>(a, grid, lds_bytes, st);
-    else launch_one_pc<LAYERS, NT, NTL, ACT, SPLIT, ACTL, FULL, GIVEN, 3>(a, grid, lds_bytes, st);
+    (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(KERNEL), 160 * 1024, lds_raised);
+    hipLaunchKernelGGL(KERNEL, grid, GNN_FUSED_THREADS, lds_bytes, st, a);
 }
 
-// a.full_tiles: the host asks for the full-tile specialisation (state width 64); it exists for NTL == 2
+// k_fused_generic in the piece format of the launch (the exact path has one)
 template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL>
-inline void launch(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+inline void launch_generic_pc(const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    if constexpr (NTL == 2) {
-        if (a.full_tiles && a.agg_in) { launch_one<LAYERS, NT, NTL, ACT, SPLIT, ACTL, true, true>(a, grid, lds_bytes, st); return; }
-        if (a.full_tiles) { launch_one<LAYERS, NT, NTL, ACT, SPLIT, ACTL, true>(a, grid, lds_bytes, st); return; }
-    }
-    launch_one<LAYERS, NT, NTL, ACT, SPLIT, ACTL, false>(a, grid, lds_bytes, st);
+    if (SPLIT && how.pieces == 2) launch_kernel<k_fused_generic<LAYERS, NT, NTL, ACT, SPLIT, 2, ACTL>>(a, grid, lds_bytes, st);
+    else launch_kernel<k_fused_generic<LAYERS, NT, NTL, ACT, SPLIT, 3, ACTL>>(a, grid, lds_bytes, st);
 }
-
 // (NT, NTL) pairs that are instantiated; gnn_fused.hip rounds every net up to one of them
-template <int LAYERS, int ACT, bool SPLIT, int ACTL = ACT>
-inline bool launch_tiles(int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+template <int LAYERS, int ACT, bool SPLIT, int ACTL>
+inline bool launch_generic(int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
+    // unreachable: make_plan sets NTL = round_tiles(Ds), so a state width of 64 has NTL == 2, and gnn_loop_decide_form gives every such
+    // loop the full-tile or the pair kernel.  k_fused_generic has none of the width-64 paths.
+    if (a.Ds == 64) return false;
     if constexpr (LAYERS == 1) {
-        if (ntl == 1) launch<1, 1, 1, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
-        else if (ntl == 2) launch<1, 2, 2, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
-        else if (ntl == 4) launch<1, 4, 4, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        if (ntl == 1) launch_generic_pc<1, 1, 1, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else if (ntl == 2) launch_generic_pc<1, 2, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else if (ntl == 4) launch_generic_pc<1, 4, 4, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
         else return false;
     } else {
-        if (nt == 1 && ntl == 1) launch<LAYERS, 1, 1, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
-        else if (nt == 2 && ntl == 2) launch<LAYERS, 2, 2, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
-        else if (nt == 4 && ntl == 2) launch<LAYERS, 4, 2, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
-        else if (nt == 4 && ntl == 4) launch<LAYERS, 4, 4, ACT, SPLIT, ACTL>(a, grid, lds_bytes, st);
+        if (nt == 1 && ntl == 1) launch_generic_pc<LAYERS, 1, 1, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else if (nt == 2 && ntl == 2) launch_generic_pc<LAYERS, 2, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else if (nt == 4 && ntl == 2) launch_generic_pc<LAYERS, 4, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else if (nt == 4 && ntl == 4) launch_generic_pc<LAYERS, 4, 4, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else return false;
+    }
+    return true;
+}
+
+// k_fused_full in the launch's gather form - a given aggregate, the graph's program, or the CSR walk - and piece format
+template <int LAYERS, int NT, int ACT, bool SPLIT, int ACTL>
+inline void launch_full_form(const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+{
+    auto gather_form = [&](auto P) {
+        constexpr int PC = P.value;
+        if (how.given) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, true, PC, false, ACTL>>(a, grid, lds_bytes, st);
+        else if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, true, ACTL>>(a, grid, lds_bytes, st);
+        else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, false, ACTL>>(a, grid, lds_bytes, st);
+    };
+    if (SPLIT && how.pieces == 2) gather_form(std::integral_constant<int, 2>{});
+    else gather_form(std::integral_constant<int, 3>{});      // (the exact path has one)
+}
+// the last layer has 2 tiles; hidden layers of 2 or 4
+template <int LAYERS, int ACT, bool SPLIT, int ACTL>
+inline bool launch_full(int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+{
+    if (ntl != 2) return false;
+    if constexpr (LAYERS == 1) launch_full_form<1, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+    else {
+        if (nt == 2) launch_full_form<LAYERS, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        else if (nt == 4) launch_full_form<LAYERS, 4, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
         else return false;
     }
     return true;
@@ -1832,18 +1978,17 @@ inline bool dispatch_act(int act, F &&f)
     }
 }
 
-template <int LAYERS, bool SPLIT>
-inline bool launch_act(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+// The entry of a translation unit: the instantiations of LAYERS layers in one arithmetic mode, for every hidden activation act.
+// MIXED: the last layer reads its activation from a.act_last (a net whose last layer has its own), else it is act
+template <int LAYERS, bool SPLIT, bool MIXED = false>
+inline bool launch_fused(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    return dispatch_act(act, [&](auto A) { return launch_tiles<LAYERS, A.value, SPLIT>(nt, ntl, a, grid, lds_bytes, st); });
-}
-
-// the instantiations of hidden activation act whose last layer reads its activation from a.act_last
-template <int LAYERS, bool SPLIT>
-inline bool launch_act_mixed(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
-{
-    static_assert(LAYERS >= 2, "a one-layer net has one activation");
-    return dispatch_act(act, [&](auto A) { return launch_tiles<LAYERS, A.value, SPLIT, GNN_ACTL_FROM_ARGS>(nt, ntl, a, grid, lds_bytes, st); });
+    static_assert(!MIXED || LAYERS >= 2, "a one-layer net has one activation");
+    return dispatch_act(act, [&](auto A) {
+        constexpr int ACT = A.value, ACTL = MIXED ? GNN_ACTL_FROM_ARGS : ACT;
+        return how.full ? launch_full<LAYERS, ACT, SPLIT, ACTL>(nt, ntl, how, a, grid, lds_bytes, st)
+                        : launch_generic<LAYERS, ACT, SPLIT, ACTL>(nt, ntl, how, a, grid, lds_bytes, st);
+    });
 }
 
 }   // namespace gnn_fused_dev

@@ -1,7 +1,7 @@
 // Instantiations of the fused iteration kernel for net_state with 2 Dense layer(s).
 #include "gnn_fused_kernel.h"
 
-bool gnn_fused_launch_l2(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+bool gnn_fused_launch_l2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    return gnn_fused_dev::launch_act<2, false>(act, nt, ntl, a, grid, lds_bytes, st);
+    return gnn_fused_dev::launch_fused<2, false>(act, nt, ntl, how, a, grid, lds_bytes, st);
 }

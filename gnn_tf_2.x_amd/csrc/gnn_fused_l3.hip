@@ -1,7 +1,7 @@
 // Instantiations of the fused iteration kernel for net_state with 3 Dense layer(s).
 #include "gnn_fused_kernel.h"
 
-bool gnn_fused_launch_l3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+bool gnn_fused_launch_l3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    return gnn_fused_dev::launch_act<3, false>(act, nt, ntl, a, grid, lds_bytes, st);
+    return gnn_fused_dev::launch_fused<3, false>(act, nt, ntl, how, a, grid, lds_bytes, st);
 }

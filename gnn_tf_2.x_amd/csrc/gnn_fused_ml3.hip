@@ -2,7 +2,7 @@
 // activation of its own (ACTL == GNN_ACTL_FROM_ARGS): one kernel per hidden activation, the last one from GnnFusedArgs::act_last.
 #include "gnn_fused_kernel.h"
 
-bool gnn_fused_launch_ml3(int act, int nt, int ntl, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+bool gnn_fused_launch_ml3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    return gnn_fused_dev::launch_act_mixed<3, false>(act, nt, ntl, a, grid, lds_bytes, st);
+    return gnn_fused_dev::launch_fused<3, false, true>(act, nt, ntl, how, a, grid, lds_bytes, st);
 }

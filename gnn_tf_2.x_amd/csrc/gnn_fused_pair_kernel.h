@@ -1,6 +1,6 @@
 // Fused iteration kernel, WAVE-PAIR form (round 5; device code).  Included by gnn_fused_p{2,3}.hip.
 //
-// Same contract as k_fused<.., SPLIT = true, FULL = true, .., PC> (gnn_fused_kernel.h): one launch = one iteration of GNN.Loop (reference
+// Same contract as k_fused_full<.., SPLIT = true, .., PC> (gnn_fused_kernel.h): one launch = one iteration of GNN.Loop (reference
 // GNN/GNN.py:223-242 + :202-220) in the split arithmetic of the default path (fp32 operands as three exact bf16 pieces on
 // v_mfma_f32_32x32x16_bf16), state width 64, 128-wide hidden layers, identical results bit for bit.  What changes is who does what:
 //
@@ -454,17 +454,18 @@ inline void launch_pair_pc(const GnnFusedArgs &a, unsigned grid, size_t lds_byte
     (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(&k_fused_pair<LAYERS, ACT, PC>), 160 * 1024, lds_raised);
     hipLaunchKernelGGL((k_fused_pair<LAYERS, ACT, PC>), grid, GNN_FUSED_THREADS, lds_bytes, st, a);
 }
+// pieces: the piece format of the launch (LoopForm::pieces)
 template <int LAYERS, int ACT>
-inline void launch_pair_one(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+inline void launch_pair_one(int pieces, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    if (a.pieces == 2) launch_pair_pc<LAYERS, ACT, 2>(a, grid, lds_bytes, st);
+    if (pieces == 2) launch_pair_pc<LAYERS, ACT, 2>(a, grid, lds_bytes, st);
     else launch_pair_pc<LAYERS, ACT, 3>(a, grid, lds_bytes, st);
 }
 
 template <int LAYERS>
-inline bool launch_pair_act(int act, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+inline bool launch_pair_act(int act, int pieces, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    return dispatch_act(act, [&](auto A) { launch_pair_one<LAYERS, A.value>(a, grid, lds_bytes, st); return true; });
+    return dispatch_act(act, [&](auto A) { launch_pair_one<LAYERS, A.value>(pieces, a, grid, lds_bytes, st); return true; });
 }
 
 }   // namespace gnn_fused_dev

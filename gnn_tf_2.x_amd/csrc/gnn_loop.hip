@@ -389,6 +389,14 @@ extern "C" int gnn_loop_set_tile_form(gnn_loop *l, int form, int *used)
     return rc;
 }
 
+extern "C" int gnn_loop_body_kernel(gnn_loop *l, int *kernel)
+{
+    ARGCHK(l && kernel, "bad arguments");
+    const int rc = gnn_loop_decide_form(l);
+    *kernel = l->form.path == GNN_PATH_UNFUSED ? 0 : l->form.kernel + 1;
+    return rc;
+}
+
 extern "C" int gnn_loop_set_gather_form(gnn_loop *l, int form, int *used)
 {
     ARGCHK(l && form >= 0 && form <= 2, "form must be 0 (library's choice), 1 (walk the CSR) or 2 (the graph's gather program)");

@@ -391,7 +391,7 @@ void gnn_split_f16(const float *v, int n, int e, uint16_t *p0, uint16_t *p1);
 int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used);
 /* Which form of the fused iteration kernel runs the bodies of GNN/GNN.py:223-242 on the default path (impl 2) when both cover the
  * net (state width 64, two or three Dense layers, 128-wide hidden layers, concat width 129 .. 144, no feature-sliced exchange):
- *   form 1  one wave owns a 32-node tile from gather to store (k_fused);
+ *   form 1  one wave owns a 32-node tile from gather to store (k_fused_full);
  *   form 2  a wave PAIR shares the tile, each wave gathering 16 of its nodes and producing half of every layer's output features
  *           (k_fused_pair);
  *   form 0  the library's choice (default).
@@ -400,6 +400,10 @@ int gnn_loop_set_persistent(gnn_loop *l, int enable, int *used);
  * The two forms evaluate the same arithmetic per node: states, outputs and k are identical bit for bit.  *used (may be NULL) = the form
  * the next run will take (1 or 2; 0 when the fused path does not cover the loop at all). */
 int gnn_loop_set_tile_form(gnn_loop *l, int form, int *used);
+/* The per-body kernel the next run takes as the loop's settings stand (on the persistent path: what a run with one launch per body would
+ * take): *kernel = 0 the fused path does not cover the loop, 1 k_fused_generic (any state width but 64), 2 k_fused_full (state width 64),
+ * 3 k_fused_pair.  A loop with state width 64 never reports 1: k_fused_generic has none of the width-64 paths. */
+int gnn_loop_body_kernel(gnn_loop *l, int *kernel);
 /* How the full-tile form-1 kernel (state width 64, impl 1 or 2, no feature-sliced exchange) finds a tile's neighbour rows:
  *   form 1  it walks the CSR: row pointers, then ids / weights in batches of 16 per lane group of 8 rows, row ends found by comparison;
  *   form 2  it reads the graph's gather program: the CSR walked once per graph and stored per tile and lane group in the order of

@@ -128,3 +128,47 @@ def test_persistent_form_follows_its_setters_on_one_handle():
     assert lp.timing()['n_iter_timed'] == c.last_k > 0                                  # (its bodies were timed one by one)
     lp.close()
     c.graph.close()
+
+
+@pytest.mark.parametrize('hidden', [(), (48,), (128,), (128, 128)])
+def test_state_width_64_never_takes_the_generic_kernel(hidden):
+    """k_fused_generic has none of the width-64 paths (csrc/gnn_fused_kernel.h; its launcher refuses the width): a loop with state width
+    64 reports k_fused_full or k_fused_pair in every mode the setters allow - impl 1 or 2, every tile form, the feature-sliced exchange on
+    and off (two ranks over the loopback transport), every gather form - and on one GPU with and without the persistent path."""
+    from test_gpu_sharded import _case, _csr_parts, _sharded_loops
+    e = _engine()
+    n, d = 333, 64
+    g, st, ou, s0 = _case(64 + len(hidden), n, d, hidden=hidden)
+    indptr, adj_src, adj_w, _, _ = _csr_parts(g)
+    comms, graphs, loops, _ = _sharded_loops(e, g, st, ou, d, 5, 0.01, s0, 2, 1)
+    for gr in graphs: gr.set_full_adjacency(n, indptr, adj_src, adj_w)
+    seen = set()
+    for lp in loops:
+        for sliced in (False, True):
+            lp.set_slice_exchange(sliced)
+            for impl in (1, 2):
+                assert lp.set_impl(impl) == impl
+                for tile_form in (0, 1, 2):
+                    lp.set_tile_form(tile_form)
+                    for gather_form in (0, 1, 2):
+                        lp.set_gather_form(gather_form)
+                        kernel = lp.body_kernel()
+                        assert kernel in (2, 3), (sliced, impl, tile_form, gather_form, kernel)
+                        seen.add(kernel)
+    for lp in loops: lp.close()
+    for c in comms: c.close()
+    case = Case(333, 64, hidden, 11)
+    lp, _ = case.loop(case.st)
+    for impl in (1, 2):
+        assert lp.set_impl(impl) == impl
+        for persistent in (True, False):
+            lp.set_persistent(persistent)
+            for tile_form in (0, 1, 2):
+                lp.set_tile_form(tile_form)
+                for gather_form in (0, 1, 2):
+                    lp.set_gather_form(gather_form)
+                    kernel = lp.body_kernel()
+                    assert kernel in (2, 3), (impl, persistent, tile_form, gather_form, kernel)
+                    seen.add(kernel)
+    lp.close()
+    assert 2 in seen and (3 in seen) == (hidden in ((128,), (128, 128)))      # the pair covers 128-wide hidden layers only

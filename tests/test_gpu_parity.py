@@ -616,6 +616,33 @@ def test_wide_states_and_fallback(d, hidden, expect_fused):
         f'k {k} (oracle {kc}), max |state - oracle| {err}, NaNs {int(np.isnan(s2).sum())}, rows off by > 1e-5: {np.nonzero(np.max(np.abs(s2 - sc), axis=1) > 1e-5)[0][:20]}'
 
 
+@pytest.mark.parametrize('n', [320, 333])
+@pytest.mark.parametrize('hidden', [(), (128,), (128, 128)])
+@pytest.mark.parametrize('d', [33, 48, 63])
+def test_generic_kernel_just_below_the_tuned_width(d, hidden, n):
+    """k_fused_generic with two feature tiles in the last layer (NTL == 2, as the state width 64 of k_fused_full has) at widths that are
+    and are not a multiple of 4, one to three layers with 128-wide hidden layers, a whole (n = 320) and a partial (n = 333) last tile, one
+    launch per body: impl 1 bit for bit against the C oracle, impl 2 the same k and the bound of test_wide_states_and_fallback in both
+    piece formats."""
+    e = _engine()
+    rng = np.random.default_rng(4100 + 10 * d + len(hidden) + n)
+    g, st, ou, s0 = _case(rng, n=n, d=d, nl=3, al=2, hidden=hidden, act='tanh', gain=0.5)
+    kc, sc, oc = corc.loop_node(g, st, ou, d, 10, 0.01, s0)
+    loop = e.Loop(_device_graph(g), e.Mlp(st['weights'], st['activations'], True), e.Mlp(ou['weights'], ou['activations'], True), d, 10, 0.01)
+    assert loop.set_impl(1) == 1 and loop.set_persistent(False) is False and loop.body_kernel() == 1
+    loop.set_state0(s0)
+    k = loop.run()
+    assert k == kc and np.array_equal(loop.state(), sc) and np.array_equal(loop.output(), oc)
+    assert loop.set_impl(2) == 2 and loop.body_kernel() == 1
+    for pieces in (2, 3):
+        assert loop.set_pieces(pieces) == pieces
+        k = loop.run()
+        s2 = loop.state()
+        err = float(np.max(np.abs(s2 - sc)))
+        assert k == kc and err < 2e-6 * max(1.0, float(np.max(np.abs(sc)))), \
+            f'pieces {pieces}: k {k} (oracle {kc}), max |state - oracle| {err}, NaNs {int(np.isnan(s2).sum())}'
+
+
 @pytest.mark.parametrize('d,nl,al,hidden,act,n', [(0, 14, 3, (32, 32), 'selu', 970), (0, 3, 1, (), 'selu', 880), (8, 3, 2, (16,), 'tanh', 4099),
                                                    (5, 2, 1, (7, 9), 'relu', 33), (16, 3, 1, (24,), 'sigmoid', 8192),
                                                    (24, 3, 2, (32, 20), 'selu', 700), (20, 2, 1, (16,), 'tanh', 5000)])

@@ -11,6 +11,7 @@ from oracle import c_oracle as corc
 from oracle import gnn_oracle as orc
 from test_gpu_gather_program import (DS, MODES, NL, bits_equal, device_graph, graph_from_degrees, make_loop, nets)
 from test_tile_schedule_host import tile_costs
+from util import make_mlp
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +149,43 @@ def test_ticket_rounds_and_hubs(name, impl, pieces):
     order) and in tile 0.  One body."""
     g, st, ou, s0, oracle = case(name)
     check(run_schedules(_engine(), g, st, ou, 1, s0, impl, pieces), impl, oracle)
+
+
+GENERIC = {}
+
+
+def generic_case(ds):
+    """The 'tickets' graph under a net_state of state width ds with one 32-wide hidden layer, and the C oracle's result after one body:
+    built once per width, shared by the modes, never modified."""
+    if ds not in GENERIC:
+        g = case('tickets')[0]
+        rng = np.random.default_rng(9000 + ds)
+        st = make_mlp(rng, 1 + 2 * (ds + NL), [32, ds], 'selu', gain=0.6, bn_random=True)
+        ou = make_mlp(rng, ds + NL, [2], 'softmax', bn_random=True)
+        s0 = (0.1 * rng.standard_normal((N_LARGE, ds))).astype(np.float32)
+        GENERIC[ds] = (g, st, ou, s0, corc.loop_node(g, st, ou, ds, 1, 0.0, s0))
+    return GENERIC[ds]
+
+
+@pytest.mark.parametrize('impl', [1, 2])
+@pytest.mark.parametrize('ds', [32, 48])
+def test_ticket_round_of_the_generic_kernel(ds, impl):
+    """k_fused_generic (state widths 32: one feature tile, and 48: two) on the 2 W + 3 full tiles and a partial one of 'tickets': the two
+    static rounds and one round of tickets drawn through the functions it shares with k_fused_full.  One body against the C oracle: impl 1
+    bit for bit, impl 2 the same k and a state within 2e-6 relative."""
+    e = _engine()
+    g, st, ou, s0, (kc, sc, oc) = generic_case(ds)
+    assert 2 * W * 32 < g['nodes'].shape[0] == N_LARGE
+    graph = device_graph(e, g)
+    lp = e.Loop(graph, e.Mlp(st['weights'], st['activations'], True), e.Mlp(ou['weights'], ou['activations'], True), ds, 1, 0.0)
+    assert lp.set_impl(impl) == impl and lp.body_kernel() == 1
+    lp.set_state0(s0)
+    k, s, o = lp.run(), lp.state(), lp.output()
+    lp.close(); graph.close()
+    if impl == 1: assert k == kc and np.array_equal(s, sc) and np.array_equal(o, oc)
+    else:
+        err = float(np.max(np.abs(s - sc)))
+        assert k == kc and err < 2e-6 * max(1.0, float(np.max(np.abs(sc)))), f'max |state - oracle| {err}, NaNs {int(np.isnan(s).sum())}'
 
 
 @pytest.mark.parametrize('impl,pieces', MODES)

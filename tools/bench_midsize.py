@@ -1,7 +1,9 @@
 """Per-iteration time of the fused kernel across graph sizes (latency-bound to throughput-bound): the bench workload's generator,
 weights and arithmetic at N nodes.  Prints ms per iteration (HIP events around every launch), the algorithmic TB/s and the fraction of
-the 8 TB/s roof.  GNN_TILE_FORM=1 / 2 forces one wave per tile (k_fused) / a wave pair per tile (k_fused_pair) on the default path; 0 (default) is the
-library's choice.     python tools/bench_midsize.py [N ...]"""
+the 8 TB/s roof.  GNN_TILE_FORM=1 / 2 forces one wave per tile (k_fused_full) / a wave pair per tile (k_fused_pair) on the default path; 0 (default) is the
+library's choice.  --state-width D (default 64, the bench workload's) sets the state width and with it net_state's input width
+1 + 2 (3 + D): any other width times k_fused_generic.     python tools/bench_midsize.py [--state-width D] [N ...]"""
+import argparse
 import os
 import sys
 
@@ -15,13 +17,17 @@ import bench                                           # noqa: E402
 
 
 def main():
-    sizes = [int(x) for x in sys.argv[1:]] or [31_250, 62_500, 125_000, 250_000, 500_000, 1_000_000]
-    d, nl, al, t = 64, 3, 1, 2
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--state-width', type=int, default=64)
+    ap.add_argument('sizes', type=int, nargs='*')
+    args = ap.parse_args()
+    sizes = args.sizes or [31_250, 62_500, 125_000, 250_000, 500_000, 1_000_000]
+    d, nl, al, t = args.state_width, 3, 1, 2
     rng = np.random.default_rng(20261003)
     st = bench.make_net(rng, al + 2 * (nl + d), [128, 128, d], 'selu')
     ou = bench.make_net(rng, nl + d, [t], 'softmax')
     mst, mou = e.Mlp(st['weights'], st['activations'], True), e.Mlp(ou['weights'], ou['activations'], True)
-    print(f'# GNN_TILE_FORM={os.environ.get("GNN_TILE_FORM", "0")} library={os.path.basename(e.LIB_PATH)}')
+    print(f'# state width {d} GNN_TILE_FORM={os.environ.get("GNN_TILE_FORM", "0")} library={os.path.basename(e.LIB_PATH)}')
     for n in sizes:
         s = utils.syntheticGraph(n, 10.0, nl, al, t, seed=20261003)
         n = s['n_nodes']
