@@ -43,6 +43,18 @@ class GNNnodeBased(BaseClass):
         self.gradient_mode = 'unrolled'     # set_gradient_mode
         self.adjoint_max_iteration = None
         self.adjoint_threshold = None
+        self.label_projection = 'off'       # set_label_projection
+
+    def set_label_projection(self, mode) -> None:
+        """The fused Loop for wide node / arc labels.  The fused kernels hold a node's whole net_state input in on-chip memory, which
+        caps it at about 144 columns (with state_vect_dim 64: about 7 node-label columns); wider inputs run one kernel per operation.
+        With the projection the label terms of net_state's first layer are computed once per Loop and every iteration runs that layer
+        over [state | aggregated state] only.  'off' / 0 (default), 'auto' / 1: where the fused path does not cover the net as it
+        stands, 'always' / 2: wherever applicable.  A form of the default arithmetic (impl 2): states and outputs within 1e-5 of the
+        reference, the iteration count the exact one; impl 1 / 0 and training-mode Loops run as without it.  Kept by copy() (so by LKO)
+        and by save() / load()."""
+        code = _engine.label_projection_mode(mode)
+        self.label_projection = {v: k for k, v in _engine.LABEL_PROJECTION_MODES.items()}[code]
 
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
         """How train() differentiates the state loop.  'unrolled' (default): back-propagation through every executed body.
@@ -77,6 +89,7 @@ class GNNnodeBased(BaseClass):
                              extra_metrics_arguments=self.mt_args, state_vect_dim=self.state_vect_dim,
                              path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
         new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
+        new.set_label_projection(self.label_projection)
         return new
 
     def save(self, path: str):
@@ -96,7 +109,7 @@ class GNNnodeBased(BaseClass):
             json.dump({'loss_function': loss_name if hasattr(losses, str(loss_name)) else None, 'loss_arguments': self.loss_args,
                        'optimizer': optimizers.serialize(self.optimizer), 'max_iteration': self.max_iteration, 'threshold': self.state_threshold,
                        'addressed_problem': self.addressed_problem, 'state_vect_dim': self.state_vect_dim,
-                       'gradient_mode': self._gradient_config()}, f)
+                       'gradient_mode': self._gradient_config(), 'label_projection': self.label_projection}, f)
 
     @classmethod
     def load(cls, path: str, path_writer=None, namespace: str = 'GNN', extra_metrics=None, extra_metrics_arguments=None):
@@ -112,6 +125,7 @@ class GNNnodeBased(BaseClass):
         loss_name = config.pop('loss_function', None)
         loss = getattr(losses, loss_name) if loss_name else None
         gradient = config.pop('gradient_mode', None) or {'mode': 'unrolled'}      # (a model saved before the mode existed: unrolled)
+        projection = config.pop('label_projection', None) or 'off'                # (a model saved before the key existed: off)
         nets = []
         for name in ('net_state', 'net_output'):
             with open(f'{path}{name}.json') as f:
@@ -122,6 +136,7 @@ class GNNnodeBased(BaseClass):
         model = cls(net_state=nets[0], net_output=nets[1], optimizer=optz, loss_function=loss, extra_metrics=extra_metrics,
                     extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
         model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'))
+        model.set_label_projection(projection)
         return model
 
     def get_dense_layers(self):
@@ -170,6 +185,9 @@ class GNNnodeBased(BaseClass):
         if getattr(loop, '_gradient_set', ('unrolled', None, None)) != gradient:
             loop.set_gradient_mode(*gradient)
             loop._gradient_set = gradient
+        if getattr(loop, '_projection_set', 'off') != self.label_projection:
+            loop.set_label_projection(self.label_projection)
+            loop._projection_set = self.label_projection
         return loop
 
     def _prerun(self, graphs) -> list:

@@ -35,6 +35,10 @@ class LGNN(BaseClass):
             gnn.namespace = [name]
             gnn.path_writer = f'{self.path_writer}{name}/'
 
+    def set_label_projection(self, mode) -> None:
+        """GNNnodeBased.set_label_projection for every layer (the layers behind the first see labels widened by states / outputs)."""
+        for gnn in self.gnns: gnn.set_label_projection(mode)
+
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
         """GNNnodeBased.set_gradient_mode for every layer.  'serial' training runs the layers' own steps and works in both modes; the joint
         steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' does not return:

@@ -24,7 +24,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
-           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
+           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
 
@@ -112,6 +112,33 @@ def small_form(dims, activations, n_rows, nlc=0) -> dict:
     out = np.zeros(3, np.int32)
     _check(lib().gnn_small_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(nlc)), C.c_int64(int(n_rows)), _ip(out)))
     return dict(persistent=bool(out[0]), tile=int(out[0]), wide=bool(out[1]), steps=int(out[2]))
+
+
+LABEL_PROJECTION_MODES = {'off': 0, 'auto': 1, 'always': 2}      # modes of gnn_loop_set_label_projection
+
+
+def label_projection_mode(mode) -> int:
+    """'off' | 'auto' | 'always' or 0 | 1 | 2 -> the mode code of gnn_loop_set_label_projection."""
+    if isinstance(mode, str):
+        if mode not in LABEL_PROJECTION_MODES: raise ValueError("param <mode> not in ['off', 'auto', 'always']")
+        return LABEL_PROJECTION_MODES[mode]
+    if isinstance(mode, bool) or int(mode) != mode or int(mode) not in (0, 1, 2): raise ValueError('param <mode> not in [0, 1, 2]')
+    return int(mode)
+
+
+def label_projection_form(dims, activations, state_dim, nl, al, n_rows, mode) -> dict:
+    """gnn_label_projection_form (host code, no device): what Loop.set_label_projection(mode) answers for a net_state of this description
+    (dims[0]: the whole concat) with state width state_dim, nl node-label columns in the concat and al arc-label columns on n_rows owned
+    nodes - dict(seeded; kernel: 0, or 1 = k_fused_generic, 2 = k_fused_full; iw: projected label columns; tiles: 32-feature tiles of P).
+    impl 2, a single GPU, no feature-sliced exchange and not profiling are the loop's part, taken at their defaults."""
+    L = len(dims) - 1
+    if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
+    d = np.ascontiguousarray(dims, np.int32)
+    a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
+    out = np.zeros(4, np.int32)
+    _check(lib().gnn_label_projection_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(state_dim)), C.c_int(int(nl)), C.c_int(int(al)),
+                                           C.c_int64(int(n_rows)), C.c_int(label_projection_mode(mode)), _ip(out)))
+    return dict(seeded=bool(out[0]), kernel=int(out[1]), iw=int(out[2]), tiles=int(out[3]))
 
 
 TRAIN_PERSISTENT_MAX_BYTES = 256 << 20      # GNN_TRAIN_PERSISTENT_MAX_BYTES of include/gnn_hip.h
@@ -869,6 +896,21 @@ class Loop:
         used = C.c_int(0)
         _check(lib().gnn_loop_set_tile_schedule(self._h, C.c_int(int(kind)), C.byref(used)))
         return used.value
+
+    def set_label_projection(self, mode) -> bool:
+        """gnn_loop_set_label_projection: the fused Loop for wide labels - the label terms of net_state's first layer computed once per
+        Loop, every body's first layer over [state | aggregated state] only.  'off' / 0 (default), 'auto' / 1 (where the fused path does
+        not cover the net as it stands), 'always' / 2 (wherever applicable).  Returns whether the next run takes the seeded kernels
+        (impl 2 with one launch per body only)."""
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_label_projection(self._h, C.c_int(label_projection_mode(mode)), C.byref(used)))
+        return bool(used.value)
+
+    def label_projection(self) -> np.ndarray:
+        """gnn_loop_get_label_projection (test hook): the projection the last run used, [owned rows, width of net_state's first layer]."""
+        out = np.zeros((self.n_rows, int(self._keep[1].dims[1])), np.float32)
+        _check(lib().gnn_loop_get_label_projection(self._h, _fp(out)))
+        return out
 
     def counters(self) -> dict:
         """gnn_counters_get: algorithmic bytes / FLOPs of one iteration on the owned rows, and the last run's iteration count and times."""

@@ -276,6 +276,16 @@ struct gnn_mlp {
     int pack_nlc = -1;                  // node-label columns of the concat the split image was laid out for (alignment hole)
     bool pack_dirty = true;             // the images are rebuilt on the next fused use (training rewrites the weights every step)
     uint64_t version = 0;
+    // Label projection (gnn_loop_set_label_projection; gnn_fused.hip, projection_ensure): the net over [state | aggregated state] - its
+    // first kernel the state / aggregated-state rows of W1 (its own slab), every other array this net's - with weight images of its own
+    // BESIDE the ordinary ones (a net shared by two loops may run both forms), and the label rows of W1 as a plain fp32 block
+    // [IW][32 tiles of layer 0] followed by a zero row and the layer's bias [32 tiles], zero-padded.  Built for (state width, node-label columns, arc-label
+    // width) from the weights of version proj_version.
+    gnn_mlp *proj = nullptr;
+    float *proj_wl = nullptr;
+    size_t proj_wl_floats = 0;
+    int proj_ds = -1, proj_nlc = -1, proj_al = -1;
+    uint64_t proj_version = ~(uint64_t)0;
 };
 
 // In-process loopback group (gnn_comm_create_loopback): `world` communicators on ONE device that share one stream; the
@@ -339,6 +349,14 @@ struct gnn_loop {
     float *inv = nullptr;                   // fused: loop-invariant label block [n_rows, inv_w]
     uint64_t inv_version = 0;               // label_version of the graph the block was built from
     bool inv_zeroed = false;                // the block's zero fill has been queued (by the first fused run, on the loop's stream)
+    // label projection: gnn_loop_set_label_projection's mode (0 off, 1 where needed, 2 wherever applicable); P = inv . W1_label + b1 of the
+    // owned rows in the seeded kernels' tile order (GnnFusedArgs::seed), cached like inv - built from the graph's labels of version
+    // proj_labels and net_state's weights of version proj_weights; proj_nt: 32-feature tiles per row tile it was built with
+    int label_projection = 0;
+    float *proj = nullptr;
+    size_t proj_floats = 0;
+    int proj_nt = 0;
+    uint64_t proj_labels = 0, proj_weights = ~(uint64_t)0;
     float *tmp[2] = {nullptr, nullptr};     // unfused: layer activations
     float *feats = nullptr, *out = nullptr, *otmp[2] = {nullptr, nullptr};
     int *flags = nullptr;                   // [(max_iter+2), world, GNN_FLAG_WORDS]

@@ -83,6 +83,11 @@ struct GnnFusedArgs {
     int lds_floats;
     // activation of the last layer (gnn_activation, never softmax): read by the instantiations with ACTL == GNN_ACTL_FROM_ARGS only
     int act_last;
+    // label projection (gnn_loop_set_label_projection), read by the seeded instantiations only: P = inv . W1_label + b1 of the owned rows,
+    // unscaled fp32, in accumulator-tile order [row tile][seed_nt feature tiles][q][lane][4] (gnn_label_project.hip) - the four features
+    // 32 jt + 8 q + 4 (lane >> 5) + 0..3 of node lane & 31, so that a register quad of a layer-0 accumulator tile is one 1 KiB wave load
+    const float *seed;
+    int seed_nt;
 };
 
 // control block of the persistent small-graph loop (gnn_small_common.h)
@@ -153,6 +158,7 @@ struct GnnFusedLaunch {
     bool given = false;              // ... whose aggregate is given (GnnFusedArgs::agg_in: feature-sliced exchange): no gather
     bool program = false;            // ... or which gathers from the graph's program (gp_ent / gp_slot) rather than walking the CSR
     int pieces = 3;                  // piece format of the split arithmetic
+    bool seed = false;               // the seeded instantiations (label projection): layer 0 over [state | aggregated state], started from GnnFusedArgs::seed
 };
 struct LoopForm {
     int path = GNN_PATH_UNFUSED;
@@ -161,6 +167,7 @@ struct LoopForm {
     bool split = false;              // split arithmetic (impl 2) rather than the exact f32 MFMA (impl 1)
     int pieces = 3;                  // piece format of the split arithmetic
     bool program = false;            // the full-tile kernel gathers from the graph's program
+    bool seeded = false;             // label projection in use: plan and args are those of the shadow net over [state | aggregated state]
     int schedule = 0;                // ... working through its tiles in 1 ascending / 2 the balanced order (0: no program)
     // launch constants of the path's launches
     FusedPlan plan;
@@ -236,3 +243,11 @@ bool gnn_fused_launch_ml2(int act, int nt, int ntl, const GnnFusedLaunch &how, c
 bool gnn_fused_launch_ml3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
 bool gnn_fused_launch_ms2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
 bool gnn_fused_launch_ms3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+// the seeded split-arithmetic instantiations (label projection; how.seed): one family per hidden activation, the last layer's activation from
+// a.act_last whether it is the net's own or not: gnn_fused_ps{1,2,3}.hip
+bool gnn_fused_launch_ps1(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ps2(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+bool gnn_fused_launch_ps3(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st);
+// P of n_rows rows in the layout of GnnFusedArgs::seed (gnn_label_project.hip): inv [rows padded to 32][IW], wl [IW + 1][32 nt] (last row zero) and bias [32 nt]
+// (columns past H1 zero); every element of the padded P is written
+int gnn_label_project_launch(hipStream_t st, int64_t n_rows, int IW, int nt, const float *inv, const float *wl, const float *bias, float *P);

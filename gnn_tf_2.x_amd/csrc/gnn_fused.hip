@@ -336,8 +336,128 @@ extern "C" int gnn_small_form(int n_layers, const int *dims, const int *acts, in
     return GNN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// label projection (gnn_loop_set_label_projection): layer 0 of net_state split by rows of W1
+//   state rows [0, Ds), aggregated-state rows [Ds + NLc, 2 Ds + NLc): the "shadow" net over [state | aggregated state], an ordinary plan
+//   with dims[0] = 2 Ds and no label columns, run by the seeded kernels;
+//   label rows (everything else, in the column order of l->inv): P = inv . W1_label + b1 once per Loop (gnn_label_project.hip).
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// description of the shadow net of m for state width ds (host only: widths and activations)
+void shadow_describe(const gnn_mlp *m, int ds, gnn_mlp &s)
+{
+    s.n_layers = m->n_layers;
+    s.dims = m->dims;
+    s.dims[0] = 2 * ds;
+    s.acts = m->acts;
+}
+
+// The shape part of the projection decision: the shadow plan, and whether the fused kernels cover it (make_plan, one workgroup's LDS, the
+// gather's column chunks - as gnn_fused_supported).  m->dims[0] must be the concat [state | nodes | agg state | agg nodes | agg arcs].
+bool projection_plan(const gnn_mlp *m, int ds, int nlc, int al, FusedPlan &sp)
+{
+    if (2 * nlc + al <= 0 || ds < 1 || m->dims.back() != ds || m->dims[0] != 2 * ds + 2 * nlc + al) return false;
+    gnn_mlp s;
+    shadow_describe(m, ds, s);
+    if (!make_plan(&s, 0, sp)) return false;
+    if (lds_bytes(sp) > 160 * 1024) return false;
+    return (ds % 4 == 0 && ds <= 256) || ds <= 64;
+}
+
+void projection_release(gnn_mlp *m)
+{
+    if (m->proj) {
+        gnn_fused_release(m->proj);
+        if (m->proj->slab) (void)hipFree(m->proj->slab);
+        delete m->proj;
+    }
+    if (m->proj_wl) (void)hipFree(m->proj_wl);
+    m->proj = nullptr;
+    m->proj_wl = nullptr;
+    m->proj_wl_floats = 0;
+    m->proj_version = ~(uint64_t)0;
+}
+
+// The shadow net's images and the label rows of W1, rebuilt when the weights (m->version) or the concat layout changed since they were built
+int projection_ensure(gnn_mlp *m, int ds, int nlc, int al, const FusedPlan &sp)
+{
+    if (m->proj && m->proj_version == m->version && m->proj_ds == ds && m->proj_nlc == nlc && m->proj_al == al) return GNN_OK;
+    const int n_in = m->dims[0], h1 = m->dims[1], iw = 2 * nlc + al, hp = 32 * sp.nt[0];
+    std::vector<float> W((size_t)n_in * h1), b(h1);
+    HIPCHK(hipMemcpy(W.data(), m->W[0], W.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(b.data(), m->b[0], b.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<float> ws((size_t)2 * ds * h1), wl((size_t)(iw + 2) * hp, 0.0f);      // (label rows, one zero row, the bias)
+    int rs = 0, rl = 0;
+    for (int k = 0; k < n_in; ++k) {
+        const bool label = (k >= ds && k < ds + nlc) || k >= 2 * ds + nlc;      // [nodes] | [agg nodes | agg arcs]: the column order of l->inv
+        if (label) memcpy(wl.data() + (size_t)rl++ * hp, W.data() + (size_t)k * h1, sizeof(float) * h1);
+        else memcpy(ws.data() + (size_t)rs++ * h1, W.data() + (size_t)k * h1, sizeof(float) * h1);
+    }
+    memcpy(wl.data() + (size_t)(iw + 1) * hp, b.data(), sizeof(float) * h1);
+    if (!m->proj) m->proj = new gnn_mlp;
+    gnn_mlp *s = m->proj;
+    if (s->slab_floats != ws.size()) {
+        if (s->slab) (void)hipFree(s->slab);
+        s->slab = nullptr; s->slab_floats = 0;
+        HIPCHK(gnn_dev_malloc((void **)&s->slab, ws.size() * sizeof(float)));
+        s->slab_floats = ws.size();
+    }
+    HIPCHK(hipMemcpy(s->slab, ws.data(), ws.size() * sizeof(float), hipMemcpyHostToDevice));
+    shadow_describe(m, ds, *s);
+    s->device = m->device;
+    s->W = m->W; s->b = m->b;
+    s->W[0] = s->slab;
+    s->has_bn = m->has_bn; s->bn_scale = m->bn_scale; s->bn_shift = m->bn_shift;      // (borrowed, like W[1..] and b: only slab and the images are the shadow's own)
+    if (m->proj_wl_floats != wl.size()) {
+        if (m->proj_wl) (void)hipFree(m->proj_wl);
+        m->proj_wl = nullptr; m->proj_wl_floats = 0;
+        HIPCHK(gnn_dev_malloc((void **)&m->proj_wl, wl.size() * sizeof(float)));
+        m->proj_wl_floats = wl.size();
+    }
+    HIPCHK(hipMemcpy(m->proj_wl, wl.data(), wl.size() * sizeof(float), hipMemcpyHostToDevice));
+    m->proj_version = ~(uint64_t)0;               // (until the images stand)
+    int rc = gnn_fused_pack(s, 0);
+    if (rc) return rc;
+    if (!s->packed || !s->packed_split) return gnn_fail(GNN_ERR_STATE, "label projection: the shadow net has no weight images");
+    s->pack_dirty = false;
+    m->proj_version = m->version; m->proj_ds = ds; m->proj_nlc = nlc; m->proj_al = al;
+    return GNN_OK;
+}
+
+}   // namespace
+
+// What the projection decision answers from shapes alone (include/gnn_hip.h): host code, no device.  The loop's part - impl 2, no
+// feature-sliced exchange, a single GPU not profiling for the persistent small-graph loop - is taken at its defaults.
+extern "C" int gnn_label_projection_form(int n_layers, const int *dims, const int *acts, int state_dim, int n_label_cols_in_concat, int arc_label_dim,
+                                         int64_t n_rows, int mode, int *out)
+{
+    ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && state_dim >= 1 && n_label_cols_in_concat >= 0 && arc_label_dim >= 0 && n_rows >= 0 &&
+           mode >= 0 && mode <= 2 && out, "bad arguments");
+    gnn_mlp m;
+    m.n_layers = n_layers;
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.acts.assign(acts, acts + n_layers);
+    for (int l = 0; l <= n_layers; ++l) ARGCHK(m.dims[l] >= 1, "bad layer width");
+    for (int l = 0; l < n_layers; ++l) ARGCHK(m.acts[l] >= GNN_ACT_LINEAR && m.acts[l] <= GNN_ACT_SOFTMAX, "bad activation code");
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (mode == 0 || n_rows < 1) return GNN_OK;
+    FusedPlan p, sp;
+    const int ds = state_dim;
+    const bool base_ok = make_plan(&m, n_label_cols_in_concat, p) && lds_bytes(p) <= 160 * 1024 && ((ds % 4 == 0 && ds <= 256) || ds <= 64);
+    if (base_ok && small_form(&m, p, n_rows).tile != 0) return GNN_OK;      // the persistent small-graph loop: exact arithmetic, stays as it is
+    if (mode == 1 && base_ok) return GNN_OK;                                // covered without it
+    if (!projection_plan(&m, ds, n_label_cols_in_concat, arc_label_dim, sp)) return GNN_OK;
+    out[0] = 1;
+    out[1] = (ds == 64 && sp.NTL == 2 ? GNN_BODY_FULL_TILE : GNN_BODY_GENERIC) + 1;      // as gnn_loop_body_kernel
+    out[2] = 2 * n_label_cols_in_concat + arc_label_dim;
+    out[3] = sp.nt[0];
+    return GNN_OK;
+}
+
 void gnn_fused_release(gnn_mlp *m)
 {
+    projection_release(m);
     if (m->packed) (void)hipFree(m->packed);
     if (m->packed_split) (void)hipFree(m->packed_split);
     m->packed = nullptr;
@@ -367,7 +487,9 @@ static bool gnn_fused_supported(gnn_loop *l, FusedPlan &p)
 // tile unguarded
 static size_t inv_floats(const gnn_loop *l) { return std::max<size_t>(1, (size_t)((l->g->n_rows + 31) / 32 * 32) * (2 * l->NLc + l->g->AL)); }
 
-// the loop-invariant label block of a fused run (allocated by the form decision)
+static int fused_build_inv(gnn_loop *l);
+
+// the loop-invariant label block of a fused run (allocated by the form decision), and the label projection of a seeded one
 int gnn_fused_prepare(gnn_loop *l)
 {
     const gnn_graph *g = l->g;
@@ -379,7 +501,21 @@ int gnn_fused_prepare(gnn_loop *l)
     if (IW == 0) return GNN_OK;
     // [nodes | Adjacency^T . nodes | ArcNode^T . arc labels]  (GNN.py:263, :259): loop-invariant, and unchanged from run to run
     // unless gnn_graph_update_labels rewrote the labels in between (LGNN stacks)
-    if (l->inv_version == g->label_version) return GNN_OK;
+    int rc = GNN_OK;
+    if (l->inv_version != g->label_version) rc = fused_build_inv(l);
+    // label projection: P from the block, cached with it - and rebuilt when net_state's weights changed (gnn_mlp_set_weights, optimizer step)
+    if (!rc && l->form.seeded && (l->proj_labels != g->label_version || l->proj_weights != l->st->version)) {
+        const gnn_mlp *m = l->st;
+        rc = gnn_label_project_launch(l->stream, g->n_rows, IW, l->proj_nt, l->inv, m->proj_wl, m->proj_wl + (size_t)(IW + 1) * 32 * l->proj_nt, l->proj);
+        if (!rc) { l->proj_labels = g->label_version; l->proj_weights = m->version; }
+    }
+    return rc;
+}
+
+static int fused_build_inv(gnn_loop *l)
+{
+    const gnn_graph *g = l->g;
+    const int IW = 2 * l->NLc + g->AL;
     l->inv_version = g->label_version;
     int rc = gnn_launch_spmm(l->stream, g->n_rows, g->sh->indptr, nullptr, g->sh->arc_w, gnn_graph_arc_labels(g), g->AL, g->AL,
                              l->inv + 2 * l->NLc, IW, nullptr, 1);
@@ -395,17 +531,20 @@ int gnn_fused_prepare(gnn_loop *l)
 }
 
 // the kernel arguments that depend neither on the body nor on the launch geometry; split: arithmetic mode / tile layout
-static void fill_args(const gnn_loop *l, const FusedPlan &p, bool split, GnnFusedArgs &a)
+// seeded (label projection): the arguments of the shadow net over [state | aggregated state] - its images, no label columns - and the seed
+static void fill_args(const gnn_loop *l, const FusedPlan &p, bool split, GnnFusedArgs &a, bool seeded = false)
 {
     const gnn_graph *g = l->g;
-    const gnn_mlp *m = l->st;
+    const gnn_mlp *m = seeded ? l->st->proj : l->st;
+    const int nlc = seeded ? 0 : l->NLc, al = seeded ? 0 : g->AL, in_s = seeded ? 2 * l->Ds : l->in_s;
     a = GnnFusedArgs{};
     a.n_rows = g->n_rows; a.row_begin = l->own_off;     // replica row of the first owned row
     a.indptr = g->sh->indptr; a.adj_src = g->sh->adj_src; a.adj_w = g->sh->adj_w;
     a.inv = l->inv;
     a.state_bytes = (int64_t)l->N_pad * l->Ds * (int64_t)sizeof(float);
     const int pad = split ? p.pad : 0;
-    a.Ds = l->Ds; a.NLc = l->NLc; a.AL = g->AL; a.IW = 2 * l->NLc + g->AL; a.in_s = l->in_s + pad; a.c_aggs = l->Ds + l->NLc + pad;
+    a.Ds = l->Ds; a.NLc = nlc; a.AL = al; a.IW = 2 * nlc + al; a.in_s = in_s + pad; a.c_aggs = l->Ds + nlc + pad;
+    if (seeded) { a.seed = l->proj; a.seed_nt = p.nt[0]; }
     a.KP = split ? p.KPs : p.KP; a.kk0 = p.kk0;
     a.vec = (l->Ds % 4 == 0) ? 4 : 1;
     int lpr = 1, lg = 0;
@@ -455,7 +594,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
     const gnn_graph *g = l->g;
     const FusedPlan &p = f.plan;
     GnnFusedArgs &a = f.args;
-    fill_args(l, p, f.split, a);
+    fill_args(l, p, f.split, a, f.seeded);
     const size_t n_tiles = (size_t)((g->n_rows + 31) / 32);
 #ifdef GNN_DIAG   // diagnostic build only (make DIAG=1): timing experiments; never in the shipped library
     static const int variant_env = getenv("GNN_FUSED_VARIANT") ? atoi(getenv("GNN_FUSED_VARIANT")) : GNN_FUSED_VARIANT_DEFAULT;
@@ -509,6 +648,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
     f.launch.given = f.launch.full && a.agg_in != nullptr;
     f.launch.program = f.launch.full && f.program && g->sh->gp_tiles > 0;
     f.launch.pieces = f.pieces;
+    f.launch.seed = f.seeded;
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;
 }
 
@@ -608,15 +748,34 @@ int gnn_loop_decide_form(gnn_loop *l)
     f = LoopForm{};
     if (l->impl_req < 1) return GNN_OK;
     HIPCHK(hipSetDevice(l->device));
-    if (!gnn_fused_supported(l, f.plan)) return GNN_OK;               // (side effect 1: the weight images)
-    if (l->device < 0 || l->device >= 64) return gnn_fail(GNN_ERR_ARG, "device %d out of range", l->device);
+    const bool base_ok = gnn_fused_supported(l, f.plan);              // (side effect 1: the weight images)
     const gnn_graph *g = l->g;
+    // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
+    // 32-feature tile per layer) or, up to 4,096 rows, with hidden layers up to 64 wide (small_form), layer-0 weights kept in registers,
+    // every tile resident at once (one wave each) with a wide margin
+    const SmallForm sf = base_ok ? small_form(l->st, f.plan, g->n_rows) : SmallForm{};
+    const bool persistent = base_ok && l->world == 1 && !l->small_disabled && !l->profiling && sf.tile != 0;
+    // Label projection (gnn_loop_set_label_projection): impl 2 with one launch per body only - mode 1 where the net as it stands is not
+    // covered and the net over [state | aggregated state] is, mode 2 wherever that one is.  Not the feature-sliced exchange (no seeded
+    // instantiation with a given aggregate), not the persistent small-graph loop and not impl 1 (exact arithmetic: they stay as they are).
+    if (l->label_projection && l->impl_req == 2 && !persistent && !l->slice_mode && (l->label_projection == 2 || !base_ok) && g->n_rows > 0 &&
+        (int64_t)l->N_pad * l->Ds * (int64_t)sizeof(float) < ((int64_t)1 << 31)) {
+        FusedPlan sp;
+        if (projection_plan(l->st, l->Ds, l->NLc, g->AL, sp)) {
+            const int rcp = projection_ensure(l->st, l->Ds, l->NLc, g->AL, sp);      // (side effect 1b: the shadow net's images, the label rows of W1)
+            if (rcp) return rcp;
+            f.plan = sp;
+            f.seeded = true;
+        }
+    }
+    if (!base_ok && !f.seeded) return GNN_OK;
+    if (l->device < 0 || l->device >= 64) return gnn_fail(GNN_ERR_ARG, "device %d out of range", l->device);
     const FusedPlan &p = f.plan;
     const int n_cu = device_cus(l->device);
     const int64_t n_tiles = (g->n_rows + 31) / 32;
     f.split = l->impl_req == 2;
     f.pieces = l->pieces == 2 ? 2 : 3;
-    const bool pair = f.split && !l->slice_mode && pair_covers(p, l->Ds) && pair_lds_bytes(p) <= 160 * 1024 &&
+    const bool pair = !f.seeded && f.split && !l->slice_mode && pair_covers(p, l->Ds) && pair_lds_bytes(p) <= 160 * 1024 &&
                       (l->tile_form ? l->tile_form == 2 : n_tiles <= (int64_t)4 * n_cu);
     f.kernel = pair ? GNN_BODY_PAIR : (l->Ds == 64 && p.NTL == 2 ? GNN_BODY_FULL_TILE : GNN_BODY_GENERIC);
     if (f.kernel == GNN_BODY_FULL_TILE && !l->slice_mode && (l->gather_form ? l->gather_form : GNN_GATHER_FORM_DEFAULT) == 2 &&
@@ -632,14 +791,19 @@ int gnn_loop_decide_form(gnn_loop *l)
         const int want = l->tile_schedule ? l->tile_schedule : (n_tiles >= 4 * waves ? GNN_TILE_SCHEDULE_DEFAULT : 1);
         f.schedule = want == 2 && gnn_tile_schedule_ensure(g, 1, waves) ? 2 : 1;
     }
-    // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
-    // 32-feature tile per layer) or, up to 4,096 rows, with hidden layers up to 64 wide (small_form), layer-0 weights kept in registers,
-    // every tile resident at once (one wave each) with a wide margin
-    const SmallForm sf = small_form(l->st, p, g->n_rows);
-    const bool persistent = l->world == 1 && !l->small_disabled && !l->profiling && sf.tile != 0;
     f.path = persistent ? GNN_PATH_PERSISTENT : GNN_PATH_BODIES;
     // (side effect 3: the label block - the arguments point to it; gnn_fused_prepare zeroes and fills it when the loop runs)
     if (!l->inv) HIPCHK(gnn_dev_malloc((void **)&l->inv, inv_floats(l) * sizeof(float)));
+    if (f.seeded) {                                                   // (side effect 4: the projection's block, whole row and feature tiles)
+        const size_t need = (size_t)n_tiles * p.nt[0] * 1024;
+        if (l->proj_floats != need || l->proj_nt != p.nt[0]) {
+            if (l->proj) (void)hipFree(l->proj);
+            l->proj = nullptr; l->proj_floats = 0;
+            HIPCHK(gnn_dev_malloc((void **)&l->proj, need * sizeof(float)));
+            l->proj_floats = need; l->proj_nt = p.nt[0];
+            l->proj_labels = 0;
+        }
+    }
     if (persistent) return decide_persistent(l, f, sf);
     decide_bodies(l, f, n_cu);
     return GNN_OK;
@@ -649,6 +813,10 @@ int gnn_loop_decide_form(gnn_loop *l)
 static bool launch_body(const LoopForm &f, const GnnFusedArgs &a, hipStream_t st)
 {
     const FusedPlan &p = f.plan;
+    if (f.seeded)                                                     // label projection: split arithmetic, never the wave pair; the last activation from a.act_last
+        return p.layers == 1 ? gnn_fused_launch_ps1(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st)
+             : p.layers == 2 ? gnn_fused_launch_ps2(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st)
+                             : gnn_fused_launch_ps3(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);
     if (p.act_last != p.act) {                                        // the last layer's own activation: a.act_last (never the wave pair)
         if (f.kernel == GNN_BODY_PAIR || p.layers < 2) return false;
         if (f.split) return p.layers == 2 ? gnn_fused_launch_ms2(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st) : gnn_fused_launch_ms3(p.act, p.NT, p.NTL, f.launch, a, f.grid, f.lds, st);

@@ -601,7 +601,9 @@ __device__ __forceinline__ void mfma_split(const v4i (&w)[T][3], v4i b0, v4i b1,
 // layer 0: input = LDS tile.  xr = X + (lane & 31) * KP + 8 * (lane >> 5); wl = split image of the layer + 4 * lane.
 // Two register sets: the weights / tile values of chunk c + 1 are requested before the MFMAs of chunk c.  The image has
 // two zero chunks of slack and the LDS allocation 128 B, so the look-ahead never leaves them; it is never consumed.
-template <int NO, bool AL16, int PC = 3>
+// SEED (label projection): acc arrives holding the tile's seed - the label terms and the bias of the layer, already at the accumulator's
+// scale (seed_tiles) - and the first MFMA of every output tile takes it as C; bias_lds is not read.
+template <int NO, bool AL16, int PC = 3, bool SEED = false>
 __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rsrc_t wrs, int voff, int soff, int n_chunks, f32x16 (&acc)[NO],
                                              const float *bias_lds, int half, float &mx)
 {
@@ -628,7 +630,7 @@ __device__ __forceinline__ void layer0_split(const float *xr, __amdgpu_buffer_rs
         float mn_ = 0.0f;                                                                           \
         _Pragma("unroll") for (int term = 0; term < TM::N; ++term)                                  \
             _Pragma("unroll") for (int t = 0; t < NO; ++t) {                                        \
-                acc[t] = mfma_piece<PC>(W[t][TM::PA[term]], P[TM::PB[term]], (Z && term == 0) ? bias_tile(bias_lds, t, half) : acc[t]);   \
+                acc[t] = mfma_piece<PC>(W[t][TM::PA[term]], P[TM::PB[term]], (!SEED && Z && term == 0) ? bias_tile(bias_lds, t, half) : acc[t]);   \
                 const int m = term * NO + t;                                                        \
                 constexpr int SL = TM::N * NO - NO;                                                 \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                     \
@@ -1556,8 +1558,40 @@ __device__ __forceinline__ void fused_opaque_pointers(GnnFusedArgs &a)
     asm volatile("" : "+s"(a.bn_scale), "+s"(a.bn_shift), "+s"(a.state_cur), "+s"(a.state_nxt), "+s"(a.inv), "+s"(a.adj_src), "+s"(a.adj_w));
 }
 
+// Label projection (gnn_loop_set_label_projection): the seed of the tile's layer-0 accumulators, P[node, feature] of GnnFusedArgs::seed - four
+// 1 KiB wave loads per feature tile straight into the accumulator registers, which are dead until layer 0 starts - times sc, the scale of
+// the accumulator: bsc[0] of the piece format, and log2(e) where the layer's output feeds the folded SELU (as gnn_fused_pack folds its weights and
+// fused_stage_vectors its bias).  Called behind the tile's gather and in front of layer 0's first weight request: vector-memory results
+// return in issue order, so in front of the gather these loads would sit in every wait of it.
+// Through a buffer descriptor of the tile's block (scalar registers) with the weight loads' vector offset 16 * lane: no vector register
+// beyond the accumulators.  SCALE false (format 3 in front of anything but the folded SELU: sc == 1): no multiplication.
+template <int NO, bool SCALE>
+__device__ __forceinline__ void seed_tiles(const GnnFusedArgs &a, int64_t i0, int lane, float sc, f32x16 (&acc)[NO])
+{
+    const float *sp = a.seed;
+    asm volatile("" : "+s"(sp));                      // (per tile, as fused_opaque_pointers)
+    const int tile_bytes = a.seed_nt * 4096;
+    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(sp + (size_t)(i0 >> 5) * (size_t)(a.seed_nt * 1024)), 0,
+                                                                         tile_bytes, 0x00020000);
+    const int sv = lane * 16;
+#pragma unroll
+    for (int jt = 0; jt < NO; ++jt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4f s = __builtin_bit_cast(v4f, bload4i(srs, sv, (jt * 4 + q) * 1024));
+            acc[jt][4 * q] = s.x; acc[jt][4 * q + 1] = s.y; acc[jt][4 * q + 2] = s.z; acc[jt][4 * q + 3] = s.w;
+        }
+    if constexpr (SCALE) {
+#pragma unroll
+        for (int jt = 0; jt < NO; ++jt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[jt][r] *= sc;
+    }
+}
+
 // ---- B: net_state.  H^T[feature][node] = W^T . X^T on MFMA f32 32x32x2 (exact) or on the piece products (SPLIT, format PC) ----
-// Declares half, out (the last layer's raw accumulators) and mx in the kernel's tile loop; a, X, KP, lane, ep, hb and stamp are the kernel's.
+// Declares half, out (the last layer's raw accumulators) and mx in the kernel's tile loop; a, X, KP, lane, i0, ep, hb and stamp are the kernel's.
+// SEED (the kernel's template parameter; split arithmetic only): layer 0 starts from the tile's label projection (seed_tiles), not from its bias.
 // AL16: layer 0 of a net with hidden layers reads the tile in 16-byte pieces (the full-tile kernel's tile layout).
 // WAIT: 12 wait states behind layer 0 of the split arithmetic.  Its chunk loop ends in a branch, what follows reads its accumulators, and
 // hipcc (ROCm 7.2) pads nothing across a basic-block edge (persistent small-graph loop): k_fused_generic, where a one-tile layer
@@ -1574,10 +1608,12 @@ __device__ __forceinline__ void fused_opaque_pointers(GnnFusedArgs &a)
         const int wv = lane * 16;                                                                                                                               \
         const float *xr = X + (lane & 31) * KP + 8 * half;                                                                                                      \
         if constexpr (LAYERS == 1) {                                                                                                                            \
-            layer0_split<NTL, false, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, out, ep, half, mx);                                                               \
+            if constexpr (SEED) seed_tiles<NTL, PC == 2>(a, i0, lane, a.bsc[0], out);                                                                           \
+            layer0_split<NTL, false, PC, SEED>(xr, wrs, wv, a.ws_off[0], a.chunks0, out, ep, half, mx);                                                         \
         } else {                                                                                                                                                \
             f32x16 h1[NT];                                                                                                                                      \
-            layer0_split<NT, AL16, PC>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);                                                                  \
+            if constexpr (SEED) seed_tiles<NT, PC == 2 || ACT == GNN_ACT_SELU>(a, i0, lane, a.bsc[0] * (ACT == GNN_ACT_SELU ? 1.44269504088896341f : 1.0f), h1); \
+            layer0_split<NT, AL16, PC, SEED>(xr, wrs, wv, a.ws_off[0], a.chunks0, h1, hb, half, mx);                                                            \
             if constexpr (WAIT) { asm volatile("s_nop 7\n\ts_nop 3" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }                                         \
             GNN_STAMP(3);                                                                                                                                       \
             GNN_STAMP(4);                                                                                                                                       \
@@ -1652,9 +1688,11 @@ __device__ __forceinline__ int fused_next_tile(const GnnFusedArgs &a0, int next2
 // check_store_generic tests and stores it.
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int PC, int ACTL>
+// SEED: the seeded form of the label projection (GNN_FUSED_DENSE_LAYERS; the arguments describe the net over [state | aggregated state]).
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int PC, int ACTL, bool SEED = false>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const GnnFusedArgs a0)
 {
+    static_assert(!SEED || SPLIT, "the label projection is a form of the split arithmetic");
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (!gnn_gate_open(a.gate, a.world)) return;
@@ -1678,6 +1716,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const Gn
     if (i0 >= a.n_rows) break;                        // wave-uniform; no workgroup barrier anywhere in the tile loop
     const int nvalid = (int)((a0.n_rows - i0) < 32 ? (a0.n_rows - i0) : 32);
     GnnFusedArgs a = a0;
+    if constexpr (SEED) { a.IW = 0; a.NLc = 0; a.AL = 0; }      // (the shadow net has no label columns: as constants, so that the tile loaders' label paths fold away)
     fused_opaque_pointers(a);
 #ifdef GNN_DIAG
     unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)tile << 3) : nullptr;
@@ -1744,9 +1783,11 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const Gn
 // last tile of the graph too (an ordinary slot of the tile schedule, prog_header_request): no CSR walk is compiled in.  A template parameter for the same reason as
 // GIVEN.  With GNN_FIRST_BATCH_AHEAD a tile's first batch is requested during the previous tile (load_tile_prog64_ahead).
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
-template <int LAYERS, int NT, int ACT, bool SPLIT, bool GIVEN, int PC, bool PROG, int ACTL>
+// SEED: the seeded form of the label projection (GNN_FUSED_DENSE_LAYERS; the arguments describe the net over [state | aggregated state]).
+template <int LAYERS, int NT, int ACT, bool SPLIT, bool GIVEN, int PC, bool PROG, int ACTL, bool SEED = false>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFusedArgs a0)
 {
+    static_assert(!SEED || (SPLIT && !GIVEN), "the label projection is a form of the split arithmetic, and of the gathering kernels");
     constexpr int NTL = 2;
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
     // Persistent workgroup of 8 waves (one per CU): every wave pulls 32-node tiles from a device-wide counter until none
@@ -1797,6 +1838,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     if (PROG ? tile >= a.gp_slots : i0 >= a.n_rows) break;        // wave-uniform; no workgroup barrier anywhere in the tile loop
     const int nvalid = (int)((a0.n_rows - i0) < 32 ? (a0.n_rows - i0) : 32);
     GnnFusedArgs a = a0;
+    if constexpr (SEED) { a.IW = 0; a.NLc = 0; a.AL = 0; }      // (the shadow net has no label columns: as constants, so that the tile loaders' label paths fold away)
     fused_opaque_pointers(a);
 #ifdef GNN_DIAG
     unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)(PROG ? tid : tile) << 3) : nullptr;      // (by tile id, whatever the schedule)
@@ -1908,56 +1950,63 @@ inline void launch_kernel(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes
 }
 
 // k_fused_generic in the piece format of the launch (the exact path has one)
-template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL>
+template <int LAYERS, int NT, int NTL, int ACT, bool SPLIT, int ACTL, bool SEED = false>
 inline void launch_generic_pc(const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
-    if (SPLIT && how.pieces == 2) launch_kernel<k_fused_generic<LAYERS, NT, NTL, ACT, SPLIT, 2, ACTL>>(a, grid, lds_bytes, st);
-    else launch_kernel<k_fused_generic<LAYERS, NT, NTL, ACT, SPLIT, 3, ACTL>>(a, grid, lds_bytes, st);
+    if (SPLIT && how.pieces == 2) launch_kernel<k_fused_generic<LAYERS, NT, NTL, ACT, SPLIT, 2, ACTL, SEED>>(a, grid, lds_bytes, st);
+    else launch_kernel<k_fused_generic<LAYERS, NT, NTL, ACT, SPLIT, 3, ACTL, SEED>>(a, grid, lds_bytes, st);
 }
 // (NT, NTL) pairs that are instantiated; gnn_fused.hip rounds every net up to one of them
-template <int LAYERS, int ACT, bool SPLIT, int ACTL>
+template <int LAYERS, int ACT, bool SPLIT, int ACTL, bool SEED = false>
 inline bool launch_generic(int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     // unreachable: make_plan sets NTL = round_tiles(Ds), so a state width of 64 has NTL == 2, and gnn_loop_decide_form gives every such
     // loop the full-tile or the pair kernel.  k_fused_generic has none of the width-64 paths.
     if (a.Ds == 64) return false;
     if constexpr (LAYERS == 1) {
-        if (ntl == 1) launch_generic_pc<1, 1, 1, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
-        else if (ntl == 2) launch_generic_pc<1, 2, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
-        else if (ntl == 4) launch_generic_pc<1, 4, 4, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        if (ntl == 1) launch_generic_pc<1, 1, 1, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
+        else if (ntl == 2) launch_generic_pc<1, 2, 2, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
+        else if (ntl == 4) launch_generic_pc<1, 4, 4, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
         else return false;
     } else {
-        if (nt == 1 && ntl == 1) launch_generic_pc<LAYERS, 1, 1, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
-        else if (nt == 2 && ntl == 2) launch_generic_pc<LAYERS, 2, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
-        else if (nt == 4 && ntl == 2) launch_generic_pc<LAYERS, 4, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
-        else if (nt == 4 && ntl == 4) launch_generic_pc<LAYERS, 4, 4, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        if (nt == 1 && ntl == 1) launch_generic_pc<LAYERS, 1, 1, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
+        else if (nt == 2 && ntl == 2) launch_generic_pc<LAYERS, 2, 2, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
+        else if (nt == 4 && ntl == 2) launch_generic_pc<LAYERS, 4, 2, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
+        else if (nt == 4 && ntl == 4) launch_generic_pc<LAYERS, 4, 4, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
         else return false;
     }
     return true;
 }
 
 // k_fused_full in the launch's gather form - a given aggregate, the graph's program, or the CSR walk - and piece format
-template <int LAYERS, int NT, int ACT, bool SPLIT, int ACTL>
+// (SEED: no instantiation with a given aggregate - launch_full refuses it)
+template <int LAYERS, int NT, int ACT, bool SPLIT, int ACTL, bool SEED = false>
 inline void launch_full_form(const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     auto gather_form = [&](auto P) {
         constexpr int PC = P.value;
-        if (how.given) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, true, PC, false, ACTL>>(a, grid, lds_bytes, st);
-        else if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, true, ACTL>>(a, grid, lds_bytes, st);
-        else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, false, ACTL>>(a, grid, lds_bytes, st);
+        if constexpr (SEED) {
+            if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, true, ACTL, true>>(a, grid, lds_bytes, st);
+            else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, false, ACTL, true>>(a, grid, lds_bytes, st);
+        } else {
+            if (how.given) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, true, PC, false, ACTL>>(a, grid, lds_bytes, st);
+            else if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, true, ACTL>>(a, grid, lds_bytes, st);
+            else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, false, ACTL>>(a, grid, lds_bytes, st);
+        }
     };
     if (SPLIT && how.pieces == 2) gather_form(std::integral_constant<int, 2>{});
     else gather_form(std::integral_constant<int, 3>{});      // (the exact path has one)
 }
 // the last layer has 2 tiles; hidden layers of 2 or 4
-template <int LAYERS, int ACT, bool SPLIT, int ACTL>
+template <int LAYERS, int ACT, bool SPLIT, int ACTL, bool SEED = false>
 inline bool launch_full(int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
 {
     if (ntl != 2) return false;
-    if constexpr (LAYERS == 1) launch_full_form<1, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+    if (SEED && how.given) return false;
+    if constexpr (LAYERS == 1) launch_full_form<1, 2, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
     else {
-        if (nt == 2) launch_full_form<LAYERS, 2, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
-        else if (nt == 4) launch_full_form<LAYERS, 4, ACT, SPLIT, ACTL>(how, a, grid, lds_bytes, st);
+        if (nt == 2) launch_full_form<LAYERS, 2, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
+        else if (nt == 4) launch_full_form<LAYERS, 4, ACT, SPLIT, ACTL, SEED>(how, a, grid, lds_bytes, st);
         else return false;
     }
     return true;
@@ -1988,6 +2037,20 @@ inline bool launch_fused(int act, int nt, int ntl, const GnnFusedLaunch &how, co
         constexpr int ACT = A.value, ACTL = MIXED ? GNN_ACTL_FROM_ARGS : ACT;
         return how.full ? launch_full<LAYERS, ACT, SPLIT, ACTL>(nt, ntl, how, a, grid, lds_bytes, st)
                         : launch_generic<LAYERS, ACT, SPLIT, ACTL>(nt, ntl, how, a, grid, lds_bytes, st);
+    });
+}
+
+// The entry of a seeded translation unit (label projection): split arithmetic, the last layer's activation always from a.act_last - one
+// family per hidden activation serves nets with and without a last activation of their own
+template <int LAYERS>
+inline bool launch_fused_seeded(int act, int nt, int ntl, const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
+{
+    if (!a.seed) return false;
+    if constexpr (LAYERS == 1) act = GNN_ACT_LINEAR;      // (no hidden layer: ACT is read nowhere, one family serves all)
+    return dispatch_act(act, [&](auto A) {
+        constexpr int ACT = LAYERS == 1 ? GNN_ACT_LINEAR : A.value;
+        return how.full ? launch_full<LAYERS, ACT, true, GNN_ACTL_FROM_ARGS, true>(nt, ntl, how, a, grid, lds_bytes, st)
+                        : launch_generic<LAYERS, ACT, true, GNN_ACTL_FROM_ARGS, true>(nt, ntl, how, a, grid, lds_bytes, st);
     });
 }
 

@@ -367,6 +367,38 @@ extern "C" int gnn_loop_drop_cached_aggregates(gnn_loop *l)
 {
     ARGCHK(l, "loop is NULL");
     l->inv_version = 0;
+    l->proj_labels = 0;         // the label projection is built from the block
+    return GNN_OK;
+}
+
+// Label projection (include/gnn_hip.h): layer 0 of net_state split by rows of its kernel - the label terms inv . W1_label + b1 once per
+// Loop (gnn_label_project.hip), every body's layer 0 over [state | aggregated state] only, started from them (seeded kernels, gnn_fused_ps*.hip)
+extern "C" int gnn_loop_set_label_projection(gnn_loop *l, int mode, int *used)
+{
+    ARGCHK(l && mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (where the fused path needs it) or 2 (wherever applicable)");
+    l->label_projection = mode;
+    const int rc = gnn_loop_decide_form(l);
+    if (used) *used = l->form.path == GNN_PATH_BODIES && l->form.seeded ? 1 : 0;
+    return rc;
+}
+
+// test hook: the projection the last run used, P [n_rows, H1] row-major (H1: width of net_state's first layer)
+extern "C" int gnn_loop_get_label_projection(gnn_loop *l, float *out)
+{
+    ARGCHK(l && out, "bad arguments");
+    if (!l->ran || !l->form.seeded || !l->proj || l->proj_labels != l->g->label_version || l->proj_weights != l->st->version)
+        return gnn_fail(GNN_ERR_STATE, "the last run of this loop did not use a label projection");
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipStreamSynchronize(l->stream));
+    std::vector<float> host(l->proj_floats);
+    HIPCHK(hipMemcpy(host.data(), l->proj, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const int h1 = l->st->dims[1], nt = l->proj_nt;
+    for (int64_t i = 0; i < l->g->n_rows; ++i)
+        for (int j = 0; j < h1; ++j) {
+            // tile order [row tile][feature tile][q][lane = 32 half + node][4]: feature 32 jt + 8 q + 4 half + e (GnnFusedArgs::seed)
+            const int jt = j >> 5, q = (j >> 3) & 3, half = (j >> 2) & 1, e = j & 3;
+            out[(size_t)i * h1 + j] = host[((((size_t)(i >> 5) * nt + jt) * 4 + q) * 64 + 32 * half + (i & 31)) * 4 + e];
+        }
     return GNN_OK;
 }
 
@@ -1111,7 +1143,7 @@ extern "C" int gnn_loop_destroy(gnn_loop *l)
     gnn_train_ctx_free(l);
     gnn_train_arena_free(l);
     for (int b = 0; b < 2; ++b) { (void)hipFree(l->state[b]); (void)hipFree(l->tmp[b]); (void)hipFree(l->otmp[b]); }
-    (void)hipFree(l->inp); (void)hipFree(l->inv); (void)hipFree(l->state_init); (void)hipFree(l->feats); (void)hipFree(l->out); (void)hipFree(l->flags); (void)hipFree(l->kfinal_dev);      // (tile_ctr lives in the flag block)
+    (void)hipFree(l->inp); (void)hipFree(l->inv); (void)hipFree(l->proj); (void)hipFree(l->state_init); (void)hipFree(l->feats); (void)hipFree(l->out); (void)hipFree(l->flags); (void)hipFree(l->kfinal_dev);      // (tile_ctr lives in the flag block)
     if (l->kfinal_host) (void)hipHostFree(l->kfinal_host);
     (void)hipFree(l->small_xs);
     for (hipEvent_t e : l->ev) (void)hipEventDestroy(e);

@@ -423,6 +423,33 @@ int gnn_loop_set_gather_form(gnn_loop *l, int form, int *used);
  * A node's arithmetic does not depend on when its tile runs: states, outputs and k are identical bit for bit.  *used (may be NULL) = the
  * order the next run will take; 0 where its launches read no program. */
 int gnn_loop_set_tile_schedule(gnn_loop *l, int kind, int *used);
+/* Label projection: a fused Loop for wide node / arc labels.  The fused kernels hold the whole concat [state | nodes | agg state | agg nodes
+ * | agg arcs] of 32 nodes in LDS, which caps it at about 144 columns; the label columns do not change during a Loop.  With the projection,
+ * layer 0 of net_state is split by rows of its kernel W1: the label terms P = [nodes | agg nodes | agg arcs] . W1_label + b1 are computed
+ * once per Loop (fp32 operands and accumulation on v_mfma_f32_32x32x2_f32, k ascending, run-to-run identical bits), and every body runs
+ * layer 0 over [state | agg state] only - K = 2 x state width - with its accumulators started from P[node, :] instead of from the bias.
+ *   mode 0  off (default): the Loop runs exactly as without this call, bit for bit;
+ *   mode 1  where needed: taken when the fused path does not cover the net as it stands and covers the net over [state | agg state];
+ *   mode 2  wherever applicable (A/B runs, tests on narrow labels).
+ * A form of the default arithmetic (impl 2, both piece formats, CSR walk and gather program) with one launch per body only: impl 1 and
+ * impl 0, the persistent small-graph loop and the feature-sliced exchange run as without it, and so does the bit-exact repeat of a Loop
+ * whose gate was not certified (per-op kernels where the net is too wide for the exact fused kernel).  The label part of layer 0 is an
+ * fp32 sum in another order than the oracle's, about 1e-7 relative: states and outputs stay within the default path's 1e-5, k is the exact
+ * chain's under the certified gate.  P is cached across runs like the label aggregates, rebuilt when the graph's labels or net_state's
+ * weights change, and dropped by gnn_loop_drop_cached_aggregates.  Training-mode runs never take it.
+ * *used (may be NULL) = 1 when the next run takes the seeded kernels, else 0. */
+int gnn_loop_set_label_projection(gnn_loop *l, int mode, int *used);
+/* Test entry points of the label projection, not part of the supported interface.
+ * The projection the last run of l used, as P [n_rows, H1] row-major (H1 = width of net_state's first layer); GNN_ERR_STATE when that run
+ * used none. */
+int gnn_loop_get_label_projection(gnn_loop *l, float *out);
+/* What gnn_loop_set_label_projection(mode) answers from shapes alone - host code, no device: dims [n_layers + 1] (dims[0] the whole
+ * concat), acts [n_layers], state width, node-label columns in the concat, arc-label width, owned rows; impl 2, a single GPU, no
+ * feature-sliced exchange, not profiling are the loop's part, taken at their defaults.  out receives 4 ints: out[0] = 1 seeded / 0 not
+ * (then the rest is 0); out[1] = per-body kernel as gnn_loop_body_kernel (1 k_fused_generic, 2 k_fused_full); out[2] = projected label
+ * columns IW; out[3] = 32-feature tiles of P per 32-row tile. */
+int gnn_label_projection_form(int n_layers, const int *dims, const int *acts, int state_dim, int n_label_cols_in_concat, int arc_label_dim,
+                              int64_t n_rows, int mode, int *out);
 /* ---- Test and diagnostic entry points of gather form 2: not part of the supported interface, they may change with the program's layout. ----
  * The gather program of rows [0, n_rows) of a CSR graph (host code; tests/test_gather_program.py).  Per full 32-row tile t: hdr[2 t] = first
  * 64-entry batch, hdr[2 t + 1] = batches; ent[(64 b + 16 g + j) 2 + {0, 1}] = {source word, weight bits} of entry j of lane group g in
@@ -508,7 +535,8 @@ int gnn_small_form(int n_layers, const int *dims, const int *acts, int n_label_c
 int gnn_loop_set_profiling(gnn_loop *l, int enable);
 /* The label aggregates ArcNode^T . arc labels and Adjacency^T . node labels (GNN/GNN.py:259, :263) do not depend on the state:
  * the fused path builds them on the first run and keeps them until the labels change (gnn_graph_update_labels).  This call
- * drops them, so that the next gnn_loop_run pays for them like every Loop() of the reference does (bench.py: cold figure). */
+ * drops them - and the label projection built from them (gnn_loop_set_label_projection) - so that the next gnn_loop_run pays for them
+ * like every Loop() of the reference does (bench.py: cold figure). */
 int gnn_loop_drop_cached_aggregates(gnn_loop *l);
 int gnn_loop_get_timing(const gnn_loop *l, float *total_ms, float *avg_iter_ms, int *n_iter_timed);
 /* With profiling on: mean time on the loop's stream between the end of one body's kernel(s) and the start of the next body's, over the last
