@@ -44,6 +44,17 @@ class GNNnodeBased(BaseClass):
         self.adjoint_max_iteration = None
         self.adjoint_threshold = None
         self.label_projection = 'off'       # set_label_projection
+        self.train_recompute = False        # set_train_recompute
+
+    def set_train_recompute(self, enable: bool) -> None:
+        """Activation recomputation in the unrolled training step (off by default).  Back-propagation through the unrolled loop keeps every
+        body's activations from the forward pass until the backward pass reaches them - memory that grows with max_iteration.  With this
+        on, the forward keeps each body's output state alone and the backward pass rebuilds a body's activations right before it walks the
+        body: one more forward pass per body, the same loss and gradients bit for bit.  Works with every net the unrolled step handles
+        (BatchNormalization, Dropout, all three GNN types, the LGNN joint steps); without effect in gradient mode 'fixed_point'.
+        Kept by copy() (so by LKO) and by save() / load()."""
+        if not isinstance(enable, bool): raise ValueError('param <enable> must be a bool')
+        self.train_recompute = enable
 
     def set_label_projection(self, mode) -> None:
         """The fused Loop for wide node / arc labels.  The fused kernels hold a node's whole net_state input in on-chip memory, which
@@ -90,6 +101,7 @@ class GNNnodeBased(BaseClass):
                              path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
         new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
         new.set_label_projection(self.label_projection)
+        new.set_train_recompute(self.train_recompute)
         return new
 
     def save(self, path: str):
@@ -109,7 +121,8 @@ class GNNnodeBased(BaseClass):
             json.dump({'loss_function': loss_name if hasattr(losses, str(loss_name)) else None, 'loss_arguments': self.loss_args,
                        'optimizer': optimizers.serialize(self.optimizer), 'max_iteration': self.max_iteration, 'threshold': self.state_threshold,
                        'addressed_problem': self.addressed_problem, 'state_vect_dim': self.state_vect_dim,
-                       'gradient_mode': self._gradient_config(), 'label_projection': self.label_projection}, f)
+                       'gradient_mode': self._gradient_config(), 'label_projection': self.label_projection,
+                       'train_recompute': self.train_recompute}, f)
 
     @classmethod
     def load(cls, path: str, path_writer=None, namespace: str = 'GNN', extra_metrics=None, extra_metrics_arguments=None):
@@ -126,6 +139,7 @@ class GNNnodeBased(BaseClass):
         loss = getattr(losses, loss_name) if loss_name else None
         gradient = config.pop('gradient_mode', None) or {'mode': 'unrolled'}      # (a model saved before the mode existed: unrolled)
         projection = config.pop('label_projection', None) or 'off'                # (a model saved before the key existed: off)
+        recompute = bool(config.pop('train_recompute', False))                    # (likewise)
         nets = []
         for name in ('net_state', 'net_output'):
             with open(f'{path}{name}.json') as f:
@@ -137,6 +151,7 @@ class GNNnodeBased(BaseClass):
                     extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
         model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'))
         model.set_label_projection(projection)
+        model.set_train_recompute(recompute)
         return model
 
     def get_dense_layers(self):
@@ -188,6 +203,9 @@ class GNNnodeBased(BaseClass):
         if getattr(loop, '_projection_set', 'off') != self.label_projection:
             loop.set_label_projection(self.label_projection)
             loop._projection_set = self.label_projection
+        if getattr(loop, '_recompute_set', False) != self.train_recompute:
+            loop.set_train_recompute(self.train_recompute)
+            loop._recompute_set = self.train_recompute
         return loop
 
     def _prerun(self, graphs) -> list:

@@ -39,6 +39,15 @@ class LGNN(BaseClass):
         """GNNnodeBased.set_label_projection for every layer (the layers behind the first see labels widened by states / outputs)."""
         for gnn in self.gnns: gnn.set_label_projection(mode)
 
+    def set_train_recompute(self, enable: bool) -> None:
+        """GNNnodeBased.set_train_recompute for every layer: the joint steps of 'parallel' / 'residual' hold the training forward of every
+        layer until the backward passes run, so the layers' activations are alive together."""
+        for gnn in self.gnns: gnn.set_train_recompute(enable)
+
+    @property
+    def train_recompute(self) -> bool:
+        return all(gnn.train_recompute for gnn in self.gnns)
+
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
         """GNNnodeBased.set_gradient_mode for every layer.  'serial' training runs the layers' own steps and works in both modes; the joint
         steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' does not return:

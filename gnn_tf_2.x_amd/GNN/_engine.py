@@ -22,6 +22,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_train_forward', 'gnn_loop_train_backward', 'gnn_loop_arm_optimizer', 'gnn_loop_optimizer_step', 'gnn_loop_update_moving_statistics', 'gnn_loss_grad',
            'gnn_loss_grad_ex', 'gnn_loop_set_loss_params', 'gnn_train_forms', 'gnn_loop_train_forms', 'gnn_loop_train_mask', 'gnn_fused_net_form', 'gnn_small_form',
            'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
+           'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
@@ -833,6 +834,24 @@ class Loop:
         used = C.c_int(0)
         _check(lib().gnn_loop_set_train_persistent(self._h, C.c_int(bool(enable)), C.byref(used)))
         return bool(used.value)
+
+    def set_train_recompute(self, enable, cacheless: bool = True) -> bool:
+        """gnn_loop_set_train_recompute: recomputation of the bodies' activations in the unrolled training step (off by default).  The forward
+        keeps each body's output state, statistics and gate alone; the backward pass rebuilds a body's cache right before it walks the body.
+        Every result equals the default step's bit for bit.  cacheless=False: the first pass runs the ordinary kernels on scratch instead of
+        the cache-less forms (A/B runs).  Returns whether a training forward of this loop would take the mode now (False in the fixed-point
+        gradient modes); NotImplementedError on a sharded loop."""
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_train_recompute(self._h, C.c_int((1 if cacheless else 2) if enable else 0), C.byref(used)))
+        return bool(used.value)
+
+    def train_recompute_info(self) -> dict:
+        """gnn_loop_train_recompute_info: dict(state_only: the last train_forward() / train_step() kept the bodies' states alone; replayed: bodies
+        rebuilt by the last backward pass; cacheless_chain: 1 when the first pass launched the cache-less three-layer chain, 0 when the
+        ordinary kernels ran on scratch)."""
+        out = np.zeros(3, np.int32)
+        _check(lib().gnn_loop_train_recompute_info(self._h, _ip(out)))
+        return dict(state_only=bool(out[0]), replayed=int(out[1]), cacheless_chain=int(out[2]))
 
     def set_gradient_mode(self, mode, max_iteration=None, threshold=None) -> int:
         """gnn_loop_set_gradient_mode: 'unrolled' / 0 (default: back-propagation through the executed bodies) or 'fixed_point' / 1 (the

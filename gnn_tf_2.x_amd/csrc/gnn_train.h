@@ -16,10 +16,10 @@ struct GNN_INTERNAL gnn_train_arena {
     std::vector<Slab> slabs;
     size_t cur = 0, off = 0;
     void reset() { cur = 0; off = 0; peak = 0; }
-    // scratch that is needed again and again (the adjoint iterations of gnn_train_adjoint.hip): everything allocated after mark() is handed out
+    // scratch that is needed again and again (the adjoint iterations of gnn_train_adjoint.hip; the bodies of the recomputing step, gnn_train.hip): everything allocated after mark() is handed out
     // again after rewind() - the work that used it runs earlier on the same stream.  INVARIANT: nothing allocated between mark() and rewind()
     // may be remembered beyond it (a pointer cached on a Net, such as Net::part, would then alias later allocations): net_backward with
-    // wgrad = false allocates per-call scratch only
+    // wgrad = false allocates per-call scratch only; the recomputing step allocates Net::part ahead of its mark
     struct Mark { size_t cur, off; };
     Mark mark() const { return Mark{cur, off}; }
     void rewind(const Mark &m) { cur = m.cur; off = m.off; }
@@ -250,6 +250,7 @@ bool fwd3_covers(const gnn_mlp *m);
 bool bwd3_covers(const gnn_mlp *m);
 int launch_gemm_f32(hipStream_t st, Buf &buf, int64_t n, int K, int n_cols, const float *X, const float *M, const float *bias, int act, int mode,
                     const uint8_t *keep, float rate, const float *a_prev, float *Y);
+// a0 == a1 == NULL: the cache-less instantiation (k_fwd3_split<ACT, false>), which writes the last layer's output alone
 int launch_fwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, int64_t n, const float *x, float *a0, float *a1, float *a2);
 int launch_bwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, float *const *WT, int64_t n, const float *dz2, const float *a1, const float *a0, float *dz1,
                 float *dz0, float *dinp, float *dsg = nullptr, int Ds = 0, int c_aggs = 0);
@@ -318,8 +319,20 @@ int small_train_launch(hipStream_t st, const Net &net, const SmallTrainForm &f, 
 void net_decide_form(Net &net, int64_t n, bool producer_dropout);
 int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
               int64_t rows, bool producer_dropout);
+// How a body of the recomputing step (gnn_loop_set_train_recompute) calls net_forward; the default is the ordinary call.
+//   y_dst: where the call's output goes (the one array of a state-only body that outlives it; NULL: allocated like the others)
+//   cacheless: the first pass may take the forms that do not store what only the backward pass reads (a0 / a1 of the three-layer chain, xhat);
+//              *cacheless_chain is set when the cache-less chain was launched
+//   replay_call >= 0: the call REPEATS BatchNormalization call `replay_call` of this step - it is not counted, c.stats is that call's slot of
+//              stats_all (left as the first pass wrote it), and the statistics it recomputes (same bits) go to scratch
+struct FwdMode {
+    float *y_dst = nullptr;
+    bool cacheless = false;
+    int replay_call = -1;
+    int *cacheless_chain = nullptr;
+};
 int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, const MaskStream &rng, NetCache &c, float **y_out,
-                gnn_comm *comm = nullptr, const InputBuild *build = nullptr);
+                gnn_comm *comm = nullptr, const InputBuild *build = nullptr, const FwdMode &mode = FwdMode());
 // wgrad = false: d x alone (no weight-gradient tiles or kernels, no sum of the chunk partials; net.grads and net.part are not touched)
 int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d, float **dx_out, const StateGradJob *job = nullptr,
                  gnn_comm *comm = nullptr, int64_t n_global = 0, bool wgrad = true);
@@ -383,6 +396,17 @@ struct GNN_INTERNAL gnn_train_ctx {
     float *d_sw = nullptr;
     float *state = nullptr, *out_nodes = nullptr;
     int k = 0;
+    // what a body is rebuilt from (the recomputing step replays body `it` in front of its backward pass; Forward fills them in every mode):
+    // states[i] = the state body i reads (row 0 of a replica; states[0] is read in place), the template of the concat, the injected masks of
+    // net_state (NULL: own generator) with the bytes of one body, the step's seed.  The rates are Net::rate.
+    std::vector<float *> states;
+    float *tmpl = nullptr;
+    uint8_t *d_masks_s = nullptr;
+    size_t mask_iter_bytes = 0;
+    uint64_t seed = 0;
+    bool recompute = false;       // the forward ran state-only: `caches` holds k empty entries until train_backward rebuilds them one at a time
+    int replayed = 0;             // ... bodies rebuilt by the backward pass
+    int cacheless_chain = 0;      // ... the first pass launched the cache-less three-layer chain (else the ordinary kernels on rewound scratch)
     bool fixed_point = false;     // gradient mode 1: `caches` holds ONE recorded body at the converged state `state` (k bodies of the inference Loop led there)
     bool persistent = false;      // the bodies ran in the persistent launch (k_train_small) ...
     int workgroups = 0, barriers = 0;     // ... of that many workgroups, with that many grid barriers per body

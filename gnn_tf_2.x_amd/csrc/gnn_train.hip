@@ -15,6 +15,9 @@
 // reduction over rows leaves per-chunk partials that are added in a fixed order (no float atomics, run-to-run identical), so
 // results are compared with the float64 oracle to a tolerance, not bit for bit.
 //
+// Opt-in (gnn_loop_set_train_recompute): the forward keeps of every body its output state, statistics and gate alone, and train_backward rebuilds
+// a body's cache (body_forward, the function the first pass ran) right before that body's backward pass - same bits, one body's cache alive.
+//
 // This unit is the step itself: the concat and the gather / scatter between the state and net_output, the loss, the label gradients,
 // train_forward / train_backward and their entry points.  gnn_train_net.hip: one Sequential in training mode (net_setup, which also
 // decides once per step which kernels the net's calls take, net_forward, net_backward).  gnn_train_wide.hip: the matrix-core products
@@ -494,6 +497,48 @@ static int graph_by_source(gnn_graph *g)
     return GNN_OK;
 }
 
+// Body `it` of net_state from cx->states[it]: the concat by the input kernel the rows and rates ask for (with the body's gate, where
+// check_gate is set), then net_forward; c: the body's cache, *y: its output state.  The first pass and the replay of the recomputing step
+// (train_backward) are this one function: same kernels, same mask stream MaskStream{seed, 0, it, row0} or slice of the injected masks.
+// check_gate = false (a replayed body): no gate is evaluated - gnn_launch_check is skipped, and the kernels that evaluate a gate in passing
+// (k_train_input, k_mlp_fwd) raise the scratch block `gate`.
+static int body_forward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, int it, int *gate, bool check_gate, NetCache &c, float **y, gnn_comm *comm,
+                        const FwdMode &mode)
+{
+    gnn_graph *g = l->g;
+    Buf &buf = cx->buf;
+    const bool sharded = l->world > 1;
+    const int64_t N = cx->N;
+    const size_t own_off = sharded ? (size_t)l->own_off : 0;
+    const int Ds = l->Ds, in_s = l->in_s, c_aggs = Ds + l->NLc;
+    int rc;
+    float *inp = nullptr;
+    uint8_t *keep0 = nullptr;
+    const float r0 = cx->ns.rate[0];
+    if ((rc = buf.get(&inp, (size_t)N * in_s))) return rc;
+    if (r0 != 0.0f && (rc = buf.get(&keep0, (size_t)N * in_s))) return rc;
+    const uint8_t *mk = cx->d_masks_s ? cx->d_masks_s + cx->mask_iter_bytes * (size_t)it : nullptr;
+    const MaskStream rng{cx->seed, 0, it, sharded ? g->row_begin : 0};
+    const float *state = cx->states[it], *own_cur = state + own_off * Ds, *own_prev = it ? cx->states[it - 1] + own_off * Ds : (const float *)nullptr;
+    // few rows: k_mlp_fwd builds the concat rows itself (one launch for input + all Dense layers) and evaluates the gate
+    const InputBuild build{Ds, c_aggs, cx->tmpl, state, own_cur, own_prev, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, l->thr, gate};
+    if (cx->ns.build_input || N == 0) {
+        // (a rank without rows: nothing to compute, it only takes part in the exchanges below)
+    } else if (r0 == 0.0f && state_rows16(Ds, N)) {
+        // many rows: the concat 16 lanes per row, gate i = condition(state_i, state_{i-1}) by k_check beside it
+        hipLaunchKernelGGL(k_train_input_rows, cdiv(N * 16, 256), 256, 0, st, N, in_s, Ds, c_aggs, cx->tmpl, state, own_cur, g->sh->indptr, g->sh->adj_src,
+                           g->sh->adj_w, inp);
+        HIPCHK(hipGetLastError());
+        if (check_gate && (rc = gnn_launch_check(st, N, Ds, own_cur, own_prev, l->thr, gate))) return rc;
+    } else {
+        // the input kernel of body i also evaluates gate i = condition(state_i, state_{i-1})
+        hipLaunchKernelGGL(k_train_input, cdiv(N * in_s, 256), 256, 0, st, N, in_s, Ds, c_aggs, cx->tmpl, state, own_cur, g->sh->indptr, g->sh->adj_src,
+                           g->sh->adj_w, r0, mk, dropout_key(cx->seed, 0, it, 0), rng.row0 * in_s, keep0, inp, own_prev, l->thr, gate);
+        HIPCHK(hipGetLastError());
+    }
+    return net_forward(st, buf, cx->ns, inp, keep0, mk, rng, c, y, comm, &build, mode);
+}
+
 // One training-mode forward: what its steps (below, in the order train_forward takes them) share
 struct Forward {
     gnn_loop *l;
@@ -507,10 +552,8 @@ struct Forward {
     uint64_t seed;
     size_t flag_words;
     int *flags, *hflags, *flags_all;      // the iteration gates: device, pinned host copy, (sharded) those of all ranks
-    float *tmpl;                  // template of the concat
-    uint8_t *d_masks_s, *d_masks_o;       // injected Dropout masks (else nullptr: own generator)
-    size_t mask_iter_bytes;       // masks of one iteration of net_state
-    std::vector<float *> states;  // states[i]: the state body i reads (row 0 of a replica); states[0] is read in place
+    uint8_t *d_masks_o;           // injected Dropout masks of net_output (else nullptr: own generator)
+    // (the state tables, the template of the concat and net_state's injected masks: gnn_train_ctx - a replayed body reads them again)
 
     // Adjacency by source for the transposed aggregation of the backward pass: the caller's arrays, or (NULL) the graph's own copy
     int by_source(const int32_t *src_indptr, const int32_t *src_dst, const float *src_w)
@@ -554,6 +597,7 @@ struct Forward {
         gnn_graph *g = l->g;
         const int in_s = l->in_s, c_nodes = l->Ds, c_aggn = l->Ds + l->NLc + l->Ds, c_agga = c_aggn + l->NLc;
         int rc;
+        float *tmpl = cx->tmpl;
         if ((rc = gnn_launch_spmm(st, N, g->sh->indptr, nullptr, g->sh->arc_w, gnn_graph_arc_labels(g), g->AL, g->AL, tmpl + c_agga, in_s, nullptr, 1))) return rc;
         if (l->D) {
             if ((rc = gnn_launch_spmm(st, N, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, g->nodes, g->NL, g->NL, tmpl + c_aggn, in_s, nullptr, 1))) return rc;
@@ -566,6 +610,8 @@ struct Forward {
     int upload_masks(const float *dropout_output, const uint8_t *masks_state, const uint8_t *masks_output)
     {
         Buf &buf = cx->buf;
+        size_t &mask_iter_bytes = cx->mask_iter_bytes;
+        uint8_t *&d_masks_s = cx->d_masks_s;
         int rc;
         // masks of one iteration of net_state: sum over the dropout positions of N * width bytes
         for (int i = 0; i <= l->st->n_layers; ++i) if (dropout_state[i] != 0.0f) mask_iter_bytes += (size_t)N * l->st->dims[i];
@@ -582,46 +628,35 @@ struct Forward {
         return GNN_OK;
     }
 
-    // body `enq`: the concat of states[enq] with its gate, net_state on it, the new state appended to states
+    // body `enq`: the concat of states[enq] with its gate, net_state on it, the new state appended to states.
+    // Recomputing step (cx->recompute): the new state table is allocated first and is all the arena keeps of the body - its concat, Dense
+    // outputs, xhat, keep bytes and weight images are handed out again for the next body (the statistics and the gate live in the zeroed block)
     int enqueue_body(int enq)
     {
-        gnn_graph *g = l->g;
         Buf &buf = cx->buf;
-        const int Ds = l->Ds, in_s = l->in_s, c_aggs = Ds + l->NLc;
         int rc;
-        float *inp = nullptr, *y = nullptr;
-        uint8_t *keep0 = nullptr;
-        const float r0 = dropout_state[0];
-        if ((rc = buf.get(&inp, (size_t)N * in_s))) return rc;
-        if (r0 != 0.0f && (rc = buf.get(&keep0, (size_t)N * in_s))) return rc;
-        const uint8_t *mk = d_masks_s ? d_masks_s + mask_iter_bytes * (size_t)enq : nullptr;
-        const MaskStream rng{seed, 0, enq, sharded ? g->row_begin : 0};
-        const float *state = states[enq], *own_cur = state + own_off * Ds, *own_prev = enq ? states[enq - 1] + own_off * Ds : (const float *)nullptr;
+        float *y = nullptr;
         int *gate = flags + (size_t)enq * GNN_FLAG_WORDS;
-        // few rows: k_mlp_fwd builds the concat rows itself (one launch for input + all Dense layers) and evaluates the gate
-        const InputBuild build{Ds, c_aggs, tmpl, state, own_cur, own_prev, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, l->thr, gate};
-        if (cx->ns.build_input || N == 0) {
-            // (a rank without rows: nothing to compute, it only takes part in the exchanges below)
-        } else if (r0 == 0.0f && state_rows16(Ds, N)) {
-            // many rows: the concat 16 lanes per row, gate i = condition(state_i, state_{i-1}) by k_check beside it
-            hipLaunchKernelGGL(k_train_input_rows, cdiv(N * 16, 256), 256, 0, st, N, in_s, Ds, c_aggs, tmpl, state, own_cur, g->sh->indptr, g->sh->adj_src,
-                               g->sh->adj_w, inp);
-            HIPCHK(hipGetLastError());
-            if ((rc = gnn_launch_check(st, N, Ds, own_cur, own_prev, l->thr, gate))) return rc;
-        } else {
-            // the input kernel of body i also evaluates gate i = condition(state_i, state_{i-1})
-            hipLaunchKernelGGL(k_train_input, cdiv(N * in_s, 256), 256, 0, st, N, in_s, Ds, c_aggs, tmpl, state, own_cur, g->sh->indptr, g->sh->adj_src,
-                               g->sh->adj_w, r0, mk, dropout_key(seed, 0, enq, 0), rng.row0 * in_s, keep0, inp, own_prev, l->thr, gate);
-            HIPCHK(hipGetLastError());
+        if (cx->recompute) {
+            FwdMode mode;
+            NetCache scratch;
+            if ((rc = buf.get(&mode.y_dst, (size_t)std::max<int64_t>(N, 1) * l->Ds))) return rc;
+            mode.cacheless = l->train.recompute == 1;
+            mode.cacheless_chain = &cx->cacheless_chain;
+            const gnn_train_arena::Mark mark = buf.arena->mark();
+            if ((rc = body_forward(l, cx, st, enq, gate, true, scratch, &y, nullptr, mode))) return rc;
+            buf.arena->rewind(mark);
+            cx->states.push_back(y);
+            return GNN_OK;
         }
         cx->caches.emplace_back();
-        if ((rc = net_forward(st, buf, cx->ns, inp, keep0, mk, rng, cx->caches.back(), &y, comm, &build))) return rc;
+        if ((rc = body_forward(l, cx, st, enq, gate, true, cx->caches.back(), &y, comm, FwdMode()))) return rc;
         if (sharded) {                               // the new rows of all ranks: what the next body gathers from
             float *rep = nullptr;
             if ((rc = train_replicate(l, buf, st, y, &rep))) return rc;
             y = rep;
         }
-        states.push_back(y);
+        cx->states.push_back(y);
         return GNN_OK;
     }
 
@@ -673,7 +708,7 @@ struct Forward {
             if ((rc = read_gates(enq, &k))) return rc;
             if (k < 0 && enq == max_iter) k = max_iter;
         }
-        cx->caches.resize((size_t)k);
+        cx->caches.resize((size_t)k);          // (recomputing step: k empty entries, rebuilt one at a time by train_backward)
         *k_out = k;
         return GNN_OK;
     }
@@ -691,7 +726,7 @@ struct Forward {
         int rc;
         if ((rc = cx->buf.get(&cache, pf.body_floats * (size_t)l->max_iter))) return rc;
         hflags[0] = 0; hflags[1] = 0;                  // [k, status]: the status word is cleared HERE, the kernel only ever sets it
-        const InputBuild build{Ds, Ds + l->NLc, tmpl, states[0], states[0], nullptr, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, l->thr, nullptr};
+        const InputBuild build{Ds, Ds + l->NLc, cx->tmpl, cx->states[0], cx->states[0], nullptr, g->sh->indptr, g->sh->adj_src, g->sh->adj_w, l->thr, nullptr};
         if ((rc = small_train_launch(st, ns, pf, build, l->max_iter, cache, flags, hflags))) return rc;
         HIPCHK(hipStreamSynchronize(st));
         if (hflags[1] != 0) { *gave_up = true; return GNN_OK; }
@@ -705,7 +740,7 @@ struct Forward {
             c.hin.assign(L, nullptr); c.a.assign(L, nullptr); c.keep.assign(L + 1, nullptr);
             for (int q = 0; q < L; ++q) { c.a[q] = blk + pf.off_a[q]; c.hin[q] = q == 0 ? blk : c.a[q - 1]; }
             if (m->has_bn) { c.xhat = blk + pf.off_xhat; c.stats = ns.stats_all + (size_t)b * 2 * F; }
-            states.push_back(m->has_bn ? blk + pf.off_y : c.a[L - 1]);
+            cx->states.push_back(m->has_bn ? blk + pf.off_y : c.a[L - 1]);
         }
         if (m->has_bn) ns.calls = k;
         cx->persistent = true; cx->workgroups = pf.grid; cx->barriers = pf.barriers;
@@ -801,6 +836,10 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     // Gradient mode 1 (the gradient at the fixed point, include/gnn_hip.h): the bodies are those of the INFERENCE Loop, with the loop's own
     // arithmetic and launch form; what follows records one training-mode body at the state it converged to.
     const bool fixed_point = l->train.adjoint.mode != 0;
+    // Recomputation of the bodies' activations (gnn_loop_set_train_recompute): the bodies keep their output state alone and run launch by
+    // launch; gradient modes 1 and 2 record one body anyway and ignore it
+    const bool recompute = l->train.recompute != 0 && !fixed_point;
+    if (recompute && sharded) return gnn_fail(GNN_ERR_UNSUPPORTED, "recomputation of the bodies' activations is single-GPU");
     float k_inference = 0.0f;
     if (fixed_point) {
         if (sharded) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient is single-GPU");
@@ -819,6 +858,7 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     gnn_train_ctx *cx = l->train_ctx = new gnn_train_ctx();
     cx->buf.arena = arena;
     cx->N = N; cx->M = M;
+    cx->recompute = recompute;
     Buf &buf = cx->buf;
     Forward f{l, cx, st, sharded, sharded ? l->comm : nullptr, N, M, sharded ? (size_t)l->own_off : 0, dropout_state, seed};
     // everything the step needs zeroed, in one block and one memset: gradients and BatchNormalization statistics of both nets, the
@@ -834,22 +874,23 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     if ((rc = net_setup(st, buf, cx->ns, l->st, dropout_state, bn_state, max_iter, zero_mem, N, true)) ||
         (rc = net_setup(st, buf, cx->no_, l->ou, dropout_output, bn_output, 1, zero_mem + z_s, M, false))) return rc;
     f.flags = reinterpret_cast<int *>(zero_mem + z_s + z_o);
-    f.tmpl = zero_mem + z_s + z_o + z_f;
+    cx->tmpl = zero_mem + z_s + z_o + z_f;
+    cx->seed = seed;
     if ((rc = f.by_source(src_indptr, src_dst, src_w)) || (rc = f.concat_template()) ||
         (rc = f.upload_masks(dropout_output, masks_state, masks_output))) return rc;
 
     // ---- while condition: state <- net_state(concat), training mode (GNN.py:271 with training=True) ----------------------
     // small batches: every body in ONE persistent launch (decided once per forward, here beside net_setup); else launch by launch
     SmallTrainForm pf;
-    if (allow_persistent && !sharded && !fixed_point && (rc = train_persistent_decide(l, cx->ns, &pf))) return rc;
+    if (allow_persistent && !sharded && !fixed_point && !recompute && (rc = train_persistent_decide(l, cx->ns, &pf))) return rc;
     f.hflags = static_cast<int *>(arena->host.get(std::max<size_t>(sizeof(int) * f.flag_words, 4096)));
     if (!f.hflags) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
     if (sharded && l->D) {
         float *rep0 = nullptr;
         if ((rc = train_replicate(l, buf, st, l->state_init, &rep0))) return rc;
-        f.states.push_back(rep0);
+        cx->states.push_back(rep0);
     } else
-        f.states.push_back(const_cast<float *>(l->D ? l->state_init : g->nodes));      // (D == 0: the node labels, a replica already)
+        cx->states.push_back(const_cast<float *>(l->D ? l->state_init : g->nodes));      // (D == 0: the node labels, a replica already)
     int k = 0;
     if (fixed_point) {
         // p = the state after the k bodies of the inference Loop, copied out of the loop's tables (publish() below rewrites them); the recorded
@@ -858,7 +899,7 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
         if ((rc = buf.get(&p, (size_t)std::max<int64_t>(N, 1) * l->Ds))) return rc;
         k = (int)k_inference;
         if (N) HIPCHK(hipMemcpyAsync(p, gnn_loop_state_after(l, l->kfinal, 0), sizeof(float) * (size_t)N * l->Ds, hipMemcpyDeviceToDevice, st));
-        f.states[0] = p;
+        cx->states[0] = p;
         if ((rc = f.enqueue_body(0))) return rc;
         cx->fixed_point = true;
         cx->state = p;
@@ -868,7 +909,7 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
             if (*gave_up) return GNN_OK;
         } else if ((rc = f.bodies_by_launch(&k)))
             return rc;
-        cx->state = f.states[(size_t)k];
+        cx->state = cx->states[(size_t)k];
         l->train.k_hint = k;
     }
     if ((rc = f.output(cx->state))) return rc;
@@ -927,6 +968,29 @@ extern "C" int gnn_loop_train_info(const gnn_loop *l, int *out)
     out[1] = cx ? cx->workgroups : 0;
     out[2] = cx ? cx->barriers : 0;
     out[3] = l->train.persistent.timeouts;
+    return GNN_OK;
+}
+
+// Recomputation of the bodies' activations in the unrolled step (include/gnn_hip.h).  enable: 0 off, 1 on, 2 on with the caching kernels in
+// the first pass (A/B runs); *used: whether a training forward of this loop would take the mode now
+extern "C" int gnn_loop_set_train_recompute(gnn_loop *l, int enable, int *used)
+{
+    ARGCHK(l, "loop is NULL");
+    if (enable != 0 && l->world > 1)
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "recomputation of the bodies' activations is single-GPU, like the training step: this loop is rank %d of %d", l->rank, l->world);
+    l->train.recompute = enable == 0 ? 0 : (enable == 2 ? 2 : 1);
+    if (used) *used = enable != 0 && l->train.adjoint.mode == 0 ? 1 : 0;
+    return GNN_OK;
+}
+
+// out[3]: the last training forward ran state-only; bodies replayed by the last backward pass; 1 when the first pass launched the cache-less chain
+extern "C" int gnn_loop_train_recompute_info(const gnn_loop *l, int *out)
+{
+    ARGCHK(l && out, "bad arguments");
+    const gnn_train_ctx *cx = l->train_ctx;
+    out[0] = cx && cx->recompute ? 1 : 0;
+    out[1] = cx ? cx->replayed : 0;
+    out[2] = cx ? cx->cacheless_chain : 0;
     return GNN_OK;
 }
 
@@ -1102,10 +1166,34 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
         }
     }
     if (cx->fixed_point && (rc = adjoint_backward(l, cx, st, d_state))) return rc;
+    // Recomputing step: body `it` is rebuilt from states[it] on scratch that every body reuses, immediately before its backward pass - the same
+    // kernels on the same inputs in the same fixed order, so the rebuilt cache holds the first pass's bits.  All that outlives a body's
+    // rewind is allocated here, ahead of the mark: the two d_prev buffers used in turn, net_state's chunk partials (Net::part is remembered
+    // from call to call) and the scratch gate block of the kernels that evaluate a gate in passing.
+    const bool replay = cx->recompute && k > 0;
+    float *d_turn[2] = {nullptr, nullptr};
+    int *scratch_gate = nullptr;
+    gnn_train_arena::Mark body_mark{};
+    if (replay) {
+        if ((rc = buf.get(&d_turn[0], (size_t)N * Ds)) || (rc = buf.get(&d_turn[1], (size_t)N * Ds)) || (rc = buf.get(&scratch_gate, (size_t)GNN_FLAG_WORDS))) return rc;
+        if (N > 0 && ns.part_rows != N) {
+            if ((rc = buf.get(&ns.part, (size_t)cdiv(N, rows_per_block(N)) * ns.g_total))) return rc;
+            ns.part_rows = N;
+        }
+        body_mark = buf.arena->mark();
+    }
     for (int it = k - 1; it >= 0; --it) {
         // net_backward consumes d_state (d loss / d state_{it+1}) in place; its last launch also writes d loss / d state_it into a new buffer
         float *d_inp = nullptr, *d_prev = nullptr;
-        if ((rc = buf.get(&d_prev, (size_t)N * Ds))) return rc;
+        if (replay) {
+            buf.arena->rewind(body_mark);
+            float *y = nullptr;
+            FwdMode mode;
+            mode.replay_call = l->st->has_bn ? it : -1;
+            if ((rc = body_forward(l, cx, st, it, scratch_gate, false, cx->caches[it], &y, nullptr, mode))) return rc;
+            ++cx->replayed;
+            d_prev = d_turn[(k - 1 - it) & 1];
+        } else if ((rc = buf.get(&d_prev, (size_t)N * Ds))) return rc;
         if (sharded) {
             if ((rc = net_backward(st, buf, ns, cx->caches[it], d_state, &d_inp, nullptr, comm, cx->N_global))) return rc;
             // d state_it[r] = d inp[r, :Ds] + sum over the arcs r -> dst of w * d inp[dst, c_aggs:]: the aggregate columns of all ranks first
@@ -1190,6 +1278,8 @@ extern "C" int gnn_loop_train_mask(const gnn_loop *l, int net, int body, int pos
     const Net &n = net == 0 ? cx->ns : cx->no_;
     ARGCHK(net == 1 || (body >= 0 && body < cx->k), "body %d: the last training forward ran %d", body, cx->k);
     ARGCHK(pos >= 0 && pos <= n.m->n_layers && n.rate[pos] != 0.0f, "no Dropout at position %d of this net", pos);
+    if (net == 0 && cx->recompute)
+        return gnn_fail(GNN_ERR_STATE, "the last training forward recomputes its activations (gnn_loop_set_train_recompute): net_state's keep bytes are scratch, not alive");
     const NetCache &c = net == 0 ? cx->caches[(size_t)body] : cx->co;
     if ((size_t)pos >= c.keep.size() || !c.keep[pos]) return gnn_fail(GNN_ERR_STATE, "internal: no mask recorded at position %d", pos);
     *count = n.rows * n.m->dims[pos];

@@ -146,6 +146,8 @@ __global__ void __launch_bounds__(256) k_bn_stats(int64_t n, int F, int cw_shift
 // batch mean / biased batch variance from the chunk statistics, then xhat = (h - mean) / sqrt(var + eps), y = gamma xhat + beta.
 // Every block combines the chunks itself (256 / CW lanes per column take every (256 / CW)-th chunk, the lanes are merged in order);
 // block 0 leaves [mean | var] in stats for the backward pass and the moving statistics.  Dynamic LDS: 2 F floats.
+// XHAT = false (the state-only first pass of the recomputing step): xhat, which only the backward pass reads, is not written.
+template <bool XHAT>
 __global__ void __launch_bounds__(256) k_bn_apply(int64_t n, int F, int cw_shift, const float *__restrict__ h, const float *__restrict__ part, int parts,
                                                   int64_t rows_per_block, float eps, const float *gamma, const float *beta, float *xhat, float *y, float *stats)
 {
@@ -157,7 +159,9 @@ __global__ void __launch_bounds__(256) k_bn_apply(int64_t n, int F, int cw_shift
     const bool small = total < ((int64_t)1 << 31);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
         const int j = small ? (int)((unsigned)i % (unsigned)F) : (int)(i % F);
-        bn_normalize(h[i], sm[j], sinv[j], gamma[j], beta[j], &xhat[i], &y[i]);
+        float xh;
+        bn_normalize(h[i], sm[j], sinv[j], gamma[j], beta[j], &xh, &y[i]);
+        if constexpr (XHAT) xhat[i] = xh;
     }
 }
 
@@ -597,7 +601,7 @@ int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float 
 // comm != NULL (sharded forward, one process per rank): the BatchNormalization statistics are those of the rows of ALL ranks.
 // net.build_input: x has NOT been filled - k_mlp_fwd builds the concat rows itself (and writes them to x for the backward pass) from *build.
 int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, const uint8_t *masks, const MaskStream &rng, NetCache &c, float **y_out,
-                gnn_comm *comm, const InputBuild *build)
+                gnn_comm *comm, const InputBuild *build, const FwdMode &mode)
 {
     const gnn_mlp *m = net.m;
     const int L = m->n_layers;
@@ -608,12 +612,20 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
     size_t mask_off = 0;
     int rc;
     int l_start = 0;
+    // the array that is the call's output (mode.y_dst takes its place): BatchNormalization's, else the Dropout's behind the last Dense layer, else that layer's
+    const bool out_is_drop = !m->has_bn && net.rate[L] != 0.0f, out_is_dense = !m->has_bn && net.rate[L] == 0.0f;
+    auto get_a = [&](int l) -> int {
+        if (l == L - 1 && out_is_dense && mode.y_dst) { c.a[l] = mode.y_dst; return GNN_OK; }
+        return buf.get(&c.a[l], (size_t)n * m->dims[l + 1]);
+    };
     if (net.fwd3) {                                // the three Dense layers in one pass (k_fwd3_split)
         if (net.rate[0] != 0.0f) { c.keep[0] = keep0; mask_off += (size_t)n * m->dims[0]; }
-        for (int l = 0; l < 3; ++l)
-            if ((rc = buf.get(&c.a[l], (size_t)n * m->dims[l + 1]))) return rc;
+        const bool keep = !mode.cacheless;         // (cache-less: a0 and a1 are neither allocated nor written)
+        for (int l = keep ? 0 : 2; l < 3; ++l)
+            if ((rc = get_a(l))) return rc;
         c.hin[0] = x; c.hin[1] = c.a[0]; c.hin[2] = c.a[1];
         if ((rc = launch_fwd3(st, buf, m, n, x, c.a[0], c.a[1], c.a[2]))) return rc;
+        if (!keep && mode.cacheless_chain) *mode.cacheless_chain = 1;
         h = c.a[2];
         l_start = L;
     }
@@ -622,8 +634,8 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
         if (net.rate[l] != 0.0f) {
             if (l == 0 && keep0) c.keep[0] = keep0;
             else {
-                float *hd = nullptr;
-                if ((rc = buf.get(&hd, (size_t)n * width)) || (rc = buf.get(&c.keep[l], (size_t)n * width))) return rc;
+                float *hd = l == L && out_is_drop ? mode.y_dst : nullptr;
+                if ((!hd && (rc = buf.get(&hd, (size_t)n * width))) || (rc = buf.get(&c.keep[l], (size_t)n * width))) return rc;
                 if (n > 0) {
                     hipLaunchKernelGGL(k_dropout_fwd, cdiv(n * width, 256), 256, 0, st, n * width, h, masks ? masks + mask_off : nullptr, net.rate[l],
                                        dropout_key(rng.seed, rng.net, rng.body, l), rng.row0 * width, c.keep[l], hd);
@@ -646,7 +658,7 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
             p.n = n; p.X = h;
             mlp_fwd_describe(p, m, net.small_maxpad);
             for (int q = 0; q < L; ++q) {
-                if ((rc = buf.get(&c.a[q], (size_t)n * m->dims[q + 1]))) return rc;
+                if ((rc = get_a(q))) return rc;
                 p.Y[q] = c.a[q];
                 c.hin[q] = q == 0 ? h : c.a[q - 1];
             }
@@ -662,7 +674,7 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
         }
         const int no = m->dims[l + 1];
         c.hin[l] = h;
-        if ((rc = buf.get(&c.a[l], (size_t)n * no))) return rc;
+        if ((rc = get_a(l))) return rc;
         const bool sm = m->acts[l] == GNN_ACT_SOFTMAX;          // softmax needs the whole row: separate pass, in place
         if (net.wide_fwd[l]) {                     // wide layer on many rows: matrix cores
             if ((rc = launch_gemm_f32(st, buf, n, width, no, h, m->W[l], m->b[l], m->acts[l], 0, nullptr, 0.0f, nullptr, c.a[l]))) return rc;
@@ -683,10 +695,17 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
     }
     if (m->has_bn) {
         const int F = m->dims.back();
-        float *y = nullptr;
-        if ((rc = buf.get(&c.xhat, (size_t)n * F)) || (rc = buf.get(&y, (size_t)n * F))) return rc;
-        if (net.calls >= std::max(1, net.max_calls)) return gnn_fail(GNN_ERR_STATE, "more BatchNormalization calls than announced");
-        c.stats = net.stats_all + (size_t)net.calls++ * 2 * F;
+        float *y = mode.y_dst, *stats_out = nullptr;
+        const bool want_xhat = !mode.cacheless || comm;
+        if ((want_xhat && (rc = buf.get(&c.xhat, (size_t)n * F))) || (!y && (rc = buf.get(&y, (size_t)n * F)))) return rc;
+        if (mode.replay_call >= 0) {               // a repeated call: its slot as the first pass left it, the recomputed statistics to scratch
+            if (mode.replay_call >= net.calls || comm) return gnn_fail(GNN_ERR_STATE, "internal: replay of BatchNormalization call %d of %d", mode.replay_call, net.calls);
+            c.stats = net.stats_all + (size_t)mode.replay_call * 2 * F;
+            if ((rc = buf.get(&stats_out, (size_t)2 * F))) return rc;
+        } else {
+            if (net.calls >= std::max(1, net.max_calls)) return gnn_fail(GNN_ERR_STATE, "more BatchNormalization calls than announced");
+            c.stats = stats_out = net.stats_all + (size_t)net.calls++ * 2 * F;
+        }
         if (comm) {
             // every rank takes part in the exchange, also one without rows (count 0)
             float *tri = nullptr, *tri_all = nullptr;
@@ -712,8 +731,12 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
             if ((rc = buf.get(&part, (size_t)parts * 2 * F))) return rc;
             const int cs = column_shift(F);
             hipLaunchKernelGGL(k_bn_stats, dim3(cdiv(F, 1 << cs), parts), 256, 0, st, n, F, cs, h, part, rpb);
-            hipLaunchKernelGGL(k_bn_apply, elementwise_grid(n * F), 256, sizeof(float) * 2 * F, st, n, F, cs, h, part, parts, rpb, m->eps, net.gamma,
-                               net.beta, c.xhat, y, c.stats);
+            if (want_xhat)
+                hipLaunchKernelGGL(k_bn_apply<true>, elementwise_grid(n * F), 256, sizeof(float) * 2 * F, st, n, F, cs, h, part, parts, rpb, m->eps, net.gamma,
+                                   net.beta, c.xhat, y, stats_out);
+            else
+                hipLaunchKernelGGL(k_bn_apply<false>, elementwise_grid(n * F), 256, sizeof(float) * 2 * F, st, n, F, cs, h, part, parts, rpb, m->eps, net.gamma,
+                                   net.beta, static_cast<float *>(nullptr), y, stats_out);
             HIPCHK(hipGetLastError());
         }
         h = y;

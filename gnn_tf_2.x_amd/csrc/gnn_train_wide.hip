@@ -326,7 +326,9 @@ struct Fwd3Args {
     float *A0, *A1, *A2;
 };
 
-template <int ACT>
+// KEEP = false (the state-only first pass of the recomputing step, gnn_loop_set_train_recompute): a0 and a1 are neither staged nor stored - the
+// same products and epilogues, so a2 holds the same bits; p.A0 / p.A1 are not read.
+template <int ACT, bool KEEP = true>
 __global__ void __launch_bounds__(64 * TG_WAVES, 2) k_fwd3_split(const Fwd3Args p)
 {
     using namespace gnn_fused_dev;
@@ -426,9 +428,9 @@ __global__ void __launch_bounds__(64 * TG_WAVES, 2) k_fwd3_split(const Fwd3Args 
         f32x16 h1[4], h2[4], out[2];
         layer0_split<4, true>(X + node * KP + 8 * half, wrs, lane * 16, 0, p.chunks0, h1, hb, half);
         layer_split_from_regs<4, 4, ACT>(h1, hb + 128, half, h2, wrs, lane * 16, p.off1);       // h1 now holds the (folded) activations of layer 0
-        store_rows(h1, std::integral_constant<int, 4>{}, p.A0, p.w1, nvalid, i0, UNFOLD, false);
+        if constexpr (KEEP) store_rows(h1, std::integral_constant<int, 4>{}, p.A0, p.w1, nvalid, i0, UNFOLD, false);
         layer_split_from_regs<4, 2, ACT>(h2, hb + 256, half, out, wrs, lane * 16, p.off2);
-        store_rows(h2, std::integral_constant<int, 4>{}, p.A1, p.w2, nvalid, i0, UNFOLD, false);
+        if constexpr (KEEP) store_rows(h2, std::integral_constant<int, 4>{}, p.A1, p.w2, nvalid, i0, UNFOLD, false);
         store_rows(out, std::integral_constant<int, 2>{}, p.A2, p.w3, nvalid, i0, 1.0f, true);
     }
 }
@@ -524,6 +526,15 @@ int launch_fwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, int64_t n, const flo
                          reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_SELU>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_ELU>),
                          reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_TANH>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_SIGMOID>)};
     (void)gnn_raise_dynamic_lds(ks, 6, 160 * 1024, lds_raised);
+    const bool keep = a0 != nullptr || a1 != nullptr;
+    if (keep && !(a0 && a1)) return gnn_fail(GNN_ERR_STATE, "internal: the three-layer chain stores both hidden activations or neither");
+    if (!keep) {
+        static bool lds_raised_nk[64] = {false};
+        const void *nk[6] = {reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_LINEAR, false>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_RELU, false>),
+                             reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_SELU, false>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_ELU, false>),
+                             reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_TANH, false>), reinterpret_cast<const void *>(&k_fwd3_split<GNN_ACT_SIGMOID, false>)};
+        (void)gnn_raise_dynamic_lds(nk, 6, 160 * 1024, lds_raised_nk);
+    }
     Fwd3Args p{};
     p.n = n; p.K = m->dims[0]; p.w1 = m->dims[1]; p.w2 = m->dims[2]; p.w3 = m->dims[3]; p.act = m->acts[0];
     p.KP = std::max(tg_kps(p.K), tg_kps(128));
@@ -544,14 +555,24 @@ int launch_fwd3(hipStream_t st, Buf &buf, const gnn_mlp *m, int64_t n, const flo
     if (lds > 160 * 1024) return gnn_fail(GNN_ERR_UNSUPPORTED, "fused forward: LDS");
     const int64_t n_tiles = (n + 31) / 32;
     const unsigned grid = (unsigned)std::min<int64_t>(TG_MAX_GRID, (n_tiles + TG_WAVES - 1) / TG_WAVES);
-    switch (p.act) {
-    case GNN_ACT_LINEAR: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_LINEAR>), grid, 64 * TG_WAVES, lds, st, p); break;
-    case GNN_ACT_RELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_RELU>), grid, 64 * TG_WAVES, lds, st, p); break;
-    case GNN_ACT_SELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_SELU>), grid, 64 * TG_WAVES, lds, st, p); break;
-    case GNN_ACT_ELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_ELU>), grid, 64 * TG_WAVES, lds, st, p); break;
-    case GNN_ACT_TANH: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_TANH>), grid, 64 * TG_WAVES, lds, st, p); break;
-    default: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_SIGMOID>), grid, 64 * TG_WAVES, lds, st, p); break;
-    }
+    if (keep)
+        switch (p.act) {
+        case GNN_ACT_LINEAR: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_LINEAR>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_RELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_RELU>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_SELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_SELU>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_ELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_ELU>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_TANH: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_TANH>), grid, 64 * TG_WAVES, lds, st, p); break;
+        default: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_SIGMOID>), grid, 64 * TG_WAVES, lds, st, p); break;
+        }
+    else
+        switch (p.act) {
+        case GNN_ACT_LINEAR: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_LINEAR, false>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_RELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_RELU, false>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_SELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_SELU, false>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_ELU: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_ELU, false>), grid, 64 * TG_WAVES, lds, st, p); break;
+        case GNN_ACT_TANH: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_TANH, false>), grid, 64 * TG_WAVES, lds, st, p); break;
+        default: hipLaunchKernelGGL((k_fwd3_split<GNN_ACT_SIGMOID, false>), grid, 64 * TG_WAVES, lds, st, p); break;
+        }
     HIPCHK(hipGetLastError());
     return GNN_OK;
 }

@@ -510,6 +510,27 @@ int gnn_train_persistent_form(int n_layers, const int *dims, const int *acts, co
 /* What the last training forward of this loop did: out[0] = 1 when its bodies ran in the persistent launch, out[1] = workgroups and
  * out[2] = grid barriers per body of that launch (0 otherwise); out[3] = time-out fall-backs of this loop so far. */
 int gnn_loop_train_info(const gnn_loop *l, int *out);
+/* Recomputation of the bodies' activations in the UNROLLED training step (opt-in, off by default; with it off every launch, allocation and
+ * result is unchanged).  Back-propagation through the unrolled loop otherwise keeps every body's cache - concat, Dense outputs, Dropout keep
+ * bytes, xhat - from the forward pass until the backward pass reaches it.  With the mode on, the bodies of gnn_loop_train_forward /
+ * gnn_loop_train_step run launch by launch (same chunks, gates and k) and keep only: the body's output state table, its BatchNormalization
+ * batch statistics and its gate words; everything else is scratch that the next body reuses.  gnn_loop_train_backward rebuilds body i's cache
+ * from the state body i read, immediately before that body's backward pass: the same input kernel, the same forward form, the same Dropout
+ * stream (seed, net 0, body i) or slice of the injected masks.  Every reduction has a fixed order, so the rebuilt cache holds the first
+ * pass's bits and every result of the step - loss, k, gradients, statistics, d_nodes, d_arc_labels - equals the default step's bit for bit.
+ * A replayed body is no BatchNormalization call (call count, recorded statistics and moving statistics are the first pass's; it recomputes
+ * the statistics into scratch) and evaluates no gate.  It is the reference's gradient, for every net the unrolled step handles.
+ *   enable   0 off; 2 on with the ordinary (caching) kernels in the first pass instead of the cache-less forms (A/B runs); any other value on
+ *   *used    (may be NULL) whether a training forward of this loop would take the mode now
+ * enable != 0 on a loop of world > 1: GNN_ERR_UNSUPPORTED (the mode is single-GPU, like the training step).  In gradient modes 1 and 2
+ * (gnn_loop_set_gradient_mode) the setting is accepted and has no effect (*used = 0): one body is recorded there anyway.  With the mode on,
+ * the persistent training forward is not taken (gnn_loop_train_info reports 0), and gnn_loop_train_mask for net 0 returns GNN_ERR_STATE
+ * after such a forward: the keep bytes of net_state are not alive (net 1 and gnn_loop_train_forms answer as ever). */
+int gnn_loop_set_train_recompute(gnn_loop *l, int enable, int *used);
+/* out[3]: out[0] = 1 when the last training forward of this loop ran state-only; out[1] = bodies replayed by the last backward pass (k after
+ * a complete one); out[2] = the form of net_state in the first pass: 1 when the cache-less three-layer chain (k_fwd3_split without its a0 / a1
+ * stores) was launched, 0 when the ordinary kernels ran on scratch. */
+int gnn_loop_train_recompute_info(const gnn_loop *l, int *out);
 /* Introspection for tests: the keep bytes (1 = kept) that the last gnn_loop_train_forward / gnn_loop_train_step of this loop recorded for the
  * Dropout at position pos (0 .. n_layers, the index of dropout_state / dropout_output) of net 0 (net_state, in body `body` < k) or 1
  * (net_output, body ignored) - the mask that was APPLIED, whether injected or drawn.  *count = rows * width of that position (this rank's rows /
