@@ -45,6 +45,7 @@ class GNNnodeBased(BaseClass):
         self.adjoint_threshold = None
         self.label_projection = 'off'       # set_label_projection
         self.train_recompute = False        # set_train_recompute
+        self.wide_state = 'off'             # set_wide_state
 
     def set_train_recompute(self, enable: bool) -> None:
         """Activation recomputation in the unrolled training step (off by default).  Back-propagation through the unrolled loop keeps every
@@ -66,6 +67,17 @@ class GNNnodeBased(BaseClass):
         and by save() / load()."""
         code = _engine.label_projection_mode(mode)
         self.label_projection = {v: k for k, v in _engine.LABEL_PROJECTION_MODES.items()}[code]
+
+    def set_wide_state(self, mode) -> None:
+        """The fused Loop for state_vect_dim 68 .. 128.  The fused kernels keep the net_state input of 32 nodes per wave in on-chip memory,
+        eight waves per workgroup, and [state | aggregated state] alone is past that for a state wider than 72: such a model runs one
+        kernel per operation.  With this form the iteration kernel runs on 4 to 7 waves per workgroup, as many as fit, and loads its tiles
+        with a loader for wide rows.  'off' / 0 (default), 'auto' / 1: where it was measured faster than one kernel per operation,
+        'always' / 2: wherever it is covered.  state_vect_dim a multiple of 4; with about a dozen label columns at 128, or any label width
+        together with set_label_projection.  The arithmetic per node is unchanged (impl 1 stays bit-exact, impl 2 within 1e-5);
+        training-mode Loops run as without it.  Kept by copy() (so by LKO) and by save() / load()."""
+        code = _engine.wide_state_mode(mode)
+        self.wide_state = {v: k for k, v in _engine.WIDE_STATE_MODES.items()}[code]
 
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
         """How train() differentiates the state loop.  'unrolled' (default): back-propagation through every executed body.
@@ -102,6 +114,7 @@ class GNNnodeBased(BaseClass):
         new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
         new.set_label_projection(self.label_projection)
         new.set_train_recompute(self.train_recompute)
+        new.set_wide_state(self.wide_state)
         return new
 
     def save(self, path: str):
@@ -122,7 +135,7 @@ class GNNnodeBased(BaseClass):
                        'optimizer': optimizers.serialize(self.optimizer), 'max_iteration': self.max_iteration, 'threshold': self.state_threshold,
                        'addressed_problem': self.addressed_problem, 'state_vect_dim': self.state_vect_dim,
                        'gradient_mode': self._gradient_config(), 'label_projection': self.label_projection,
-                       'train_recompute': self.train_recompute}, f)
+                       'train_recompute': self.train_recompute, 'wide_state': self.wide_state}, f)
 
     @classmethod
     def load(cls, path: str, path_writer=None, namespace: str = 'GNN', extra_metrics=None, extra_metrics_arguments=None):
@@ -140,6 +153,7 @@ class GNNnodeBased(BaseClass):
         gradient = config.pop('gradient_mode', None) or {'mode': 'unrolled'}      # (a model saved before the mode existed: unrolled)
         projection = config.pop('label_projection', None) or 'off'                # (a model saved before the key existed: off)
         recompute = bool(config.pop('train_recompute', False))                    # (likewise)
+        wide_state = config.pop('wide_state', None) or 'off'                      # (likewise)
         nets = []
         for name in ('net_state', 'net_output'):
             with open(f'{path}{name}.json') as f:
@@ -152,6 +166,7 @@ class GNNnodeBased(BaseClass):
         model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'))
         model.set_label_projection(projection)
         model.set_train_recompute(recompute)
+        model.set_wide_state(wide_state)
         return model
 
     def get_dense_layers(self):
@@ -203,6 +218,9 @@ class GNNnodeBased(BaseClass):
         if getattr(loop, '_projection_set', 'off') != self.label_projection:
             loop.set_label_projection(self.label_projection)
             loop._projection_set = self.label_projection
+        if getattr(loop, '_wide_state_set', 'off') != self.wide_state:
+            loop.set_wide_state(self.wide_state)
+            loop._wide_state_set = self.wide_state
         if getattr(loop, '_recompute_set', False) != self.train_recompute:
             loop.set_train_recompute(self.train_recompute)
             loop._recompute_set = self.train_recompute

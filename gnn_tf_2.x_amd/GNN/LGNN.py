@@ -39,6 +39,10 @@ class LGNN(BaseClass):
         """GNNnodeBased.set_label_projection for every layer (the layers behind the first see labels widened by states / outputs)."""
         for gnn in self.gnns: gnn.set_label_projection(mode)
 
+    def set_wide_state(self, mode) -> None:
+        """GNNnodeBased.set_wide_state for every layer."""
+        for gnn in self.gnns: gnn.set_wide_state(mode)
+
     def set_train_recompute(self, enable: bool) -> None:
         """GNNnodeBased.set_train_recompute for every layer: the joint steps of 'parallel' / 'residual' hold the training forward of every
         layer until the backward passes run, so the layers' activations are alive together."""

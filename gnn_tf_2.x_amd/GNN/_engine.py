@@ -25,7 +25,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
-           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
+           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
 
@@ -140,6 +140,25 @@ def label_projection_form(dims, activations, state_dim, nl, al, n_rows, mode) ->
     _check(lib().gnn_label_projection_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(state_dim)), C.c_int(int(nl)), C.c_int(int(al)),
                                            C.c_int64(int(n_rows)), C.c_int(label_projection_mode(mode)), _ip(out)))
     return dict(seeded=bool(out[0]), kernel=int(out[1]), iw=int(out[2]), tiles=int(out[3]))
+
+
+WIDE_STATE_MODES = LABEL_PROJECTION_MODES       # modes of gnn_loop_set_wide_state: the same three
+wide_state_mode = label_projection_mode
+
+
+def wide_state_form(dims, activations, state_dim, nl, al, n_rows, mode, label_projection='off') -> dict:
+    """gnn_wide_state_form (host code, no device): what Loop.set_wide_state(mode) answers for a net_state of this description (arguments as
+    label_projection_form) with the label projection in mode label_projection - dict(taken; kernel: 0, or 1 = k_fused_generic; waves: waves
+    per workgroup of the launch, 4 .. 7; seeded: the launch is the label projection's).  impl 2, a single GPU and no feature-sliced exchange
+    are the loop's part, taken at their defaults."""
+    L = len(dims) - 1
+    if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
+    d = np.ascontiguousarray(dims, np.int32)
+    a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
+    out = np.zeros(4, np.int32)
+    _check(lib().gnn_wide_state_form(C.c_int(L), _ip(d), _ip(a), C.c_int(int(state_dim)), C.c_int(int(nl)), C.c_int(int(al)), C.c_int64(int(n_rows)),
+                                     C.c_int(wide_state_mode(mode)), C.c_int(label_projection_mode(label_projection)), _ip(out)))
+    return dict(taken=bool(out[0]), kernel=int(out[1]), waves=int(out[2]), seeded=bool(out[3]))
 
 
 TRAIN_PERSISTENT_MAX_BYTES = 256 << 20      # GNN_TRAIN_PERSISTENT_MAX_BYTES of include/gnn_hip.h
@@ -923,6 +942,36 @@ class Loop:
         (impl 2 with one launch per body only)."""
         used = C.c_int(0)
         _check(lib().gnn_loop_set_label_projection(self._h, C.c_int(label_projection_mode(mode)), C.byref(used)))
+        return bool(used.value)
+
+    def set_wide_state(self, mode) -> bool:
+        """gnn_loop_set_wide_state: the one-launch-per-body Loop for state widths 68 .. 128 - k_fused_generic on a workgroup of 4 to 7
+        waves, as many 32-node tiles as fit its LDS.  mode 'off' | 'auto' (where it was measured faster than one kernel per op) | 'always'
+        (wherever it is covered and the eight-wave path is not), or 0 | 1 | 2.  Returns whether the next run takes the form."""
+        used = C.c_int()
+        _check(lib().gnn_loop_set_wide_state(self._h, C.c_int(wide_state_mode(mode)), C.byref(used)))
+        return bool(used.value)
+
+    def body_launch(self) -> tuple:
+        """gnn_loop_body_launch (test hook): (waves per workgroup, workgroups) of the launch per body of the last form decision; (0, 0): none."""
+        out = np.zeros(2, np.int32)
+        _check(lib().gnn_loop_body_launch(self._h, _ip(out)))
+        return int(out[0]), int(out[1])
+
+    def set_grid_limit(self, n) -> int:
+        """gnn_loop_set_grid_limit (test hook): at most n workgroups per k_fused_generic launch, 0 = the library's choice.  Returns the
+        grid of the next run's launch per body."""
+        if isinstance(n, bool) or int(n) != n or int(n) < 0: raise ValueError('param <n> must be an integer >= 0')
+        used = C.c_int()
+        _check(lib().gnn_loop_set_grid_limit(self._h, C.c_int(int(n)), C.byref(used)))
+        return int(used.value)
+
+    def set_wide_loader(self, loader) -> bool:
+        """gnn_loop_set_wide_loader (test hook): the tile loader of the wide-state form's full tiles, 'wide' (load_tile_wide, the default)
+        or 'generic' (load_tile_generic); same bits.  Returns whether the next run's launches use load_tile_wide."""
+        if loader not in ('wide', 'generic'): raise ValueError("param <loader> not in ['wide', 'generic']")
+        used = C.c_int()
+        _check(lib().gnn_loop_set_wide_loader(self._h, C.c_int(0 if loader == 'wide' else 1), C.byref(used)))
         return bool(used.value)
 
     def label_projection(self) -> np.ndarray:

@@ -359,6 +359,10 @@ struct gnn_loop {
     size_t proj_floats = 0;
     int proj_nt = 0;
     uint64_t proj_labels = 0, proj_weights = ~(uint64_t)0;
+    // wide-state form: gnn_loop_set_wide_state's mode (0 off, 1 where measured faster than one kernel per op, 2 wherever covered), its tile
+    // loader (gnn_loop_set_wide_loader: 0 load_tile_wide, 1 load_tile_generic) and the cap on the grid of k_fused_generic launches
+    // (gnn_loop_set_grid_limit, 0: none) - test entry points both
+    int wide_state = 0, wide_loader = 0, grid_limit = 0;
     float *tmp[2] = {nullptr, nullptr};     // unfused: layer activations
     float *feats = nullptr, *out = nullptr, *otmp[2] = {nullptr, nullptr};
     int *flags = nullptr;                   // [(max_iter+2), world, GNN_FLAG_WORDS]

@@ -62,7 +62,7 @@ struct GnnFusedArgs {
     int ws_bytes, ws_off[GNN_FUSED_MAXL];
     int tile_base;           // first tile of this launch (tickets count from it)
     int full_tiles;          // 1: state width 64 - launch the full-tile specialisation of the kernel (a partial last tile takes its masked branch)
-    int variant;             // tuning switches (bit 0: raised wave priority during the gather); fixed in the shipped build
+    int variant;             // tuning switches (bit 0: raised wave priority during the gather); fixed in the shipped build.  Bit 3: the wide-state form's full tiles through load_tile_wide
     // feature-sliced exchange: aggregated states of the owned rows [n_rows, Ds], computed outside the kernel (no gather), else nullptr
     const float *agg_in;
     // gather program of the graph (gnn_gather_program_build; gather form 2 of the full-tile kernel), or gp_tiles == 0: walk the CSR.
@@ -74,7 +74,7 @@ struct GnnFusedArgs {
     // the launch stands for the tile of slot s, the partial last tile an ordinary slot; the program kernel reads its headers from here
     const int32_t *gp_hdr, *gp_ent, *gp_slot;
     int gp_tiles, gp_last_first, gp_last_nb, gp_slots;
-    int threads;             // threads per workgroup of the launch (0: GNN_FUSED_THREADS)
+    int threads;             // threads per workgroup of the launch (0: GNN_FUSED_THREADS); 256 .. 448 in the wide-state form of k_fused_generic
     int single_ticket;       // 1: the launch has no more tiles than waves - a wave draws ONE ticket at start (no look-ahead tile)
     // diagnostics only (GNN_FUSED_STAMPS=<file>): s_memtime stamps per wave at the phase boundaries, else nullptr
     unsigned long long *stamps;
@@ -150,7 +150,8 @@ struct FusedPlan {
 enum GnnLoopPath { GNN_PATH_UNFUSED = 0, GNN_PATH_BODIES = 1, GNN_PATH_PERSISTENT = 2 };      // one kernel per TF op / one launch per body / all bodies in one launch
 enum GnnBodyKernel { GNN_BODY_GENERIC = 0, GNN_BODY_FULL_TILE = 1, GNN_BODY_PAIR = 2 };       // k_fused_generic / k_fused_full / k_fused_pair
 // What the launchers of gnn_fused_kernel.h pick an instantiation by, beyond the net's shape.  Host side only: no kernel sees it.
-// (GnnFusedArgs still carries full_tiles, gp_tiles and pieces, which no kernel and no launcher reads, beside seven more unread fields:
+// (GnnFusedArgs still carries full_tiles, gp_tiles and pieces, which no kernel and no launcher reads, beside six more unread fields -
+// `threads` is the launcher's block size since the wide-state form -:
 // taking fields out moves every kernel's argument offsets, and with them the register allocation of instantiations that stand at 256
 // registers - three of them spilled, one k_small16 lost a wave of occupancy; profiles/fused_two_kernels.txt.)
 struct GnnFusedLaunch {
@@ -168,6 +169,8 @@ struct LoopForm {
     int pieces = 3;                  // piece format of the split arithmetic
     bool program = false;            // the full-tile kernel gathers from the graph's program
     bool seeded = false;             // label projection in use: plan and args are those of the shadow net over [state | aggregated state]
+    bool wide = false;               // wide-state form (gnn_loop_set_wide_state): k_fused_generic on a workgroup of `waves` < 8 waves
+    int waves = GNN_FUSED_WAVES;     // waves per workgroup of a launch per body
     int schedule = 0;                // ... working through its tiles in 1 ascending / 2 the balanced order (0: no program)
     // launch constants of the path's launches
     FusedPlan plan;

@@ -100,11 +100,27 @@ bool make_plan(const gnn_mlp *m, int nlc, FusedPlan &p)
     return true;
 }
 
-// GNN_FUSED_WAVES wave tiles [32][KP], 128 B of slack (the layer-0 pipeline reads two groups past the last tile), GNN_FUSED_WAVES x 36 row pointers
-size_t lds_bytes(const FusedPlan &p)
+// LDS of a workgroup of `waves` waves: waves wave tiles [32][KP], 128 B of slack (the layer-0 pipeline reads two groups past the last tile), waves x 36 row pointers
+size_t lds_bytes(const FusedPlan &p, int waves = GNN_FUSED_WAVES)
 {
     // ... and the last layer's bias / BatchNormalization scale / shift (3 x 32 NTL floats) and the hidden biases (2 x 32 NT)
-    return (size_t)GNN_FUSED_WAVES * 32 * std::max(p.KP, p.KPs) * sizeof(float) + 128 + GNN_FUSED_WAVES * 36 * sizeof(int) + (3 + 2) * 32 * 4 * sizeof(float) + 16;
+    return (size_t)waves * 32 * std::max(p.KP, p.KPs) * sizeof(float) + 128 + waves * 36 * sizeof(int) + (3 + 2) * 32 * 4 * sizeof(float) + 16;
+}
+
+// Wide-state form (gnn_loop_set_wide_state): k_fused_generic on a workgroup of fewer than eight waves, for a plan whose eight tiles do not
+// fit one workgroup's LDS.  State widths 68 .. 128 in multiples of 4 (load_tile_wide's rows; up to 64 the label projection is the answer,
+// and width 64 is k_fused_full's, which keeps eight waves).  Returns the waves per workgroup - the most that fit, at least 4, one per
+// SIMD - or 0: not taken (mode 0, a plan that eight waves cover, another width, no room for four tiles, or mode 1 below its row floor).
+// mode 1 ('auto') takes the form where profiles/wide_state.txt measured it faster than one kernel per op: from GNN_WIDE_AUTO_MIN_ROWS owned rows.
+constexpr int64_t GNN_WIDE_AUTO_MIN_ROWS = 1;
+int wide_waves(const FusedPlan &p, int ds, int mode, int64_t n_rows)
+{
+    if (mode == 0 || ds % 4 != 0 || ds <= 64 || ds > 128 || n_rows < 1) return 0;
+    if (lds_bytes(p) <= 160 * 1024) return 0;
+    if (mode == 1 && n_rows < GNN_WIDE_AUTO_MIN_ROWS) return 0;
+    int w = GNN_FUSED_WAVES - 1;
+    while (w >= 4 && lds_bytes(p, w) > 160 * 1024) --w;
+    return w >= 4 ? w : 0;
 }
 
 // the wave-pair form (gnn_fused_pair_kernel.h) covers the tuned shape family only: split arithmetic, state width 64, two or three layers, 128-wide
@@ -355,14 +371,18 @@ void shadow_describe(const gnn_mlp *m, int ds, gnn_mlp &s)
 
 // The shape part of the projection decision: the shadow plan, and whether the fused kernels cover it (make_plan, one workgroup's LDS, the
 // gather's column chunks - as gnn_fused_supported).  m->dims[0] must be the concat [state | nodes | agg state | agg nodes | agg arcs].
-bool projection_plan(const gnn_mlp *m, int ds, int nlc, int al, FusedPlan &sp)
+// waves: the waves per workgroup the shadow plan runs on - eight, or with a wide-state mode (wide_mode, on n_rows rows) wide_waves' count
+bool projection_plan(const gnn_mlp *m, int ds, int nlc, int al, FusedPlan &sp, int wide_mode = 0, int64_t n_rows = 0, int *waves = nullptr)
 {
     if (2 * nlc + al <= 0 || ds < 1 || m->dims.back() != ds || m->dims[0] != 2 * ds + 2 * nlc + al) return false;
     gnn_mlp s;
     shadow_describe(m, ds, s);
     if (!make_plan(&s, 0, sp)) return false;
-    if (lds_bytes(sp) > 160 * 1024) return false;
-    return (ds % 4 == 0 && ds <= 256) || ds <= 64;
+    if (!((ds % 4 == 0 && ds <= 256) || ds <= 64)) return false;
+    int w = GNN_FUSED_WAVES;
+    if (lds_bytes(sp) > 160 * 1024 && !(w = wide_waves(sp, ds, wide_mode, n_rows))) return false;
+    if (waves) *waves = w;
+    return true;
 }
 
 void projection_release(gnn_mlp *m)
@@ -455,6 +475,41 @@ extern "C" int gnn_label_projection_form(int n_layers, const int *dims, const in
     return GNN_OK;
 }
 
+// What the wide-state decision answers from shapes alone (include/gnn_hip.h): host code, no device.  The loop's part is taken at its
+// defaults, as in gnn_label_projection_form: impl 2 (the label projection is a form of it; impl 1 takes the same decision without it), no
+// feature-sliced exchange.  The same steps as gnn_loop_decide_form.
+extern "C" int gnn_wide_state_form(int n_layers, const int *dims, const int *acts, int state_dim, int n_label_cols_in_concat, int arc_label_dim,
+                                   int64_t n_rows, int mode, int label_projection_mode, int *out)
+{
+    ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && state_dim >= 1 && n_label_cols_in_concat >= 0 && arc_label_dim >= 0 && n_rows >= 0 &&
+           mode >= 0 && mode <= 2 && label_projection_mode >= 0 && label_projection_mode <= 2 && out, "bad arguments");
+    gnn_mlp m;
+    m.n_layers = n_layers;
+    m.dims.assign(dims, dims + n_layers + 1);
+    m.acts.assign(acts, acts + n_layers);
+    for (int l = 0; l <= n_layers; ++l) ARGCHK(m.dims[l] >= 1, "bad layer width");
+    for (int l = 0; l < n_layers; ++l) ARGCHK(m.acts[l] >= GNN_ACT_LINEAR && m.acts[l] <= GNN_ACT_SOFTMAX, "bad activation code");
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (mode == 0 || n_rows < 1) return GNN_OK;
+    FusedPlan p, sp;
+    const int ds = state_dim, lpm = label_projection_mode;
+    if ((int64_t)n_rows * ds * (int64_t)sizeof(float) >= ((int64_t)1 << 31)) return GNN_OK;      // 32-bit row offsets
+    const bool shape_ok = make_plan(&m, n_label_cols_in_concat, p) && m.dims.back() == ds && ((ds % 4 == 0 && ds <= 256) || ds <= 64);
+    const bool base_ok = shape_ok && lds_bytes(p) <= 160 * 1024;
+    const int base_wide = shape_ok && !base_ok ? wide_waves(p, ds, mode, n_rows) : 0;
+    int sw = 0;
+    const bool seeded = lpm && (lpm == 2 || !base_ok) && !(base_ok && small_form(&m, p, n_rows).tile != 0) &&
+                        projection_plan(&m, ds, n_label_cols_in_concat, arc_label_dim, sp, mode, n_rows, &sw) &&
+                        (sw == GNN_FUSED_WAVES || !base_wide || lpm == 2);
+    const int waves = seeded ? sw : (!base_ok && base_wide ? base_wide : GNN_FUSED_WAVES);
+    if (waves == GNN_FUSED_WAVES) return GNN_OK;
+    out[0] = 1;
+    out[1] = GNN_BODY_GENERIC + 1;                    // as gnn_loop_body_kernel: the form is k_fused_generic's
+    out[2] = waves;
+    out[3] = seeded ? 1 : 0;
+    return GNN_OK;
+}
+
 void gnn_fused_release(gnn_mlp *m)
 {
     projection_release(m);
@@ -468,19 +523,26 @@ void gnn_fused_release(gnn_mlp *m)
 
 // The feasibility part of the form decision: the plan of the loop's net_state, its weight images - packed HERE when the weights (or the
 // concat layout) changed since they were built - and the shape limits of the kernels.
-static bool gnn_fused_supported(gnn_loop *l, FusedPlan &p)
+// wide: set to the waves per workgroup of the wide-state form where everything but one workgroup's LDS admits the net and the loop's
+// mode takes the form (wide_waves), else to 0
+static bool gnn_fused_supported(gnn_loop *l, FusedPlan &p, int &wide)
 {
+    wide = 0;
     if (!make_plan(l->st, l->NLc, p)) return false;
     if (l->st->pack_dirty || l->st->pack_nlc != l->NLc) {
         if (gnn_fused_pack(l->st, l->NLc) != GNN_OK) return false;
         l->st->pack_dirty = false;
     }
     if (!l->st->packed) return false;
-    if (lds_bytes(p) > 160 * 1024) return false;                            // one 8-wave workgroup per CU
     const int Ds = l->Ds;
     if (!((Ds % 4 == 0 && Ds <= 256) || Ds <= 64)) return false;           // one column chunk per lane in the gather
     if ((int64_t)l->N_pad * Ds * (int64_t)sizeof(float) >= ((int64_t)1 << 31)) return false;   // 32-bit row offsets
-    return l->g->n_rows > 0;
+    if (l->g->n_rows <= 0) return false;
+    if (lds_bytes(p) > 160 * 1024) {                                        // one 8-wave workgroup per CU
+        wide = wide_waves(p, Ds, l->wide_state, l->g->n_rows);
+        return false;
+    }
+    return true;
 }
 
 // label block [n_rows, IW]; rows padded to whole 32-node tiles and zeroed: the full-tile kernel reads the label columns of a partial last
@@ -604,7 +666,11 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
 #endif
     // one workgroup per CU; small graphs spread their tiles over as many CUs as they have tiles (a tile alone on a CU runs
     // faster than eight sharing its L1 / LDS / SIMDs; the waves without a tile leave at once)
-    const unsigned grid = (unsigned)std::min<size_t>((size_t)n_cu, n_tiles);
+    unsigned grid = (unsigned)std::min<size_t>((size_t)n_cu, n_tiles);
+    // test entry point (gnn_loop_set_grid_limit): fewer workgroups, so that a few hundred rows reach a wave's second static tile and the
+    // ticket counter; the spread and the ticket fields below follow the capped grid
+    if (l->grid_limit > 0 && f.kernel == GNN_BODY_GENERIC) grid = std::min(grid, (unsigned)l->grid_limit);
+    const size_t waves = (size_t)f.waves;                             // per workgroup of this launch: eight, fewer in the wide-state form
     int stagger_rounds = GNN_FUSED_SPREAD_DEFAULT;
 #ifdef GNN_DIAG
     static const int stagger_env = getenv("GNN_FUSED_STAGGER") ? atoi(getenv("GNN_FUSED_STAGGER")) : GNN_FUSED_SPREAD_DEFAULT;   // tuning experiments
@@ -612,19 +678,24 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
 #endif
     // start-up spread (k_fused): the full amount when every wave has four or more tiles; the small one between one and four tiles per wave
     // (tools/bench_midsize.py, profiles/r04_midsize.txt); none when no wave has a second tile
-    a.stagger = n_tiles >= (size_t)4 * GNN_FUSED_WAVES * grid ? stagger_rounds : (n_tiles > (size_t)GNN_FUSED_WAVES * grid ? GNN_FUSED_SPREAD_SMALL_DEFAULT : 0);
+    a.stagger = n_tiles >= 4 * waves * grid ? stagger_rounds : (n_tiles > waves * grid ? GNN_FUSED_SPREAD_SMALL_DEFAULT : 0);
 #ifdef GNN_DIAG      // experiment: small grids (1 - 4 tiles per wave) with the two-cluster offset (variant bit 2): waves 4-7 start GNN_FUSED_STAGGER_SMALL x 8k cycles late
     static const int stagger_small = getenv("GNN_FUSED_STAGGER_SMALL") ? atoi(getenv("GNN_FUSED_STAGGER_SMALL")) : 0;
-    const bool small_grid = n_tiles > (size_t)GNN_FUSED_WAVES * grid && n_tiles < (size_t)4 * GNN_FUSED_WAVES * grid;
+    const bool small_grid = n_tiles > waves * grid && n_tiles < 4 * waves * grid;
     if (small_grid && stagger_small > 0) { a.stagger = stagger_small; a.variant |= 4; }
     static const int spread_small = getenv("GNN_FUSED_SPREAD_SMALL") ? atoi(getenv("GNN_FUSED_SPREAD_SMALL")) : -1;      // ... or the hashed spread 0 .. n rounds
     if (small_grid && spread_small >= 0) a.stagger = spread_small;
 #endif
     // fewer tiles than waves: a wave that drew two tickets at start would run two tiles one after the other while another wave of the
     // launch gets none (N = 31k: 488 of 2,048 waves did all the work) - the look-ahead ticket is only drawn when every wave has a tile
-    a.single_ticket = n_tiles <= (size_t)GNN_FUSED_WAVES * grid ? 1 : 0;
+    a.single_ticket = n_tiles <= waves * grid ? 1 : 0;
     f.grid = grid;
-    f.lds = lds_bytes(p);
+    f.lds = lds_bytes(p, f.waves);
+    if (f.wide) {
+        a.threads = 64 * f.waves;
+        // the wide-row loader on the full tiles, unless the aggregate is given or the loop asks for load_tile_generic (gnn_loop_set_wide_loader)
+        if (!a.agg_in && l->wide_loader == 0) a.variant |= 8;
+    }
     if (f.kernel == GNN_BODY_PAIR) {
         // wave-pair form: four pairs per workgroup, one workgroup per CU; the tile counters, gates and flags are k_fused's
         const int64_t n_tiles64 = (int64_t)n_tiles;
@@ -748,7 +819,8 @@ int gnn_loop_decide_form(gnn_loop *l)
     f = LoopForm{};
     if (l->impl_req < 1) return GNN_OK;
     HIPCHK(hipSetDevice(l->device));
-    const bool base_ok = gnn_fused_supported(l, f.plan);              // (side effect 1: the weight images)
+    int base_wide = 0;                                                // waves of the wide-state form of the net as it stands, or 0
+    const bool base_ok = gnn_fused_supported(l, f.plan, base_wide);   // (side effect 1: the weight images)
     const gnn_graph *g = l->g;
     // small graphs: the initial state, the first condition and every body inside ONE persistent launch - nets no wider than 32 (one
     // 32-feature tile per layer) or, up to 4,096 rows, with hidden layers up to 64 wide (small_form), layer-0 weights kept in registers,
@@ -760,15 +832,24 @@ int gnn_loop_decide_form(gnn_loop *l)
     // instantiation with a given aggregate), not the persistent small-graph loop and not impl 1 (exact arithmetic: they stay as they are).
     if (l->label_projection && l->impl_req == 2 && !persistent && !l->slice_mode && (l->label_projection == 2 || !base_ok) && g->n_rows > 0 &&
         (int64_t)l->N_pad * l->Ds * (int64_t)sizeof(float) < ((int64_t)1 << 31)) {
+        // Both forms on: a shadow plan that needs the wide-state form too is taken where the net as it stands has no wide-state form of
+        // its own, or where the projection is asked for wherever it applies (mode 2).
         FusedPlan sp;
-        if (projection_plan(l->st, l->Ds, l->NLc, g->AL, sp)) {
+        int sw = 0;
+        if (projection_plan(l->st, l->Ds, l->NLc, g->AL, sp, l->wide_state, g->n_rows, &sw) &&
+            (sw == GNN_FUSED_WAVES || !base_wide || l->label_projection == 2)) {
             const int rcp = projection_ensure(l->st, l->Ds, l->NLc, g->AL, sp);      // (side effect 1b: the shadow net's images, the label rows of W1)
             if (rcp) return rcp;
             f.plan = sp;
             f.seeded = true;
+            f.waves = sw;
         }
     }
-    if (!base_ok && !f.seeded) return GNN_OK;
+    // Wide-state form (gnn_loop_set_wide_state) of the net as it stands: either impl, any exchange - with the feature-sliced one the
+    // aggregate is given and the tile load is load_tile_generic's
+    if (!base_ok && !f.seeded && base_wide) f.waves = base_wide;
+    f.wide = f.waves != GNN_FUSED_WAVES;
+    if (!base_ok && !f.seeded && !f.wide) return GNN_OK;
     if (l->device < 0 || l->device >= 64) return gnn_fail(GNN_ERR_ARG, "device %d out of range", l->device);
     const FusedPlan &p = f.plan;
     const int n_cu = device_cus(l->device);
@@ -787,7 +868,7 @@ int gnn_loop_decide_form(gnn_loop *l)
     if (f.program) {
         // tile schedule (gnn_loop_set_tile_schedule): the balanced order where it is asked for, or where the choice is the library's and
         // every wave of a launch on this device has four tiles or more; its slot headers are built here, on first demand
-        const int64_t waves = (int64_t)GNN_FUSED_WAVES * n_cu;
+        const int64_t waves = (int64_t)f.waves * n_cu;                 // (the program kernel is k_fused_full: eight)
         const int want = l->tile_schedule ? l->tile_schedule : (n_tiles >= 4 * waves ? GNN_TILE_SCHEDULE_DEFAULT : 1);
         f.schedule = want == 2 && gnn_tile_schedule_ensure(g, 1, waves) ? 2 : 1;
     }

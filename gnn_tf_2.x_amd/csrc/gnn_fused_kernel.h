@@ -1079,6 +1079,124 @@ __device__ __forceinline__ void load_tile_fast64(const GnnFusedArgs &a, float *X
     own.write(a, X, i0, lane, KP, c_aggs);                                   // own state and label columns into the tile
 }
 
+// ---- wide rows: Ds % 4 == 0, 64 < Ds <= 128, full tile, CSR walk (the wide-state form of k_fused_generic, gnn_loop_set_wide_state) ----
+// one batch: entry J of the group's batch (held by lane J of BOTH 16-lane DPP rows of the 32-lane group) is broadcast to its row, and
+// the 32 lanes request the neighbour's state row, 16 B each.  rowb: bytes of a state row for the lanes that hold a piece of it, 0 for the
+// lanes behind column Ds, whose voff0 is GNN_GP_NOROW - past the descriptor's range, the load returns zeros.  Source ids are below 2^23
+// (a replica under 2 GiB of rows over 256 B), so the 24-bit multiply is exact.
+template <int GB, int... J>
+__device__ __forceinline__ void gather_batch_wide(int my_src, float my_w, __amdgpu_buffer_rsrc_t rsrc, unsigned rowb, int voff0, float (&w)[GB],
+                                                  v4f (&x)[GB], std::integer_sequence<int, J...>)
+{
+    ((w[J] = row_bcast_f<J>(my_w),
+      x[J] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)__umul24((unsigned)row_bcast_i<J>(my_src), rowb) + voff0, 0, 0))), ...);
+}
+
+// Lane group g (32 lanes, 16 B per lane = one state row of up to 512 B per group and instruction) owns the 16 consecutive nodes
+// 16g .. 16g+15 and walks their contiguous CSR entries in batches of 16, as load_tile_fast64 does with four groups of 16 lanes: ids and
+// weights of a batch fetched coalesced - by both DPP rows of the group, so that row_bcast serves unchanged - and those of the next batch
+// prefetched, all 16 neighbour rows requested before the first is consumed (64 VGPRs in flight per lane), the v_fma_f32 chain per element
+// in stored order from +0, flushed to LDS at every row boundary (an empty row writes +0): the C oracle's chain, bit for bit.
+// The tile's rows are not 16-byte aligned (KP is odd): four ds_write_b32 per row piece.
+// Own state rows: 32 Ds / 4 <= 1,024 pieces of 16 B, up to 16 per lane, requested first of all and written to LDS behind the request for
+// the first batch's ids and weights: vector-memory results return in issue order, so the rows are there before the ids are - the wait
+// is the one the gather starts with anyway - and their 64 registers are free again when the gather's 64 are needed.  Label columns
+// (few, and none in the seeded form) and the zero padding: load_tile_generic's way, in front.
+// A partial tile and a given aggregate keep load_tile_generic (k_fused_generic).
+__device__ __forceinline__ void load_tile_wide(const GnnFusedArgs &a, float *X, const int *ipt, int64_t i0, int lane, int KP, int c_aggs)
+{
+    constexpr int GB = 16;
+    // (a fresh, compiler-opaque lane id per tile, as fused_opaque_pointers: everything below that depends on the lane and the shapes alone -
+    // the row / column of 16 own pieces, the group's offsets - is otherwise computed once per kernel and held across the dense layers)
+    // - and likewise the shapes: the kernels stand at 106 scalar registers, and a hoisted scalar is a spill into a vector register
+    int Ds = a.Ds;
+    asm volatile("" : "+v"(lane));
+    asm volatile("" : "+s"(Ds), "+s"(KP), "+s"(c_aggs));
+    const int gl = lane & 31, grp = lane >> 5;
+    zero_pad_columns(a, X, lane, KP);
+    // own state rows, contiguous in HBM: piece t = lane + 64 u of the tile's 8 Ds pieces is columns 4 (t mod Ds / 4) .. of row t / (Ds / 4)
+    const int qw = Ds >> 2, n_own = 8 * Ds;
+    v4f own[16];
+    {
+        const float *src = a.state_cur + (a.row_begin + i0) * Ds + lane * 4;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) own[u] = (lane + 64 * u < n_own) ? gload4(src + u * 256) : v4f{0.f, 0.f, 0.f, 0.f};
+    }
+    if (a.IW > 0) {
+        const float *src = a.inv + i0 * a.IW;
+        const int total = 32 * a.IW;
+        RowCol rc(lane, a.IW);
+        for (int t = lane; t < total; t += 64, rc.next()) X[rc.i * KP + label_col(rc.c, Ds, a.NLc, c_aggs)] = gload1(src + t);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                   // ipt visible to the whole wave
+
+    int node = grp * 16;
+    const int node_end = node + 16;
+    const int e_begin = ipt[node], e_end = ipt[node_end];
+    int next_end = ipt[node + 1];
+    int my_src = 0;
+    float my_w = 0.0f;
+    if (e_begin + (lane & 15) < e_end) { my_src = gstream1(a.adj_src + e_begin + (lane & 15)); my_w = gstream1(a.adj_w + e_begin + (lane & 15)); }
+    {   // own state into columns [0, Ds)
+        RowCol rc(lane, qw);
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            if (lane + 64 * u < n_own) {
+                float *x = X + rc.i * KP + rc.c * 4;
+                x[0] = own[u].x; x[1] = own[u].y; x[2] = own[u].z; x[3] = own[u].w;
+            }
+            rc.next();
+        }
+    }
+    v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
+    const bool colok = gl * 4 < Ds;
+    const unsigned rowb = colok ? (unsigned)Ds * 4u : 0u;
+    const int voff0 = colok ? gl * 16 : (int)GNN_GP_NOROW;
+    float *xo = X + c_aggs + gl * 4;
+#define GNN_ROW_BOUNDARY(e)                                                                     \
+    while ((e) >= next_end) {                                                                   \
+        if (colok) { float *xr = xo + node * KP; xr[0] = acc01.x; xr[1] = acc01.y; xr[2] = acc23.x; xr[3] = acc23.y; }   \
+        acc01 = v2f{0.f, 0.f}; acc23 = v2f{0.f, 0.f};                                           \
+        ++node;                                                                                 \
+        next_end = ipt[node + 1];                                                               \
+    }
+    int base = e_begin;
+    for (; base + GB <= e_end; base += GB) {                                 // full batches: no guards
+        float w[GB];
+        v4f x[GB];
+        gather_batch_wide<GB>(my_src, my_w, rsrc, rowb, voff0, w, x, std::make_integer_sequence<int, GB>{});
+        const int nb = base + GB + (lane & 15);                              // ids / weights of the next batch
+        my_src = 0; my_w = 0.0f;
+        if (nb < e_end) { my_src = gstream1(a.adj_src + nb); my_w = gstream1(a.adj_w + nb); }
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+            GNN_ROW_BOUNDARY(base + u)
+            gather_fma(acc01, acc23, w[u], x[u]);
+        }
+    }
+    {                                                                        // tail batch: cnt in [0, GB)
+        const int cnt = e_end - base;
+        float w[GB];
+        v4f x[GB];
+        // all GB slots are requested (slots >= cnt re-read whatever id the lane holds: an entry of this batch or 0 = row 0, always a
+        // valid row) and only the first cnt are consumed
+        gather_batch_wide<GB>(my_src, my_w, rsrc, rowb, voff0, w, x, std::make_integer_sequence<int, GB>{});
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+            if (u < cnt) {
+                GNN_ROW_BOUNDARY(base + u)
+                gather_fma(acc01, acc23, w[u], x[u]);
+            }
+        }
+    }
+#undef GNN_ROW_BOUNDARY
+    for (; node < node_end; ++node) {                                        // last row with entries, then empty rows
+        if (colok) { float *xr = xo + node * KP; xr[0] = acc01.x; xr[1] = acc01.y; xr[2] = acc23.x; xr[3] = acc23.y; }
+        acc01 = v2f{0.f, 0.f}; acc23 = v2f{0.f, 0.f};
+    }
+}
+
 // ---- the same tile from the graph's gather program (gather form 2; gnn_gather_program_build) ----
 // The CSR structure never changes after the graph is created, so it is walked once, on the host: per tile and lane group the program holds
 // the (source word, weight) entries in the order the group consumes them, all four streams padded to the same number of 16-entry batches.
@@ -1539,13 +1657,13 @@ __device__ __forceinline__ void fused_stage_vectors(const GnnFusedArgs &a, float
 // Start-up spread.  All waves of the chip run the same phases on tiles of similar cost: started together they gather together
 // (HBM saturated, 3-4 us per round trip) and compute together (HBM idle).  Every wave therefore waits a different fraction of
 // one tile period before its first tile; the dynamic tickets keep the load balanced.  variant bit 2: the old two-cluster
-// stagger (waves 4-7 delayed by a fixed amount).
-__device__ __forceinline__ void fused_startup_spread(const GnnFusedArgs &a, int wave)
+// stagger (waves 4-7 delayed by a fixed amount).  waves: waves per workgroup of the launch (k_fused_generic passes its own).
+__device__ __forceinline__ void fused_startup_spread(const GnnFusedArgs &a, int wave, int waves = GNN_FUSED_WAVES)
 {
     if (a.stagger > 0) {
         int rounds = 0;
-        if (a.variant & 4) rounds = wave >= GNN_FUSED_WAVES / 2 ? a.stagger : 0;
-        else rounds = (int)((((unsigned)blockIdx.x * GNN_FUSED_WAVES + (unsigned)wave) * 0x9E3779B1u) >> 16) % (unsigned)(a.stagger + 1);
+        if (a.variant & 4) rounds = wave >= waves / 2 ? a.stagger : 0;
+        else rounds = (int)((((unsigned)blockIdx.x * (unsigned)waves + (unsigned)wave) * 0x9E3779B1u) >> 16) % (unsigned)(a.stagger + 1);
         for (int i = 0; i < rounds; ++i) __builtin_amdgcn_s_sleep(127);
     }
 }
@@ -1686,6 +1804,8 @@ __device__ __forceinline__ int fused_next_tile(const GnnFusedArgs &a0, int next2
 // device-wide counter until none is left; the waves never synchronise with each other after the staging.  The tile load is
 // load_tile_generic (any width, partial tiles, a given aggregate a.agg_in), the epilogue writes the new state to the tile and
 // check_store_generic tests and stores it.
+// Wide-state form (gnn_loop_set_wide_state): the same kernel on a workgroup of 4 to 7 waves, as many as a wider tile leaves room for
+// in LDS - every LDS offset and the ticket arithmetic follow blockDim - with load_tile_wide on the full tiles.
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
 // SEED: the seeded form of the label projection (GNN_FUSED_DENSE_LAYERS; the arguments describe the net over [state | aggregated state]).
@@ -1701,15 +1821,16 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const Gn
     const int KP = a.KP, Ds = a.Ds;
     float *X = lds + (size_t)wave * 32 * KP;
     const int c_aggs = a.c_aggs;                      // column of the aggregated state block (Ds + NLc + alignment hole)
-    const int W_launch = (int)gridDim.x * (int)(blockDim.x >> 6);            // (tiles and tickets: fused_draw_ticket)
+    const int waves = (int)(blockDim.x >> 6);         // waves of THIS launch's workgroup: 8, or 4 .. 7 in the wide-state form (gnn_loop_set_wide_state)
+    const int W_launch = (int)gridDim.x * waves;      // (tiles and tickets: fused_draw_ticket)
     const int w_launch = wave * (int)gridDim.x + (int)blockIdx.x;
     const bool third_round = (int64_t)2 * W_launch * 32 < a.n_rows;
     int tile = w_launch + a.tile_base, next_tile = w_launch + W_launch + a.tile_base;
     const int ip_first_raw = tile_rowptr_request(a, tile, lane);      // on its way while the workgroup stages its vectors below
-    float *ep = lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32 + GNN_FUSED_WAVES * 36;
+    float *ep = lds + (size_t)waves * 32 * KP + 32 + waves * 36;
     float *hb = ep + 3 * 32 * NTL;
     fused_stage_vectors<LAYERS, NT, NTL, ACT, SPLIT>(a, ep, hb);
-    fused_startup_spread(a, wave);
+    fused_startup_spread(a, wave, waves);
     int ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
   for (;;) {
     const int64_t i0 = (int64_t)tile * 32;
@@ -1725,13 +1846,18 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const Gn
 
     // the tile's 33 row pointers go through LDS: the gather re-reads them inside divergent code, where a cross-lane
     // broadcast from lanes of another group would not be safe
-    int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
+    int *ipt = reinterpret_cast<int *>(lds + (size_t)waves * 32 * KP + 32) + wave * 36;
     if (lane <= 32) ipt[lane] = ip_cur;               // requested during the previous tile
     const int ip_next_raw = tile_rowptr_request(a, next_tile, lane);      // row pointers of the NEXT tile: on their way during the gather
     // the gather is a chain of few instructions and long memory waits: with a raised priority its loads are issued ahead of the
     // SIMD partner's dense VALU / MFMA stream instead of behind it
     if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
-    load_tile_generic(a, X, ipt, i0, lane, nvalid, KP, c_aggs);
+    // NTL == 4 is a state wider than 64: only those instantiations hold the wide-row loader, and only a launch of the wide-state form
+    // (variant bit 3, wave-uniform; Ds % 4 == 0, no given aggregate) takes it - for its full tiles
+    if constexpr (NTL == 4) {
+        if ((a.variant & 8) && nvalid == 32) load_tile_wide(a, X, ipt, i0, lane, KP, c_aggs);
+        else load_tile_generic(a, X, ipt, i0, lane, nvalid, KP, c_aggs);
+    } else load_tile_generic(a, X, ipt, i0, lane, nvalid, KP, c_aggs);
     if (a.variant & 1) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     GNN_STAMP(2);
@@ -1946,7 +2072,7 @@ inline void launch_kernel(const GnnFusedArgs &a, unsigned grid, size_t lds_bytes
 {
     static bool lds_raised[64] = {false};   // (one table per instantiation)
     (void)gnn_raise_dynamic_lds(reinterpret_cast<const void *>(KERNEL), 160 * 1024, lds_raised);
-    hipLaunchKernelGGL(KERNEL, grid, GNN_FUSED_THREADS, lds_bytes, st, a);
+    hipLaunchKernelGGL(KERNEL, grid, a.threads ? a.threads : GNN_FUSED_THREADS, lds_bytes, st, a);      // (a.threads: the wide-state form of k_fused_generic)
 }
 
 // k_fused_generic in the piece format of the launch (the exact path has one)

@@ -382,6 +382,47 @@ extern "C" int gnn_loop_set_label_projection(gnn_loop *l, int mode, int *used)
     return rc;
 }
 
+// Wide-state form (include/gnn_hip.h): one launch per body for a net_state whose tile of eight waves does not fit one workgroup's LDS -
+// k_fused_generic on 4 to 7 waves (gnn_fused.hip, wide_waves)
+extern "C" int gnn_loop_set_wide_state(gnn_loop *l, int mode, int *used)
+{
+    ARGCHK(l && mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (where it is faster than one kernel per op) or 2 (wherever covered)");
+    l->wide_state = mode;
+    const int rc = gnn_loop_decide_form(l);
+    if (used) *used = l->form.path == GNN_PATH_BODIES && l->form.wide ? 1 : 0;
+    return rc;
+}
+
+// test entry point: the tile loader of the wide-state form's full tiles - 0 load_tile_wide (the default), 1 load_tile_generic
+extern "C" int gnn_loop_set_wide_loader(gnn_loop *l, int loader, int *used)
+{
+    ARGCHK(l && (loader == 0 || loader == 1), "loader must be 0 (load_tile_wide) or 1 (load_tile_generic)");
+    l->wide_loader = loader;
+    const int rc = gnn_loop_decide_form(l);
+    if (used) *used = l->form.path == GNN_PATH_BODIES && l->form.wide && (l->form.args.variant & 8) ? 1 : 0;      // load_tile_wide in use
+    return rc;
+}
+
+// test entry point: {waves per workgroup, grid} of the launch per body of the last form decision - a setter's or a run's ({0, 0}: no such launch)
+extern "C" int gnn_loop_body_launch(const gnn_loop *l, int *out)
+{
+    ARGCHK(l && out, "bad arguments");
+    const bool bodies = l->form.path == GNN_PATH_BODIES;
+    out[0] = bodies ? l->form.waves : 0;
+    out[1] = bodies ? (int)l->form.grid : 0;
+    return GNN_OK;
+}
+
+// test entry point: at most max_workgroups workgroups per k_fused_generic launch (0: the library's choice)
+extern "C" int gnn_loop_set_grid_limit(gnn_loop *l, int max_workgroups, int *used)
+{
+    ARGCHK(l && max_workgroups >= 0, "max_workgroups must be >= 0");
+    l->grid_limit = max_workgroups;
+    const int rc = gnn_loop_decide_form(l);
+    if (used) *used = l->form.path == GNN_PATH_BODIES ? (int)l->form.grid : 0;
+    return rc;
+}
+
 // test hook: the projection the last run used, P [n_rows, H1] row-major (H1: width of net_state's first layer)
 extern "C" int gnn_loop_get_label_projection(gnn_loop *l, float *out)
 {

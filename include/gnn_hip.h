@@ -450,6 +450,37 @@ int gnn_loop_get_label_projection(gnn_loop *l, float *out);
  * columns IW; out[3] = 32-feature tiles of P per 32-row tile. */
 int gnn_label_projection_form(int n_layers, const int *dims, const int *acts, int state_dim, int n_label_cols_in_concat, int arc_label_dim,
                               int64_t n_rows, int mode, int *out);
+/* Wide-state form: one launch per body for state widths 68 .. 128.  The fused kernels hold the concat of 32 nodes per wave in LDS, eight
+ * waves per workgroup; [state | agg state] alone is past that for a state wider than 72.  With this form k_fused_generic runs on a
+ * workgroup of 4 to 7 waves - as many 32-node tiles as fit 160 KiB of LDS, at least one wave per SIMD - and loads the full tiles with a
+ * loader for rows of 68 to 128 floats (load_tile_wide: one row per 32-lane group and instruction, 16 rows in flight per lane).
+ *   mode 0  off (default): the Loop runs exactly as without this call, bit for bit;
+ *   mode 1  where profiles/wide_state.txt measured the form faster than one kernel per op;
+ *   mode 2  wherever it is covered and the eight-wave path is not.
+ * Covered: a state width that is a multiple of 4 in 68 .. 128 and a net_state the fused path refuses ONLY for its LDS (layers up to 128
+ * wide, no softmax, one activation for all hidden layers) whose tile fits at four waves - a 128-wide state with about a dozen label
+ * columns; with the label projection on (gnn_loop_set_label_projection), the net over [state | agg state] likewise, whatever the labels'
+ * width.  impl 1 and impl 2, both piece formats, the certified-gate and range-guard repeats, row-exchange shards; with the feature-sliced
+ * exchange the same launch with the given aggregate (load_tile_generic).  The arithmetic per node is the eight-wave kernel's: impl 1 is
+ * bit-identical to the C oracle.  The persistent small-graph loop and training-mode runs never take it.
+ * *used (may be NULL) = 1 when the next run takes the form, else 0. */
+int gnn_loop_set_wide_state(gnn_loop *l, int mode, int *used);
+/* What gnn_loop_set_wide_state(mode) answers from shapes alone, with the label projection in label_projection_mode - host code, no device;
+ * arguments and the loop's part as gnn_label_projection_form.  out receives 4 ints: out[0] = 1 taken / 0 not (then the rest is 0);
+ * out[1] = per-body kernel as gnn_loop_body_kernel (always 1, k_fused_generic); out[2] = waves per workgroup (4 .. 7); out[3] = 1 when the
+ * launch is the seeded one of the label projection. */
+int gnn_wide_state_form(int n_layers, const int *dims, const int *acts, int state_dim, int n_label_cols_in_concat, int arc_label_dim,
+                        int64_t n_rows, int mode, int label_projection_mode, int *out);
+/* Test entry points of the launch per body, not part of the supported interface.
+ * out[0] = waves per workgroup, out[1] = workgroups of the launch per body of the loop's last form decision - a setter's or a run's
+ * (0, 0: the loop takes no such launch). */
+int gnn_loop_body_launch(const gnn_loop *l, int *out);
+/* At most max_workgroups workgroups per k_fused_generic launch (0, the default: the library's choice), so that a few hundred rows reach a
+ * wave's second static tile and the ticket counter.  Results do not depend on it.  *used (may be NULL) = the grid of the next run's launch. */
+int gnn_loop_set_grid_limit(gnn_loop *l, int max_workgroups, int *used);
+/* The tile loader of the wide-state form's full tiles: 0 load_tile_wide (default), 1 load_tile_generic - same bits, for A/B runs.
+ * *used (may be NULL) = 1 when the next run's launches use load_tile_wide. */
+int gnn_loop_set_wide_loader(gnn_loop *l, int loader, int *used);
 /* ---- Test and diagnostic entry points of gather form 2: not part of the supported interface, they may change with the program's layout. ----
  * The gather program of rows [0, n_rows) of a CSR graph (host code; tests/test_gather_program.py).  Per full 32-row tile t: hdr[2 t] = first
  * 64-entry batch, hdr[2 t + 1] = batches; ent[(64 b + 16 g + j) 2 + {0, 1}] = {source word, weight bits} of entry j of lane group g in
