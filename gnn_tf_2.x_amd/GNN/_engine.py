@@ -25,7 +25,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
-           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
+           'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_gather_program_compact', 'gnn_graph_gather_program_format', 'gnn_graph_set_program_entries', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
            'gnn_comm_create_loopback', 'gnn_graph_set_full_adjacency', 'gnn_loop_set_slice_exchange', 'gnn_loop_run_group', 'gnn_loop_readout_group', 'gnn_graph_update_labels_group']
 
@@ -270,6 +270,16 @@ def gather_program(indptr, adj_src, adj_w):
     return hdr, ent.view(np.uint32)
 
 
+def gather_program_compact(hdr, ent):
+    """gnn_gather_program_compact (host code): (words [batches, 64] uint32, roww [tiles, 32] float32) of a program built by gather_program -
+    its source words and one weight per tile-local row; NotImplementedError when a row's entries differ in their weights' bits."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.int32)
+    ent = np.ascontiguousarray(ent).view(np.int32)
+    words, roww = np.zeros(ent.shape[:2], np.int32), np.zeros((hdr.shape[0], 32), np.float32)
+    _check(lib().gnn_gather_program_compact(C.c_int64(hdr.shape[0]), _ip(hdr), C.c_int64(ent.shape[0]), _ip(ent), _ip(words), _fp(roww)))
+    return words.view(np.uint32), roww
+
+
 def tile_schedule(cost, waves: int, kind: int):
     """gnn_tile_schedule_build (host code): order [slots] int32, order[slot] = the tile that ticket `slot` of a launch of `waves` waves
     stands for; cost[t] = real entries (arcs) of tile t; kind 0 the identity, 1 the balanced order."""
@@ -415,6 +425,19 @@ class Graph:
         t, b, n, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
         _check(lib().gnn_graph_gather_program_info(self._h, C.byref(t), C.byref(b), C.byref(n), C.byref(ms)))
         return dict(tiles=t.value, batches=b.value, bytes=n.value, build_ms=ms.value)
+
+    def gather_program_format(self) -> int:
+        """gnn_graph_gather_program_format: entry format of the program on the device - 0 none (yet), 8, or 4 (source words + one weight per row)."""
+        n = C.c_int(0)
+        _check(lib().gnn_graph_gather_program_format(self._h, C.byref(n)))
+        return n.value
+
+    def set_program_entries(self, entries: int) -> int:
+        """gnn_graph_set_program_entries (A/B runs, tests): 0 the library's choice, 8 or 4; drops the program and its schedules and returns
+        the format held from now on (8 where 4 is not available, 0 without a program)."""
+        used = C.c_int(0)
+        _check(lib().gnn_graph_set_program_entries(self._h, C.c_int(int(entries)), C.byref(used)))
+        return used.value
 
     def tile_schedule_info(self) -> dict:
         """gnn_graph_tile_schedule_info: slots of the program kernel's tile schedule, the kind built so far (0 none, 1 ascending only, 2 the

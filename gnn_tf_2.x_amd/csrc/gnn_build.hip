@@ -285,6 +285,46 @@ extern "C" int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Compact format of the program (entry format 4; gnn_fused_kernel.h: prog_weight).  Host code.
+//
+// The weights of one destination row are equal in every graph the reference builds ('sum' 1, 'average' 1 / in-degree, 'normalized'
+// 1 / arcs), so half of an 8-byte entry repeats a value that one float per row carries: words[b][l] = the source word of entry l of batch
+// b, unchanged; roww[t][r] = the bit pattern all entries of tile-local row r of tile t share, +0 for an empty row (its single entry had
+// weight +0).  Padding needs no weight: it sits behind its group's last row end, and what it accumulates is never written.
+// false: some row holds two entries whose weights differ as bit patterns (+0 beside -0 included) - nothing of such a graph is compacted.
+// ---------------------------------------------------------------------------------------------------------------------
+static bool gather_program_compact(int64_t tiles, const int32_t *hdr, const int32_t *ent, int32_t *words, float *roww)
+{
+    for (int64_t t = 0; t < tiles; ++t) {
+        uint32_t bits[32] = {0};
+        bool seen[32] = {false};
+        const int64_t first = hdr[2 * t], nb = hdr[2 * t + 1];
+        for (int64_t s = first * 64; s < (first + nb) * 64; ++s) {
+            uint32_t word, wb;
+            memcpy(&word, ent + 2 * s, 4);
+            memcpy(&wb, ent + 2 * s + 1, 4);
+            words[s] = ent[2 * s];
+            if ((word & GNN_GP_NOROW) == GNN_GP_NOROW) continue;      // no source: padding, or an empty row's entry (weight +0)
+            const int r = (int)(word & GNN_GP_ROW_MASK);
+            if (seen[r] && bits[r] != wb) return false;
+            seen[r] = true; bits[r] = wb;
+        }
+        memcpy(roww + 32 * t, bits, sizeof(bits));
+    }
+    return true;
+}
+
+extern "C" int gnn_gather_program_compact(int64_t tiles, const int32_t *hdr, int64_t n_batches, const int32_t *ent, int32_t *words, float *roww)
+{
+    ARGCHK(tiles >= 0 && n_batches >= 0 && (tiles == 0 || (hdr && roww)) && (n_batches == 0 || (ent && words)), "hdr / ent / words / roww are required");
+    for (int64_t t = 0; t < tiles; ++t)
+        ARGCHK(hdr[2 * t] >= 0 && hdr[2 * t + 1] >= 0 && (int64_t)hdr[2 * t] + hdr[2 * t + 1] <= n_batches, "header of tile %lld outside the program", (long long)t);
+    if (!gather_program_compact(tiles, hdr, ent, words, roww))
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "not compactable: a row holds entries of different weights");
+    return GNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Tile schedule of the program kernel: the order in which a launch works through its tiles.  Host code.
 //
 // order[slot] = the tile that ticket `slot` stands for.  Kind 0: the identity.  Kind 1, the balanced order, from the tiles sorted by cost
@@ -336,11 +376,14 @@ bool gnn_tile_schedule_ensure(const gnn_graph *g, int kind, int64_t waves)
     int32_t *d_slot = nullptr;
     bool ok = false;
     try {
-        std::vector<int32_t> order((size_t)slots), slot((size_t)slots * 4);
+        // entry format 4: the row weights of every slot's tile behind the headers, in slot order - a launch finds them from its ticket alone
+        const bool roww = sh->gp_entries == 4;
+        std::vector<int32_t> order((size_t)slots), slot((size_t)slots * (roww ? 36 : 4));
         ok = gnn_tile_schedule_build(slots, sh->gp_cost.data(), waves, kind, order.data()) == GNN_OK;
         for (int64_t s = 0; ok && s < slots; ++s) {
             const int32_t t = order[s];
             slot[4 * s] = sh->gp_hdr_host[2 * (size_t)t]; slot[4 * s + 1] = sh->gp_hdr_host[2 * (size_t)t + 1]; slot[4 * s + 2] = t; slot[4 * s + 3] = 0;
+            if (roww) memcpy(&slot[4 * (size_t)slots + 32 * (size_t)s], &sh->gp_roww_host[32 * (size_t)t], 32 * sizeof(float));
         }
         ok = ok && gnn_dev_malloc((void **)&d_slot, sizeof(int32_t) * std::max<size_t>(4, slot.size())) == hipSuccess &&
              hipMemcpy(d_slot, slot.data(), sizeof(int32_t) * slot.size(), hipMemcpyHostToDevice) == hipSuccess;
@@ -381,6 +424,8 @@ extern "C" int gnn_graph_tile_schedule_info(const gnn_graph *g, int64_t *slots, 
 // rows, one GNN_GP_NOROW | GNN_GP_ROW_END slot each, an exact +0 aggregate as the CSR walk gives them.  Its batches follow the full tiles'
 // in gp_ent; its header stays on the host (gp_last_first, gp_last_nb), so that gp_hdr / gp_tiles keep describing the full tiles only, and
 // reaches the kernel as the last slot of the ascending tile schedule (gnn_tile_schedule_ensure), an ordinary slot of the balanced one.
+// The device holds ONE entry format per graph (gp_entries): the 8-byte program is built on the host, compacted where every row's weights
+// are one bit pattern (gather_program_compact; the partial last tile's program too), and only the format taken is copied to the device.
 int gnn_gather_program_ensure(const gnn_graph *g)
 {
     gnn_graph_shared *sh = g->sh;
@@ -397,6 +442,8 @@ int gnn_gather_program_ensure(const gnn_graph *g)
     int32_t last_hdr[2] = {0, 0};
     std::vector<int32_t> hdr_host;
     std::vector<int64_t> cost;
+    std::vector<float> roww_host;
+    int entries = 8;
     bool ok = false;
     try {
         std::vector<int32_t> indptr((size_t)g->n_rows + 1), hdr((size_t)tiles * 2), src, ent;
@@ -418,6 +465,19 @@ int gnn_gather_program_ensure(const gnn_graph *g)
             ok = gnn_gather_program_build(tiles * 32, indptr.data(), src.data(), w.data(), nullptr, ent.data(), &batches) == GNN_OK;
             if (ok && rem) ok = gnn_gather_program_build(32, last_ip, src.data(), w.data(), nullptr, ent.data() + (size_t)batches * 128, &last_batches) == GNN_OK;
         }
+        // the compact format where every row's weights are one bit pattern (and gnn_graph_set_program_entries did not ask for 8): the
+        // device then holds the source words alone, the partial last tile's behind the full tiles' as before.  (A graph without arcs has no
+        // weight to share - its program is empty rows' entries and padding - and keeps the 8-byte format unless 4 is asked for.)
+        if (ok && sh->gp_entries_req != 8 && (E > 0 || sh->gp_entries_req == 4)) {
+            std::vector<int32_t> words(ent.size() / 2);
+            roww_host.assign((size_t)(tiles + (rem ? 1 : 0)) * 32, 0.0f);
+            const int32_t last_rel[2] = {0, (int32_t)last_batches};
+            if (gather_program_compact(tiles, hdr.data(), ent.data(), words.data(), roww_host.data()) &&
+                (!rem || gather_program_compact(1, last_rel, ent.data() + (size_t)batches * 128, words.data() + (size_t)batches * 64, roww_host.data() + (size_t)tiles * 32))) {
+                ent.swap(words);
+                entries = 4;
+            } else roww_host.clear();
+        }
         ok = ok && gnn_dev_malloc((void **)&d_hdr, sizeof(int32_t) * hdr.size()) == hipSuccess &&
              gnn_dev_malloc((void **)&d_ent, sizeof(int32_t) * ent.size()) == hipSuccess &&
              hipMemcpy(d_hdr, hdr.data(), sizeof(int32_t) * hdr.size(), hipMemcpyHostToDevice) == hipSuccess &&
@@ -433,10 +493,11 @@ int gnn_gather_program_ensure(const gnn_graph *g)
         sh->gp_hdr = d_hdr; sh->gp_ent = d_ent; sh->gp_tiles = tiles; sh->gp_batches = batches + last_batches;
         sh->gp_rows = g->n_rows; sh->gp_last_first = (int32_t)batches; sh->gp_last_nb = (int32_t)last_batches;
         sh->gp_hdr_host.swap(hdr_host); sh->gp_cost.swap(cost);
+        sh->gp_entries = entries; sh->gp_roww_host.swap(roww_host);
         // the kernel finds every tile through a slot header: a program without the ascending schedule's array is no program
         if (!gnn_tile_schedule_ensure(g, 0, 1)) {
             (void)hipFree(d_hdr); (void)hipFree(d_ent);
-            sh->gp_hdr = sh->gp_ent = nullptr; sh->gp_tiles = sh->gp_batches = 0;
+            sh->gp_hdr = sh->gp_ent = nullptr; sh->gp_tiles = sh->gp_batches = 0; sh->gp_entries = 0;
             (void)hipGetLastError();
         }
         sh->gp_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -455,7 +516,43 @@ extern "C" int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles,
     const bool have = sh->gp_ent != nullptr;
     if (tiles) *tiles = have ? sh->gp_tiles : 0;
     if (batches) *batches = have ? sh->gp_batches : 0;
-    if (bytes) *bytes = have ? sh->gp_tiles * 8 + sh->gp_batches * 512 : 0;
+    // (entry format 4: 256 bytes per batch, and the row-weight block of one tile schedule, 128 bytes per slot)
+    if (bytes) *bytes = !have ? 0 : sh->gp_entries == 4 ? sh->gp_tiles * 8 + sh->gp_batches * 256 + (int64_t)sh->gp_cost.size() * 128
+                                                        : sh->gp_tiles * 8 + sh->gp_batches * 512;
     if (build_ms) *build_ms = have ? sh->gp_build_ms : 0.0f;
+    return GNN_OK;
+}
+
+extern "C" int gnn_graph_gather_program_format(const gnn_graph *g, int *entries)
+{
+    ARGCHK(g && entries, "graph / entries are NULL");
+    *entries = g->sh->gp_ent ? g->sh->gp_entries : 0;
+    return GNN_OK;
+}
+
+// Drops the graph's program and its tile schedules (the next form decision of a Loop rebuilds them) and records the entry format to
+// build.  Where the graph had a program, or a format is asked for, the program is rebuilt at once, so that *used is the format the graph
+// holds from now on.  The caller's Loops on this graph (and on the graphs derived from it) are idle: hipFree waits for the device.
+extern "C" int gnn_graph_set_program_entries(gnn_graph *g, int entries, int *used)
+{
+    ARGCHK(g, "graph is NULL");
+    ARGCHK(entries == 0 || entries == 4 || entries == 8, "entries must be 0 (the library's choice), 4 or 8");
+    gnn_graph_shared *sh = g->sh;
+    const bool had = sh->gp_ent != nullptr;
+    int dev_before = -1;
+    HIPCHK(hipGetDevice(&dev_before));
+    HIPCHK(hipSetDevice(g->device));
+    (void)hipFree(sh->gp_hdr); (void)hipFree(sh->gp_ent); (void)hipFree(sh->gp_slot[0]); (void)hipFree(sh->gp_slot[1]);
+    (void)hipSetDevice(dev_before);
+    sh->gp_hdr = sh->gp_ent = sh->gp_slot[0] = sh->gp_slot[1] = nullptr;
+    sh->gp_tiles = sh->gp_batches = sh->gp_rows = 0;
+    sh->gp_last_first = sh->gp_last_nb = 0;
+    sh->gp_hdr_host.clear(); sh->gp_cost.clear(); sh->gp_roww_host.clear();
+    sh->gp_sched_waves = sh->gp_sched_tail = 0;
+    sh->gp_tried = sh->gp_sched_tried = false;
+    sh->gp_entries = 0;
+    sh->gp_entries_req = entries;
+    if (had || entries) gnn_gather_program_ensure(g);
+    if (used) *used = sh->gp_ent ? sh->gp_entries : 0;
     return GNN_OK;
 }

@@ -209,8 +209,16 @@ struct gnn_graph_shared {
     int32_t gp_last_first = 0, gp_last_nb = 0;      // header of the partial last tile's program (no entry of gp_hdr), or gp_last_nb == 0
     bool gp_tried = false;
     float gp_build_ms = 0.0f;               // host time of the build, copies included
+    // Entry format of the program on the device, one per graph (gnn_gather_program_compact): 8 = gp_ent [batches][64][2] {source word,
+    // weight}; 4 = gp_ent [batches][64] source words, the weights - one per tile-local row, where every row's entries carry one bit
+    // pattern - in a [32]-float block per slot behind the slot headers of every tile schedule (gp_slot).  0: no program.
+    // gp_entries_req: what gnn_graph_set_program_entries asked for (0: 4 where the graph allows it, else 8).
+    // gp_roww_host: the row weights of every slot's tile in ascending order, kept on the host for the schedules' builds (format 4 only).
+    int gp_entries = 0, gp_entries_req = 0;
+    std::vector<float> gp_roww_host;
     // Tile schedules of the program kernel (gnn_tile_schedule_build, gnn_tile_schedule_ensure): the kernel finds the tile of a ticket
-    // through gp_slot[kind] [slots][4] = {first batch, batches, tile id, 0}, slots = gp_tiles + (a partial last tile ? 1 : 0).  [0]: the
+    // through gp_slot[kind] [slots][4] = {first batch, batches, tile id, 0}, slots = gp_tiles + (a partial last tile ? 1 : 0), followed in
+    // entry format 4 by [slots][32] floats, the row weights of every slot's tile in slot order (prog_roww_request).  [0]: the
     // ascending order, built with the program; [1]: the balanced order for launches of gp_sched_waves waves, built on first demand.
     // gp_hdr_host / gp_cost: header and real entries (arcs) of every slot's tile in ascending order, kept on the host for that build.
     int32_t *gp_slot[2] = {nullptr, nullptr};

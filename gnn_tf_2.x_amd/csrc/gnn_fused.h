@@ -18,6 +18,9 @@ constexpr int GNN_FUSED_THREADS = 64 * GNN_FUSED_WAVES;
 #define GNN_GP_ROW_MASK 31u
 #define GNN_GP_ROW_END 32u
 #define GNN_GP_NOROW 0xfffffe00u
+// Gather form of a k_fused_full instantiation (its PROG template parameter): the CSR walk, or the graph's program with 8-byte entries
+// {source word, weight} or with 4-byte entries (the source word; one weight per tile-local row, gnn_gather_program_compact)
+constexpr int GNN_PROG_NONE = 0, GNN_PROG_ENT8 = 1, GNN_PROG_ENT4 = 2;
 // Last-layer activation of the kernels' ACTL template parameter for a net whose last layer has an activation of its own: "read
 // GnnFusedArgs::act_last" (one instantiation per hidden activation serves all last activations).  Library-internal, not a gnn_activation.
 constexpr int GNN_ACTL_FROM_ARGS = -1;
@@ -72,6 +75,8 @@ struct GnnFusedArgs {
     // host-side record only - the kernel reads every header, this one included, from gp_slot
     // gp_slot [gp_slots][4] = {first batch, batches, tile id, 0}: the program kernel's tile schedule (gnn_tile_schedule_build) - ticket s of
     // the launch stands for the tile of slot s, the partial last tile an ordinary slot; the program kernel reads its headers from here
+    // Entry format 4 (GNN_PROG_ENT4 instantiations; gnn_gather_program_compact): gp_ent [batches][64] = the source words alone, and behind
+    // gp_slot's headers [gp_slots][32] floats: the weight of every tile-local row of the slot's tile (all entries of a row share it)
     const int32_t *gp_hdr, *gp_ent, *gp_slot;
     int gp_tiles, gp_last_first, gp_last_nb, gp_slots;
     int threads;             // threads per workgroup of the launch (0: GNN_FUSED_THREADS); 256 .. 448 in the wide-state form of k_fused_generic
@@ -158,7 +163,8 @@ struct GnnFusedLaunch {
     bool full = false;               // k_fused_full (state width 64) rather than k_fused_generic
     bool given = false;              // ... whose aggregate is given (GnnFusedArgs::agg_in: feature-sliced exchange): no gather
     bool program = false;            // ... or which gathers from the graph's program (gp_ent / gp_slot) rather than walking the CSR
-    int pieces = 3;                  // piece format of the split arithmetic
+    int entries = 8;                 // ... whose entries are 8 bytes {source word, weight} or 4 (source word; the weights per row behind gp_slot's headers)
+    int pieces = 3;                 // piece format of the split arithmetic
     bool seed = false;               // the seeded instantiations (label projection): layer 0 over [state | aggregated state], started from GnnFusedArgs::seed
 };
 struct LoopForm {

@@ -718,6 +718,7 @@ static void decide_bodies(const gnn_loop *l, LoopForm &f, int n_cu)
     f.launch.full = f.kernel == GNN_BODY_FULL_TILE;
     f.launch.given = f.launch.full && a.agg_in != nullptr;
     f.launch.program = f.launch.full && f.program && g->sh->gp_tiles > 0;
+    f.launch.entries = g->sh->gp_entries == 4 ? 4 : 8;
     f.launch.pieces = f.pieces;
     f.launch.seed = f.seeded;
     a.lds_floats = gnn_poison_enabled() ? (int)(f.lds / sizeof(float)) : 0;

@@ -1240,14 +1240,42 @@ __device__ __forceinline__ v4i prog_header_request(const GnnFusedArgs &a, int sl
     if (slot < a.gp_slots) h = *reinterpret_cast<const GNN_GLOBAL v4i *>(gptr(a.gp_slot) + 4 * (int64_t)slot);
     return h;
 }
+// ---- the two entry formats of the program (GNN_PROG_ENT8 / GNN_PROG_ENT4; gnn_gather_program_compact) ----
+// ENT, a lane's entry of a batch as the loaders hold it: v2i {source word, weight} in the 8-byte format, int - the source word - in the
+// 4-byte one, where the weight is the entry's ROW's: all entries of a destination row carry one weight, so the program holds it once per
+// tile-local row, and a lane holds the 32 weights of the tile it works on in one register (roww: lane l has row l & 31's, one dword load
+// per tile beside the slot header).  From the weight on, both formats run the same instructions: the same DPP broadcast, the same
+// v_fma_f32 chain, the same flush at a row end.
+template <int PROG> using prog_ent_t = std::conditional_t<PROG == GNN_PROG_ENT4, int, v2i>;
+template <class ENT> __device__ __forceinline__ ENT prog_ent_make(int word) { if constexpr (std::is_same_v<ENT, int>) return word; else return v2i{word, 0}; }
+__device__ __forceinline__ int prog_word(v2i e) { return e.x; }
+__device__ __forceinline__ int prog_word(int e) { return e; }
+// the weight of this lane's entry: its second half, or row (word & 31)'s of the tile - one ds_bpermute_b32 per batch (the word of padding
+// names row 0: whatever that row weighs, what padding accumulates is never written; an empty row weighs +0, as its entry did)
+__device__ __forceinline__ float prog_weight(v2i e, int) { return __int_as_float(e.y); }
+__device__ __forceinline__ float prog_weight(int e, int roww) { return __int_as_float(__builtin_amdgcn_ds_bpermute((e & (int)GNN_GP_ROW_MASK) << 2, roww)); }
 // this lane's entry of batch b of the program
-__device__ __forceinline__ v2i prog_entry(const GnnFusedArgs &a, int b, int lane)
+template <class ENT>
+__device__ __forceinline__ ENT prog_entry(const GnnFusedArgs &a, int b, int lane)
 {
-    return *reinterpret_cast<const GNN_GLOBAL v2i *>(gptr(a.gp_ent) + ((int64_t)b * 64 + lane) * 2);
+    if constexpr (std::is_same_v<ENT, int>) return *(gptr(a.gp_ent) + ((int64_t)b * 64 + lane));
+    else return *reinterpret_cast<const GNN_GLOBAL v2i *>(gptr(a.gp_ent) + ((int64_t)b * 64 + lane) * 2);
 }
-// first / nb: the tile's header; ent: this lane's entry of the first batch, requested during the previous tile
-template <bool AL16>
-__device__ __forceinline__ void load_tile_prog64(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs, int first, int nb, v2i ent)
+// 4-byte format: the row weights of the tile that ticket `slot` stands for, [gp_slots][32] floats in slot order behind the slot headers -
+// an address from the ticket alone, so the load goes out with the header's; 0 for a slot at or past gp_slots, and in the 8-byte format
+template <class ENT>
+__device__ __forceinline__ int prog_roww_request(const GnnFusedArgs &a, int slot, int lane)
+{
+    int w = 0;
+    if constexpr (std::is_same_v<ENT, int>) {
+        if (slot < a.gp_slots) w = *(gptr(a.gp_slot) + 4 * (int64_t)a.gp_slots + 32 * (int64_t)slot + (lane & 31));
+    }
+    return w;
+}
+// first / nb: the tile's header; ent: this lane's entry of the first batch, requested during the previous tile; roww: the tile's row
+// weights (4-byte format)
+template <bool AL16, class ENT>
+__device__ __forceinline__ void load_tile_prog64(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs, int first, int nb, ENT ent, int roww)
 {
     constexpr int GB = 16;
     const int gl = lane & 15;
@@ -1260,9 +1288,9 @@ __device__ __forceinline__ void load_tile_prog64(const GnnFusedArgs &a, float *X
     for (int b = 0; b < nb; ++b) {
         float w[GB];
         v4f x[GB];
-        const int words = ent.x;
-        prog_batch<AL16, GB>(words, __int_as_float(ent.y), rsrc, voff0, w, x, std::make_integer_sequence<int, GB>{});
-        if (b + 1 < nb) ent = prog_entry(a, first + b + 1, lane);           // (wave-uniform)
+        const int words = prog_word(ent);
+        prog_batch<AL16, GB>(words, prog_weight(ent, roww), rsrc, voff0, w, x, std::make_integer_sequence<int, GB>{});
+        if (b + 1 < nb) ent = prog_entry<ENT>(a, first + b + 1, lane);      // (wave-uniform)
         prog_consume_all<AL16, GB>(words, w, x, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
     }
     own.write(a, X, i0, lane, KP, c_aggs);
@@ -1285,27 +1313,30 @@ __device__ __forceinline__ void prog_rows_request(int words, __amdgpu_buffer_rsr
     ((x[J] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (row_bcast_i<J>(words) & ~0xff) | voff0, 0, 0))), ...);
 }
 template <bool AL16, int GB, int... J>
-__device__ __forceinline__ void prog_consume_first(v2i ent, const v4f (&x)[GB], v2f &acc01, v2f &acc23, float *xo, int KP, std::integer_sequence<int, J...>)
+__device__ __forceinline__ void prog_consume_first(int words, float my_w, const v4f (&x)[GB], v2f &acc01, v2f &acc23, float *xo, int KP, std::integer_sequence<int, J...>)
 {
-    (prog_consume<AL16, J>(ent.x, row_bcast_f<J>(__int_as_float(ent.y)), x[J], acc01, acc23, xo, KP), ...);
+    (prog_consume<AL16, J>(words, row_bcast_f<J>(my_w), x[J], acc01, acc23, xo, KP), ...);
 }
 // the entry of batch 1 of the tile with header (first, nb), if it has one, and the rows of its batch 0 from that batch's entry ent0.  The
 // conditional request goes FIRST: the compiler counts a wait down from the path with the fewest requests behind what it waits for, so behind
 // the rows it would make every wait in front of them (the gate words') reach one request further - to the first row.
-__device__ __forceinline__ void prog_first_batch_request(const GnnFusedArgs &a, int first, int nb, v2i ent0, int lane, v4f (&x0)[16], v2i &ent1)
+template <class ENT>
+__device__ __forceinline__ void prog_first_batch_request(const GnnFusedArgs &a, int first, int nb, ENT ent0, int lane, v4f (&x0)[16], ENT &ent1)
 {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.state_cur), 0, (int)a.state_bytes, 0x00020000);
-    if (nb > 1) ent1 = prog_entry(a, first + 1, lane);                      // (wave-uniform)
+    if (nb > 1) ent1 = prog_entry<ENT>(a, first + 1, lane);                 // (wave-uniform)
     __builtin_amdgcn_sched_barrier(0);
-    prog_rows_request<16>(ent0.x, rsrc, (lane & 15) * 16, x0, std::make_integer_sequence<int, 16>{});
+    prog_rows_request<16>(prog_word(ent0), rsrc, (lane & 15) * 16, x0, std::make_integer_sequence<int, 16>{});
 }
 // The loader that starts by consuming that batch.  ent0 / x0: entry and rows of batch 0; ent: entry of batch 1 (nb > 1).  hdr_next_raw: the
 // next tile's slot header, requested at the top of this tile; with the last batch of this tile it is read (first_next, nb_next, tid_next) and the entry of
 // the next tile's batch 0 requested (ent_next; {GNN_GP_NOROW, 0} when there is no such tile).  A one-batch tile waits for the header.
-template <bool AL16>
+// roww: this tile's row weights (4-byte format): the weights of batch 0 are fetched from them here, where the batch is consumed - across
+// the previous tile's epilogue the batch is its rows and its source word.
+template <bool AL16, class ENT>
 __device__ __forceinline__ void load_tile_prog64_ahead(const GnnFusedArgs &a, float *X, int64_t i0, int lane, int KP, int c_aggs, int first, int nb,
-                                                       v2i ent0, const v4f (&x0)[16], v2i ent, v4i hdr_next_raw, int &first_next, int &nb_next,
-                                                       int &tid_next, v2i &ent_next)
+                                                       ENT ent0, const v4f (&x0)[16], ENT ent, int roww, v4i hdr_next_raw, int &first_next, int &nb_next,
+                                                       int &tid_next, ENT &ent_next)
 {
     constexpr int GB = 16;
     const int gl = lane & 15;
@@ -1320,17 +1351,17 @@ __device__ __forceinline__ void load_tile_prog64_ahead(const GnnFusedArgs &a, fl
     auto request_next = [&]() {
         first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
         tid_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.z);
-        ent = v2i{(int)GNN_GP_NOROW, 0};
-        if (nb_next > 0) ent = prog_entry(a, first_next, lane);             // (wave-uniform)
+        ent = prog_ent_make<ENT>((int)GNN_GP_NOROW);
+        if (nb_next > 0) ent = prog_entry<ENT>(a, first_next, lane);        // (wave-uniform)
     };
     if (nb <= 1) request_next();
-    prog_consume_first<AL16, GB>(ent0, x0, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
+    prog_consume_first<AL16, GB>(prog_word(ent0), prog_weight(ent0, roww), x0, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
     for (int b = 1; b < nb; ++b) {
         float w[GB];
         v4f x[GB];
-        const int words = ent.x;
-        prog_batch<AL16, GB>(words, __int_as_float(ent.y), rsrc, voff0, w, x, std::make_integer_sequence<int, GB>{});
-        if (b + 1 < nb) ent = prog_entry(a, first + b + 1, lane);           // (wave-uniform)
+        const int words = prog_word(ent);
+        prog_batch<AL16, GB>(words, prog_weight(ent, roww), rsrc, voff0, w, x, std::make_integer_sequence<int, GB>{});
+        if (b + 1 < nb) ent = prog_entry<ENT>(a, first + b + 1, lane);      // (wave-uniform)
         else request_next();
         prog_consume_all<AL16, GB>(words, w, x, acc01, acc23, xo, KP, std::make_integer_sequence<int, GB>{});
     }
@@ -1905,15 +1936,22 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_generic(const Gn
 // GIVEN: the aggregated states come from a.agg_in (feature-sliced exchange) - row copies instead of the gather.  A template parameter,
 // not a branch: a wave-uniform branch in the tile loop of this kernel cost 3 % (0.700 -> 0.721 ms).
 // PC: piece format of the split arithmetic (3 = bf16 x 3, 2 = fp16 x 2; gnn_loop_set_pieces)
-// PROG (not GIVEN): every tile is gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the partial
+// PROG (not GIVEN; GNN_PROG_NONE: the CSR walk): every tile is gathered from the graph's gather program (load_tile_prog64; gnn_loop_set_gather_form), the partial
 // last tile of the graph too (an ordinary slot of the tile schedule, prog_header_request): no CSR walk is compiled in.  A template parameter for the same reason as
 // GIVEN.  With GNN_FIRST_BATCH_AHEAD a tile's first batch is requested during the previous tile (load_tile_prog64_ahead).
+// GNN_PROG_ENT8 / GNN_PROG_ENT4: the program's entry format, one per graph (prog_ent_t).  In the 4-byte format a tile's 32 row weights are
+// one dword per lane, requested with the tile's slot header - a tile ahead, in front of the start-up spread for a wave's first tile - where
+// the first batch is requested ahead, and with the next tile's first entry behind the dense layers where it is not (those instantiations
+// have no register to carry them across).
 // ACTL: the last layer's activation (tile_epilogue_last); used in section C only.
 // SEED: the seeded form of the label projection (GNN_FUSED_DENSE_LAYERS; the arguments describe the net over [state | aggregated state]).
-template <int LAYERS, int NT, int ACT, bool SPLIT, bool GIVEN, int PC, bool PROG, int ACTL, bool SEED = false>
+template <int LAYERS, int NT, int ACT, bool SPLIT, bool GIVEN, int PC, int PROG, int ACTL, bool SEED = false>
 __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFusedArgs a0)
 {
     static_assert(!SEED || (SPLIT && !GIVEN), "the label projection is a form of the split arithmetic, and of the gathering kernels");
+    static_assert(PROG == GNN_PROG_NONE || PROG == GNN_PROG_ENT8 || PROG == GNN_PROG_ENT4, "CSR walk, or the program in one of its two entry formats");
+    constexpr bool PROGRAM = PROG != GNN_PROG_NONE;
+    using ENT = prog_ent_t<PROG>;
     constexpr int NTL = 2;
     const GnnFusedArgs &a = a0;      // (shadowed inside the tile loop)
     // Persistent workgroup of 8 waves (one per CU): every wave pulls 32-node tiles from a device-wide counter until none
@@ -1934,7 +1972,8 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     int tile = w_launch + a.tile_base, next_tile = w_launch + W_launch + a.tile_base;
     int ip_first_raw = 0;
     v4i hdr_first_raw = {0, 0, 0, 0};
-    if constexpr (PROG) hdr_first_raw = prog_header_request(a, tile);
+    int roww_cur = 0, roww_next = 0;                  // 4-byte entries: the row weights of the current / the next tile (prog_weight)
+    if constexpr (PROGRAM) { hdr_first_raw = prog_header_request(a, tile); roww_cur = prog_roww_request<ENT>(a, tile, lane); }
     else ip_first_raw = tile_rowptr_request(a, tile, lane);           // on its way while the workgroup stages its vectors below
     float *ep = lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32 + GNN_FUSED_WAVES * 36;
     float *hb = ep + 3 * 32 * NTL;
@@ -1945,14 +1984,14 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     // PROG: header of the current tile (wave-uniform) and this lane's entry of its first batch; AHEAD: the rows of that batch and the entry of
     // the second too
     // (not the bf16-piece format on 128-wide hidden layers: those instantiations stand at 254 - 255 registers without it and spill with it)
-    constexpr bool AHEAD = PROG && GNN_FIRST_BATCH_AHEAD && !(SPLIT && PC == 3 && NT == 4);
+    constexpr bool AHEAD = PROGRAM && GNN_FIRST_BATCH_AHEAD && !(SPLIT && PC == 3 && NT == 4);
     int hdr_first = 0, hdr_nb = 0, tid = 0;
-    v2i ent_cur = {AHEAD ? (int)GNN_GP_NOROW : 0, 0}, ent_second = {0, 0};
+    ENT ent_cur = prog_ent_make<ENT>(AHEAD ? (int)GNN_GP_NOROW : 0), ent_second = prog_ent_make<ENT>(0);
     v4f x_first[16];
-    if constexpr (PROG) {
+    if constexpr (PROGRAM) {
         hdr_first = __builtin_amdgcn_readfirstlane(hdr_first_raw.x); hdr_nb = __builtin_amdgcn_readfirstlane(hdr_first_raw.y);
         tid = __builtin_amdgcn_readfirstlane(hdr_first_raw.z);
-        if (hdr_nb > 0) ent_cur = prog_entry(a, hdr_first, lane);
+        if (hdr_nb > 0) ent_cur = prog_entry<ENT>(a, hdr_first, lane);
         if constexpr (AHEAD) prog_first_batch_request(a, hdr_first, hdr_nb, ent_cur, lane, x_first, ent_second);
     } else {
         ip_cur = tile_rowptr_clamp(a, tile, lane, ip_first_raw);
@@ -1960,14 +1999,14 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     }
     zero_pad_columns(a, X, lane, KP);                 // once: no tile ever writes the padding columns
   for (;;) {
-    const int64_t i0 = (int64_t)(PROG ? tid : tile) * 32;
-    if (PROG ? tile >= a.gp_slots : i0 >= a.n_rows) break;        // wave-uniform; no workgroup barrier anywhere in the tile loop
+    const int64_t i0 = (int64_t)(PROGRAM ? tid : tile) * 32;
+    if (PROGRAM ? tile >= a.gp_slots : i0 >= a.n_rows) break;        // wave-uniform; no workgroup barrier anywhere in the tile loop
     const int nvalid = (int)((a0.n_rows - i0) < 32 ? (a0.n_rows - i0) : 32);
     GnnFusedArgs a = a0;
     if constexpr (SEED) { a.IW = 0; a.NLc = 0; a.AL = 0; }      // (the shadow net has no label columns: as constants, so that the tile loaders' label paths fold away)
     fused_opaque_pointers(a);
 #ifdef GNN_DIAG
-    unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)(PROG ? tid : tile) << 3) : nullptr;      // (by tile id, whatever the schedule)
+    unsigned long long *stamp = a.stamps ? a.stamps + ((size_t)(PROGRAM ? tid : tile) << 3) : nullptr;      // (by tile id, whatever the schedule)
 #endif
     GNN_STAMP(0);
 
@@ -1976,9 +2015,12 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     [[maybe_unused]] int *ipt = reinterpret_cast<int *>(lds + (size_t)GNN_FUSED_WAVES * 32 * KP + 32) + wave * 36;
     int ip_next_raw = 0;
     int hdr_first_next = 0, hdr_nb_next = 0, tid_next = 0;
-    v2i ent_next = {0, 0};
+    ENT ent_next = prog_ent_make<ENT>(0);
     v4i hdr_next_raw = {0, 0, 0, 0};
-    if constexpr (PROG) hdr_next_raw = prog_header_request(a, next_tile);     // program header of the NEXT tile: on its way during the gather
+    if constexpr (PROGRAM) {
+        hdr_next_raw = prog_header_request(a, next_tile);     // program header of the NEXT tile: on its way during the gather
+        if constexpr (AHEAD) roww_next = prog_roww_request<ENT>(a, next_tile, lane);      // ... and with it that tile's row weights
+    }
     else {
         if (lane <= 32) ipt[lane] = ip_cur;           // requested during the previous tile
         ip_next_raw = tile_rowptr_request(a, next_tile, lane);            // row pointers of the NEXT tile: on their way during the gather
@@ -1988,9 +2030,9 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     if (a.variant & 1) __builtin_amdgcn_s_setprio(3);
     if constexpr (GIVEN) load_tile_given64<SPLIT>(a, X, i0, lane, KP, c_aggs);      // feature-sliced exchange: no gather (a.agg_in)
     else if constexpr (AHEAD)
-        load_tile_prog64_ahead<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, x_first, ent_second, hdr_next_raw, hdr_first_next, hdr_nb_next, tid_next, ent_next);
-    else if constexpr (PROG) {
-        load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur);      // (every tile of the launch has a program)
+        load_tile_prog64_ahead<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, x_first, ent_second, roww_cur, hdr_next_raw, hdr_first_next, hdr_nb_next, tid_next, ent_next);
+    else if constexpr (PROGRAM) {
+        load_tile_prog64<SPLIT>(a, X, i0, lane, KP, c_aggs, hdr_first, hdr_nb, ent_cur, roww_cur);      // (every tile of the launch has a program)
         // the next tile's slot header came back in front of the gather's rows: read here, it crosses the dense layers in scalar registers
         // (these instantiations have no vector register to spare: the bf16-piece format on 128-wide hidden layers)
         hdr_first_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.x); hdr_nb_next = __builtin_amdgcn_readfirstlane(hdr_next_raw.y);
@@ -2015,8 +2057,9 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     int ip_next = 0, src_next = 0;
     float w_next = 0.0f;
     if constexpr (AHEAD) { }                                  // (header and batch-0 entry of the next tile: read with this tile's last gather batch)
-    else if constexpr (PROG) {
-        if (hdr_nb_next > 0) ent_next = prog_entry(a, hdr_first_next, lane);      // (header of the next tile: read behind the gather)
+    else if constexpr (PROGRAM) {
+        if (hdr_nb_next > 0) ent_next = prog_entry<ENT>(a, hdr_first_next, lane);      // (header of the next tile: read behind the gather)
+        roww_next = prog_roww_request<ENT>(a, next_tile, lane);
     } else {
         ip_next = tile_rowptr_clamp(a, next_tile, lane, ip_next_raw);
         tile_first_ids(a, ip_next, lane, src_next, w_next);
@@ -2060,7 +2103,7 @@ __global__ void __launch_bounds__(GNN_FUSED_THREADS, 2) k_fused_full(const GnnFu
     tile = next_tile;
     next_tile = fused_next_tile<AHEAD>(a0, next2_tile, third_round, W_launch);
     ip_cur = ip_next; src_cur = src_next; w_cur = w_next;
-    hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; tid = tid_next; ent_cur = ent_next;
+    hdr_first = hdr_first_next; hdr_nb = hdr_nb_next; tid = tid_next; ent_cur = ent_next; roww_cur = roww_next;
   }
 }
 #undef GNN_STAMP
@@ -2104,7 +2147,8 @@ inline bool launch_generic(int nt, int ntl, const GnnFusedLaunch &how, const Gnn
     return true;
 }
 
-// k_fused_full in the launch's gather form - a given aggregate, the graph's program, or the CSR walk - and piece format
+// k_fused_full in the launch's gather form - a given aggregate, the graph's program in the entry format the graph holds, or the CSR walk -
+// and piece format
 // (SEED: no instantiation with a given aggregate - launch_full refuses it)
 template <int LAYERS, int NT, int ACT, bool SPLIT, int ACTL, bool SEED = false>
 inline void launch_full_form(const GnnFusedLaunch &how, const GnnFusedArgs &a, unsigned grid, size_t lds_bytes, hipStream_t st)
@@ -2112,12 +2156,14 @@ inline void launch_full_form(const GnnFusedLaunch &how, const GnnFusedArgs &a, u
     auto gather_form = [&](auto P) {
         constexpr int PC = P.value;
         if constexpr (SEED) {
-            if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, true, ACTL, true>>(a, grid, lds_bytes, st);
-            else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, false, ACTL, true>>(a, grid, lds_bytes, st);
+            if (how.program && how.entries == 4) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, GNN_PROG_ENT4, ACTL, true>>(a, grid, lds_bytes, st);
+            else if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, GNN_PROG_ENT8, ACTL, true>>(a, grid, lds_bytes, st);
+            else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, GNN_PROG_NONE, ACTL, true>>(a, grid, lds_bytes, st);
         } else {
-            if (how.given) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, true, PC, false, ACTL>>(a, grid, lds_bytes, st);
-            else if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, true, ACTL>>(a, grid, lds_bytes, st);
-            else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, false, ACTL>>(a, grid, lds_bytes, st);
+            if (how.given) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, true, PC, GNN_PROG_NONE, ACTL>>(a, grid, lds_bytes, st);
+            else if (how.program && how.entries == 4) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, GNN_PROG_ENT4, ACTL>>(a, grid, lds_bytes, st);
+            else if (how.program) launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, GNN_PROG_ENT8, ACTL>>(a, grid, lds_bytes, st);
+            else launch_kernel<k_fused_full<LAYERS, NT, ACT, SPLIT, false, PC, GNN_PROG_NONE, ACTL>>(a, grid, lds_bytes, st);
         }
     };
     if (SPLIT && how.pieces == 2) gather_form(std::integral_constant<int, 2>{});

@@ -409,7 +409,9 @@ int gnn_loop_body_kernel(gnn_loop *l, int *kernel);
  *   form 2  it reads the graph's gather program: the CSR walked once per graph and stored per tile and lane group in the order of
  *           consumption, the tile's rows split into four contiguous ranges of near-equal entry count (gnn_gather_program_build).  The
  *           program is built with the first Loop that takes this form, shared by the graphs derived from the same graph, and costs
- *           about 9.2 bytes per arc of device memory; a graph for which it cannot be built (no memory, no full tile) runs form 1;
+ *           about 5.5 bytes per arc of device memory where the weights of every destination row are equal (all of the reference's
+ *           aggregation modes: 4-byte entries and one weight per row), about 9.2 otherwise (8-byte entries); a graph for which it
+ *           cannot be built (no memory, no full tile) runs form 1;
  *   form 0  the library's choice (default).
  * Every row's fmaf chain is the same in both forms: states, outputs and k are identical bit for bit.  *used (may be NULL) = the form the
  * next run will take (0 when the fused path does not cover the loop at all); asking for the form builds the program if it is needed. */
@@ -489,8 +491,22 @@ int gnn_loop_set_wide_loader(gnn_loop *l, int loader, int *used);
  * NULL: *n_batches is always set, so a first call sizes ent.  Returns GNN_ERR_UNSUPPORTED when a source id does not fit (>= 2^23). */
 int gnn_gather_program_build(int64_t n_rows, const int32_t *indptr, const int32_t *adj_src, const float *adj_w, int32_t *hdr, int32_t *ent,
                              int64_t *n_batches);
-/* Size and host build time of the program of g's graph: 0 tiles when it has none (yet).  Any pointer may be NULL. */
+/* Size and host build time of the program of g's graph: 0 tiles when it has none (yet).  Any pointer may be NULL.  bytes: 8 tiles + 512
+ * batches in entry format 8; 8 tiles + 256 batches + 128 slots (the row weights of one tile schedule) in entry format 4. */
 int gnn_graph_gather_program_info(const gnn_graph *g, int64_t *tiles, int64_t *batches, int64_t *bytes, float *build_ms);
+/* The compact form of a program (host code; tests/test_gather_program_compact.py): words[64 b + l] = the source word of entry l of batch b,
+ * unchanged; roww[32 t + r] = the weight all entries of tile-local row r of tile t share, +0 for an empty row.  hdr [tiles][2] as built by
+ * gnn_gather_program_build, ent [n_batches][64][2].  Returns GNN_ERR_UNSUPPORTED - "not compactable" - when a row holds two entries whose
+ * weights differ as bit patterns. */
+int gnn_gather_program_compact(int64_t tiles, const int32_t *hdr, int64_t n_batches, const int32_t *ent, int32_t *words, float *roww);
+/* The entry format of the program g's graph holds on its device: *entries = 0 none (yet), 8 {source word, weight} pairs, 4 source words
+ * and one weight per row. */
+int gnn_graph_gather_program_format(const gnn_graph *g, int *entries);
+/* The entry format to build, for A/B runs and tests: 0 the library's choice (4 where every row's weights are one bit pattern, else 8), 8,
+ * or 4.  Drops the program and the tile schedules the graph (and the graphs derived from it) holds, so that the next form-2 Loop rebuilds
+ * them, and rebuilds at once where there was a program or a format is asked for.  *used (may be NULL) = the format held from now on:
+ * asking for 4 on a graph with a non-uniform row keeps 8 (not available); 0 = no program.  Results do not depend on the format. */
+int gnn_graph_set_program_entries(gnn_graph *g, int entries, int *used);
 /* A tile schedule (host code; tests/test_tile_schedule_host.py): order[slot] = the tile that ticket `slot` stands for, for `slots` tiles of
  * cost[t] real entries (arcs) each and launches of `waves` waves.  kind 0: the identity.  kind 1: tiles sorted by cost descending (ties by
  * id ascending); the lightest min(2 waves, slots / 2) last, heaviest of them first; the rest dealt column-wise over 61 strata of the sorted
