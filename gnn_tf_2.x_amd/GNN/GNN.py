@@ -43,6 +43,7 @@ class GNNnodeBased(BaseClass):
         self.gradient_mode = 'unrolled'     # set_gradient_mode
         self.adjoint_max_iteration = None
         self.adjoint_threshold = None
+        self.adjoint_batch_normalization = None     # set_gradient_mode(..., batch_normalization='frozen')
         self.label_projection = 'off'       # set_label_projection
         self.train_recompute = False        # set_train_recompute
         self.wide_state = 'off'             # set_wide_state
@@ -79,26 +80,43 @@ class GNNnodeBased(BaseClass):
         code = _engine.wide_state_mode(mode)
         self.wide_state = {v: k for k, v in _engine.WIDE_STATE_MODES.items()}[code]
 
-    def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
+    def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None, *,
+                          batch_normalization: Optional[str] = None) -> None:
         """How train() differentiates the state loop.  'unrolled' (default): back-propagation through every executed body.
         'fixed_point': the gradient at the converged state (Almeida-Pineda; Scarselli et al. 2009, section III) - the inference Loop
         finds the state, ONE body is recorded there, the adjoint iteration z <- g + J^T z runs until no node's z moves by more than
         ``threshold`` (relative L2, default: the model's state threshold) or ``max_iteration`` iterations (default: the model's), and one
         weight-gradient pass with the final z gives net_state's gradients.  These are not a sum over bodies: ``mean`` does NOT divide them
         by the iteration count.  Needs a net_state without Dropout and BatchNormalization (NotImplementedError); net_output is free.
+        ``batch_normalization='frozen'`` (opt-in; None by default) accepts a net_state that ends in BatchNormalization - what MLP() builds by
+        default - and runs that layer on its MOVING statistics, as in fine-tuning: this is the map the inference Loop iterates, a per-row
+        affine map.  gamma and beta train like any other array; the moving statistics of net_state are NOT updated by train() in this mode
+        (net_output's are).  Dropout in net_state stays refused.
         Kept by copy() (so by LKO) and by save() / load()."""
         if mode not in ('unrolled', 'fixed_point'): raise ValueError("param <mode> not in ['unrolled', 'fixed_point']")
-        if mode == 'fixed_point' and (self.net_state.batch_normalization or any(float(r) != 0.0 for r in self.net_state.dropout_rates())):
+        if batch_normalization not in (None, 'frozen'): raise ValueError("param <batch_normalization> not in [None, 'frozen']")
+        if mode == 'fixed_point' and any(float(r) != 0.0 for r in self.net_state.dropout_rates()):
             raise NotImplementedError('fixed_point gradients need a net_state without Dropout and BatchNormalization: its training-mode '
                                       'forward must be the inference forward')
+        if mode == 'fixed_point' and self.net_state.batch_normalization and batch_normalization is None:
+            raise NotImplementedError('fixed_point gradients need a net_state without Dropout and BatchNormalization: its training-mode '
+                                      "forward must be the inference forward (batch_normalization='frozen' runs it on its moving statistics)")
         if max_iteration is not None and int(max_iteration) < 1: raise ValueError('param <max_iteration> must be >= 1 or None')
         if threshold is not None and not float(threshold) >= 0.0: raise ValueError('param <threshold> must be >= 0 or None')
         self.gradient_mode = mode
         self.adjoint_max_iteration = None if max_iteration is None else int(max_iteration)
         self.adjoint_threshold = None if threshold is None else float(threshold)
+        self.adjoint_batch_normalization = batch_normalization
 
     def _gradient_config(self) -> dict:
-        return {'mode': self.gradient_mode, 'max_iteration': self.adjoint_max_iteration, 'threshold': self.adjoint_threshold}
+        config = {'mode': self.gradient_mode, 'max_iteration': self.adjoint_max_iteration, 'threshold': self.adjoint_threshold}
+        # (written only when set: the dicts and files of models without it are what they were)
+        if self.adjoint_batch_normalization is not None: config['batch_normalization'] = self.adjoint_batch_normalization
+        return config
+
+    def _frozen_state_bn(self) -> bool:
+        """net_state's BatchNormalization runs on its moving statistics in train(): they are not updated."""
+        return self.gradient_mode == 'fixed_point' and self.adjoint_batch_normalization == 'frozen'
 
     # ---- copies, weights ---------------------------------------------------------------------------------------------
     def copy(self, *, path_writer: str = '', namespace: str = '', copy_weights: bool = True):
@@ -111,7 +129,7 @@ class GNNnodeBased(BaseClass):
                              addressed_problem=self.addressed_problem, extra_metrics=self.extra_metrics,
                              extra_metrics_arguments=self.mt_args, state_vect_dim=self.state_vect_dim,
                              path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
-        new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
+        new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, batch_normalization=self.adjoint_batch_normalization)
         new.set_label_projection(self.label_projection)
         new.set_train_recompute(self.train_recompute)
         new.set_wide_state(self.wide_state)
@@ -163,7 +181,8 @@ class GNNnodeBased(BaseClass):
             nets.append(sequential_from_config(arch, weights))
         model = cls(net_state=nets[0], net_output=nets[1], optimizer=optz, loss_function=loss, extra_metrics=extra_metrics,
                     extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
-        model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'))
+        model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'),
+                                batch_normalization=gradient.get('batch_normalization'))
         model.set_label_projection(projection)
         model.set_train_recompute(recompute)
         model.set_wide_state(wide_state)
@@ -211,9 +230,10 @@ class GNNnodeBased(BaseClass):
         if getattr(loop, '_impl_set', None) != self.impl:      # (gnn_loop_set_impl checks the fused path, which re-packs the weight images when the weights
             loop.set_impl(self.impl)                          #  have changed - 0.17 ms after every optimizer step; the next inference Loop packs them anyway)
             loop._impl_set = self.impl
-        gradient = (self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold)
-        if getattr(loop, '_gradient_set', ('unrolled', None, None)) != gradient:
-            loop.set_gradient_mode(*gradient)
+        gradient = (self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, self.adjoint_batch_normalization)
+        if getattr(loop, '_gradient_set', ('unrolled', None, None, None)) != gradient:
+            # (the flag belongs to the fixed-point modes; an unrolled model that carries the keyword sets the plain mode)
+            loop.set_gradient_mode(*gradient[:3], batch_normalization=gradient[3] if gradient[0] != 'unrolled' else None)
             loop._gradient_set = gradient
         if getattr(loop, '_projection_set', 'off') != self.label_projection:
             loop.set_label_projection(self.label_projection)
@@ -333,7 +353,8 @@ class GNNnodeBased(BaseClass):
         new = self.optimizer.apply_gradients(zip(gs + res['grads_output'], ws + wo))
         self.net_state.set_trainable(new[:len(ws)])
         self.net_output.set_trainable(new[len(ws):])
-        self.net_state.update_moving_statistics(res['bn_batch_state'])
+        # (a frozen BatchNormalization took no batch statistics: its moving statistics stay)
+        if not self._frozen_state_bn(): self.net_state.update_moving_statistics(res['bn_batch_state'])
         if loop.n_masked: self.net_output.update_moving_statistics(res['bn_batch_output'])
         return res
 

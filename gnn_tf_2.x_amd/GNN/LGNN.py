@@ -52,11 +52,13 @@ class LGNN(BaseClass):
     def train_recompute(self) -> bool:
         return all(gnn.train_recompute for gnn in self.gnns)
 
-    def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None) -> None:
-        """GNNnodeBased.set_gradient_mode for every layer.  'serial' training runs the layers' own steps and works in both modes; the joint
+    def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None, *,
+                          batch_normalization: Optional[str] = None) -> None:
+        """GNNnodeBased.set_gradient_mode for every layer (``batch_normalization``: forwarded to them).  'serial' training runs the layers'
+        own steps and works in both modes; the joint
         steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' does not return:
         they raise NotImplementedError while any layer is in that mode."""
-        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold)
+        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold, batch_normalization=batch_normalization)
 
     def copy(self, *, path_writer: str = '', namespace: str = '', copy_weights: bool = True) -> 'LGNN':
         optimizer = self.optimizer

@@ -24,6 +24,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
            'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
+           'gnn_loop_set_gradient_mode_ex', 'gnn_adjoint_form_ex', 'gnn_loop_adjoint_z',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_gather_program_compact', 'gnn_graph_gather_program_format', 'gnn_graph_set_program_entries', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -181,21 +182,34 @@ def train_persistent_form(dims, activations, n_rows, max_iter, rates=None) -> di
 
 GATHER_NAMES = {0: 'generic', 1: 'rows', 2: 'rows_aligned', 3: 'narrow'}       # gather form of gnn_loop_adjoint_info / gnn_adjoint_form
 ADJOINT_REFUSALS = {0: None, 1: 'batch_normalization', 2: 'dropout'}
+ADJOINT_FROZEN_BN = 1           # GNN_ADJOINT_FROZEN_BN of include/gnn_hip.h (gnn_loop_set_gradient_mode_ex, gnn_adjoint_form_ex)
+
+
+def adjoint_flags(batch_normalization) -> int:
+    """The flags of gnn_loop_set_gradient_mode_ex for the keyword ``batch_normalization`` of the Python layers: None or 'frozen'."""
+    if batch_normalization not in (None, 'frozen'): raise ValueError("param <batch_normalization> not in [None, 'frozen']")
+    return ADJOINT_FROZEN_BN if batch_normalization == 'frozen' else 0
 NARROW_REFUSALS = {0: None, 3: 'layers', 4: 'width', 5: 'concat', 6: 'rows', 7: 'softmax'}      # why the one-launch iteration of narrow nets is not taken
 
 
-def adjoint_form(dims, activations, n_rows, rates=None, batch_normalization=False) -> dict:
+def adjoint_form(dims, activations, n_rows, rates=None, batch_normalization=False, *, frozen_bn=None) -> dict:
     """gnn_adjoint_form (host code, no device): what an adjoint iteration of the fixed-point gradient launches for a net_state of this
     description on n_rows rows - dict(eligible; reason: None, 'batch_normalization' or 'dropout'; gather: a name of GATHER_NAMES;
     backward: one name of FORM_NAMES per Dense layer; narrow_refusal: None when an iteration is ONE launch (k_adjoint_narrow), else why
-    not: 'layers' (> 3), 'width' (> 64), 'concat' (> 96), 'rows' (>= 4,096 or none), 'softmax').  The state width is dims[-1]."""
+    not: 'layers' (> 3), 'width' (> 64), 'concat' (> 96), 'rows' (>= 4,096 or none), 'softmax').  The state width is dims[-1].
+    frozen_bn='frozen' (gnn_adjoint_form_ex with GNN_ADJOINT_FROZEN_BN): the report for a loop set with that flag - a net with
+    batch_normalization is then eligible, with the forms of its Dense chain."""
     L = len(dims) - 1
     if L < 1 or len(activations) != L: raise ValueError('dims needs one entry more than activations')
     d = np.ascontiguousarray(dims, np.int32)
     a = np.asarray([ACT_CODES[x] for x in activations], np.int32)
     r = _f32(rates if rates is not None else np.zeros(L + 1), (L + 1,))
     out = np.zeros(4 + L, np.int32)
-    _check(lib().gnn_adjoint_form(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int(bool(batch_normalization)), C.c_int64(int(n_rows)), _ip(out)))
+    flags = adjoint_flags(frozen_bn)
+    if flags:
+        _check(lib().gnn_adjoint_form_ex(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int(bool(batch_normalization)), C.c_int(flags), C.c_int64(int(n_rows)), _ip(out)))
+    else:
+        _check(lib().gnn_adjoint_form(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int(bool(batch_normalization)), C.c_int64(int(n_rows)), _ip(out)))
     return dict(eligible=bool(out[0]), reason=ADJOINT_REFUSALS[int(out[1])], gather=GATHER_NAMES[int(out[2])],
                 backward=[FORM_NAMES[int(v)] for v in out[3:3 + L]], narrow_refusal=NARROW_REFUSALS[int(out[3 + L])])
 
@@ -702,6 +716,8 @@ class Loop:
             return out
 
         kk = int(k.value)
+        # (fixed-point modes: the k bodies were the inference Loop's - net_state has no batch statistics, bn_batch_state is left unwritten)
+        if getattr(self, '_gradient_mode', 0) != 0: kk = 0
         res = dict(loss=float(loss.value), k=float(k.value), grads_state=split(gs, shp_s), grads_output=split(go, shp_o),
                    bn_batch_state=bns[:kk], bn_batch_output=bno)
         if getattr(self, '_gradient_mode', 0) != 0:
@@ -795,6 +811,7 @@ class Loop:
         """gnn_loop_train_backward: dict(grads_state, grads_output (raw sums over the iterations), bn_batch_state,
         bn_batch_output, d_nodes [N, NL] or None)."""
         net_state, net_output, kk = self._train_nets
+        if getattr(self, '_gradient_mode', 0) != 0: kk = 0       # (fixed-point modes: no batch statistics of net_state, as in train_step)
         shp_s, shp_o = self._grad_shapes(net_state), self._grad_shapes(net_output)
         gs = np.zeros(sum(int(np.prod(x)) for x in shp_s), np.float32)
         go = np.zeros(sum(int(np.prod(x)) for x in shp_o), np.float32)
@@ -895,17 +912,24 @@ class Loop:
         _check(lib().gnn_loop_train_recompute_info(self._h, _ip(out)))
         return dict(state_only=bool(out[0]), replayed=int(out[1]), cacheless_chain=int(out[2]))
 
-    def set_gradient_mode(self, mode, max_iteration=None, threshold=None) -> int:
+    def set_gradient_mode(self, mode, max_iteration=None, threshold=None, *, batch_normalization=None) -> int:
         """gnn_loop_set_gradient_mode: 'unrolled' / 0 (default: back-propagation through the executed bodies) or 'fixed_point' / 1 (the
         gradient at the converged state: inference Loop, one recorded body, adjoint iteration z <- g + J^T z, one weight-gradient pass).
         max_iteration / threshold of the adjoint iteration: None = the loop's own.  In fixed-point mode grads_state is NOT a sum over bodies
         (never divide it by k), train_step() reports adjoint_iterations / adjoint_converged, and net_state must have neither Dropout nor
-        BatchNormalization (NotImplementedError).  'fixed_point_chain' / 2: fixed point without the one-launch iteration of narrow nets (A/B runs, tests)."""
+        BatchNormalization (NotImplementedError).  'fixed_point_chain' / 2: fixed point without the one-launch iteration of narrow nets (A/B runs, tests).
+        batch_normalization='frozen' (gnn_loop_set_gradient_mode_ex with GNN_ADJOINT_FROZEN_BN): a net_state that ends in BatchNormalization is
+        accepted, on its moving statistics, which the step leaves untouched; gamma and beta train.  None: gnn_loop_set_gradient_mode."""
         code = {'unrolled': 0, 'fixed_point': 1, 'fixed_point_chain': 2, 0: 0, 1: 1, 2: 2}.get(mode)
         if code is None: raise ValueError("gradient mode must be 'unrolled' or 'fixed_point'")
+        flags = adjoint_flags(batch_normalization)
         used = C.c_int(0)
-        _check(lib().gnn_loop_set_gradient_mode(self._h, C.c_int(code), C.c_int(int(max_iteration) if max_iteration else 0),
-                                                C.c_float(-1.0 if threshold is None else float(threshold)), C.byref(used)))
+        if flags:
+            _check(lib().gnn_loop_set_gradient_mode_ex(self._h, C.c_int(code), C.c_int(int(max_iteration) if max_iteration else 0),
+                                                       C.c_float(-1.0 if threshold is None else float(threshold)), C.c_int(flags), C.byref(used)))
+        else:
+            _check(lib().gnn_loop_set_gradient_mode(self._h, C.c_int(code), C.c_int(int(max_iteration) if max_iteration else 0),
+                                                    C.c_float(-1.0 if threshold is None else float(threshold)), C.byref(used)))
         self._gradient_mode = used.value
         return used.value
 
@@ -914,6 +938,12 @@ class Loop:
         it, cv, fm = C.c_int(0), C.c_int(0), C.c_int(0)
         _check(lib().gnn_loop_adjoint_info(self._h, C.byref(it), C.byref(cv), C.byref(fm)))
         return dict(iterations=int(it.value), converged=bool(cv.value), gather=GATHER_NAMES[int(fm.value)])
+
+    def adjoint_z(self) -> np.ndarray:
+        """gnn_loop_adjoint_z (test entry point): z_final [n_rows, Ds] of the last backward pass in a fixed-point mode."""
+        z = np.zeros((self.n_rows, self.Ds), np.float32)
+        _check(lib().gnn_loop_adjoint_z(self._h, _fp(z)))
+        return z
 
     def train_arena_bytes(self) -> int:
         """gnn_loop_train_arena_bytes (test entry point): bytes of device scratch the last training forward / backward of this loop used."""

@@ -185,6 +185,9 @@ struct Net {
     size_t g_total = 0;
     float *part = nullptr;        // [chunks of the rows][g_total]: the partial gradients of ONE net_backward call
     int64_t part_rows = -1;
+    // BatchNormalization on its MOVING statistics (the fixed-point gradient with GNN_ADJOINT_FROZEN_BN; net_freeze_bn): frozen [2 F] =
+    // inv_j = 1 / sqrtf(var_mov_j + eps) | s_j = gamma_j inv_j, made once per step; no call is counted, stats_all stays zero
+    float *frozen = nullptr;
     float *stats_all = nullptr;   // [max forward calls][2 F]: batch mean | biased batch variance of every BatchNormalization call, in call order
     int calls = 0, max_calls = 0;
     // The form every forward / backward call of this step takes, decided once by net_setup for the `rows` rows of each call:
@@ -319,6 +322,8 @@ int small_train_launch(hipStream_t st, const Net &net, const SmallTrainForm &f, 
 void net_decide_form(Net &net, int64_t n, bool producer_dropout);
 int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float *rates, const float *bn_gamma_beta_host, int max_calls, float *zero_mem,
               int64_t rows, bool producer_dropout);
+// behind net_setup: this step runs the net's BatchNormalization on its moving statistics (Net::frozen)
+int net_freeze_bn(hipStream_t st, Buf &buf, Net &net);
 // How a body of the recomputing step (gnn_loop_set_train_recompute) calls net_forward; the default is the ordinary call.
 //   y_dst: where the call's output goes (the one array of a state-only body that outlives it; NULL: allocated like the others)
 //   cacheless: the first pass may take the forms that do not store what only the backward pass reads (a0 / a1 of the three-layer chain, xhat);
@@ -346,9 +351,10 @@ enum { ADJ_GATHER_GENERIC = 0, ADJ_GATHER_ROWS = 1, ADJ_GATHER_ROWS_ALIGNED = 2,
 // state rows of whole 16-byte pieces, at most 16 of them: 16 lanes per row take four columns each (else: every 16th column)
 inline bool adjoint_rows16(int Ds) { return (Ds & 3) == 0 && Ds <= 64; }
 // why a net_state cannot take gradient mode 1 (0: it can): 1 BatchNormalization, 2 a Dropout rate != 0
-inline int adjoint_refusal(const gnn_mlp *m, const float *rates)
+// (flags: gnn_loop_set_gradient_mode_ex - with GNN_ADJOINT_FROZEN_BN the BatchNormalization runs on its moving statistics and is accepted)
+inline int adjoint_refusal(const gnn_mlp *m, const float *rates, int flags = 0)
 {
-    if (m->has_bn) return 1;
+    if (m->has_bn && !(flags & GNN_ADJOINT_FROZEN_BN)) return 1;
     for (int l = 0; l <= m->n_layers; ++l) if (rates[l] != 0.0f) return 2;
     return 0;
 }
@@ -375,6 +381,7 @@ struct AdjNarrow {
     int Ds, c_aggs, L, gather;    // gather: form z_L from u_prev / z_prev / g and evaluate the gate (else z_L is read from z_cur)
     int dims[4], acts[3];
     const float *WT[3], *a[3];
+    const float *colscale;        // frozen BatchNormalization behind the last layer: s_j = gamma_j inv_j [Ds] (NULL: none)
     const int32_t *sip, *sdst;
     const float *sw, *g, *z_prev, *u_prev;
     float *z_cur, *u_out;
@@ -407,6 +414,7 @@ struct GNN_INTERNAL gnn_train_ctx {
     bool recompute = false;       // the forward ran state-only: `caches` holds k empty entries until train_backward rebuilds them one at a time
     int replayed = 0;             // ... bodies rebuilt by the backward pass
     int cacheless_chain = 0;      // ... the first pass launched the cache-less three-layer chain (else the ordinary kernels on rewound scratch)
+    float *adjoint_z = nullptr;   // gradient modes 1 and 2, behind the backward pass: z_final [N, Ds] (gnn_loop_adjoint_z)
     bool fixed_point = false;     // gradient mode 1: `caches` holds ONE recorded body at the converged state `state` (k bodies of the inference Loop led there)
     bool persistent = false;      // the bodies ran in the persistent launch (k_train_small) ...
     int workgroups = 0, barriers = 0;     // ... of that many workgroups, with that many grid barriers per body
@@ -429,7 +437,8 @@ namespace gnn_train GNN_INTERNAL {
 // both nets of the loop with what differs between them: BatchNormalization calls of this step's forward (their statistics rows in
 // Net::stats_all), index 0 net_state, 1 net_output
 struct LoopNet { gnn_mlp *m; Net *net; int calls; };
-inline std::array<LoopNet, 2> loop_nets(gnn_loop *l, gnn_train_ctx *cx) { return {{{l->st, &cx->ns, cx->k}, {l->ou, &cx->no_, cx->M > 0 ? 1 : 0}}}; }
+// (gradient modes 1 and 2: the k bodies were the inference Loop's - net_state made no BatchNormalization call, its moving statistics stay)
+inline std::array<LoopNet, 2> loop_nets(gnn_loop *l, gnn_train_ctx *cx) { return {{{l->st, &cx->ns, cx->fixed_point ? 0 : cx->k}, {l->ou, &cx->no_, cx->M > 0 ? 1 : 0}}}; }
 
 // gnn_train_update.hip: between the backward pass and the update
 int grad_prepare(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st);

@@ -843,7 +843,7 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     float k_inference = 0.0f;
     if (fixed_point) {
         if (sharded) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient is single-GPU");
-        const int why = adjoint_refusal(l->st, dropout_state);
+        const int why = adjoint_refusal(l->st, dropout_state, l->train.adjoint.flags);
         if (why) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient needs a net_state whose training-mode forward is the inference forward: this one has %s",
                                  why == 1 ? "a BatchNormalization" : "a Dropout rate != 0");
         if ((rc = gnn_loop_run(l, 0, &k_inference))) return rc;
@@ -873,6 +873,8 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
     HIPCHK(hipMemsetAsync(zero_mem, 0, sizeof(float) * std::max<size_t>(1, z_total), st));
     if ((rc = net_setup(st, buf, cx->ns, l->st, dropout_state, bn_state, max_iter, zero_mem, N, true)) ||
         (rc = net_setup(st, buf, cx->no_, l->ou, dropout_output, bn_output, 1, zero_mem + z_s, M, false))) return rc;
+    // (gradient modes 1 and 2 reach this line with a BatchNormalization in net_state only under GNN_ADJOINT_FROZEN_BN: adjoint_refusal above)
+    if (fixed_point && l->st->has_bn && (rc = net_freeze_bn(st, buf, cx->ns))) return rc;
     f.flags = reinterpret_cast<int *>(zero_mem + z_s + z_o);
     cx->tmpl = zero_mem + z_s + z_o + z_f;
     cx->seed = seed;
@@ -1057,6 +1059,7 @@ static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, floa
                 p.n = N; p.Ds = Ds; p.c_aggs = Ds + l->NLc; p.L = m->n_layers; p.gather = t > t0;
                 for (int q = 0; q <= m->n_layers; ++q) p.dims[q] = m->dims[q];
                 for (int q = 0; q < m->n_layers; ++q) { p.acts[q] = m->acts[q]; p.WT[q] = ns.WT[q]; p.a[q] = c.a[q]; }
+                p.colscale = ns.frozen ? ns.frozen + Ds : nullptr;
                 p.sip = cx->d_sip; p.sdst = cx->d_sdst; p.sw = cx->d_sw;
                 p.g = g_state; p.z_prev = t > 0 ? z_of(t - 1) : nullptr; p.u_prev = ub[(t + 1) & 1]; p.z_cur = z_of(t); p.u_out = ub[t & 1];
                 p.thr = thr; p.gate_prev = gate_of(t - 2); p.gate = gate_of(t - 1);
@@ -1088,6 +1091,7 @@ static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, floa
         }
     }
     arena->rewind(mark);
+    cx->adjoint_z = adj.iterations == 0 ? g_state : zb[adj.iterations & 1];
     // `work` holds z_final (the last gather wrote it beside its z buffer; without an iteration it is the copy of g)
     float *u = nullptr;
     return net_backward(st, buf, ns, cx->caches[0], work, &u, nullptr, nullptr, 0, true);

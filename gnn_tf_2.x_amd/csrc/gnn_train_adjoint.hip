@@ -198,6 +198,7 @@ __global__ void __launch_bounds__(256) k_adjoint_narrow(const AdjNarrow p)
                 nrm = nrm + zp * zp;
             } else
                 zc = p.z_cur[r * Ds + c];
+            if (p.colscale) zc = zc * p.colscale[c];                    // frozen BatchNormalization behind the last layer: d h = d s_j
             zc = zc * act_grad(p.a[L - 1][r * Ds + c], p.acts[L - 1]);
         }
         db[0][lr * ADJ_NARROW_MAXW + c] = zc;
@@ -264,8 +265,9 @@ int launch_adjoint_gather(hipStream_t st, const StateGradJob &job, const float *
 
 }   // namespace gnn_train
 
-extern "C" int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int64_t n_rows, int *out)
+extern "C" int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out)
 {
+    ARGCHK((flags & ~GNN_ADJOINT_FROZEN_BN) == 0, "flags: GNN_ADJOINT_FROZEN_BN or 0");
     ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && rates && n_rows >= 0 && out, "bad arguments");
     gnn_mlp m;
     m.n_layers = n_layers;
@@ -279,7 +281,7 @@ extern "C" int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, 
     net.rate.assign(rates, rates + n_layers + 1);
     net_decide_form(net, n_rows, true);
     const int Ds = m.dims[n_layers];
-    out[1] = adjoint_refusal(&m, rates);
+    out[1] = adjoint_refusal(&m, rates, flags);
     out[0] = out[1] == 0;
     // (the chain leaves its aligned rows where state_rows16 holds: with its many rows, wherever the state rows are 16-byte pieces)
     out[2] = adjoint_rows16(Ds) ? (net.bwd3 && n_rows > 0 ? ADJ_GATHER_ROWS_ALIGNED : ADJ_GATHER_ROWS) : ADJ_GATHER_GENERIC;
@@ -293,19 +295,31 @@ extern "C" int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, 
     return GNN_OK;
 }
 
-extern "C" int gnn_loop_set_gradient_mode(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int *used)
+extern "C" int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int64_t n_rows, int *out)
+{
+    return gnn_adjoint_form_ex(n_layers, dims, acts, rates, has_bn, 0, n_rows, out);
+}
+
+extern "C" int gnn_loop_set_gradient_mode_ex(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int flags, int *used)
 {
     ARGCHK(l, "loop is NULL");
+    ARGCHK((flags & ~GNN_ADJOINT_FROZEN_BN) == 0, "flags: GNN_ADJOINT_FROZEN_BN or 0");
     ARGCHK(mode >= 0 && mode <= 2, "gradient mode: 0 unrolled, 1 fixed point, 2 fixed point without the one-launch iteration of narrow nets");
     ARGCHK(adjoint_max_iter >= 0 && !std::isnan(adjoint_threshold), "adjoint_max_iter must be >= 0 (0: the loop's max_iter), adjoint_threshold a number (< 0: the loop's threshold)");
     if (mode && l->world > 1) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient is single-GPU (this loop is rank %d of %d)", l->rank, l->world);
-    if (mode && l->st->has_bn)
+    if (mode && l->st->has_bn && !(flags & GNN_ADJOINT_FROZEN_BN))
         return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient needs a net_state without BatchNormalization (its training-mode forward must be the inference forward)");
     l->train.adjoint.mode = mode;
+    l->train.adjoint.flags = mode ? flags : 0;
     l->train.adjoint.max_iter = adjoint_max_iter;
     l->train.adjoint.thr = adjoint_threshold;
     if (used) *used = mode;
     return GNN_OK;
+}
+
+extern "C" int gnn_loop_set_gradient_mode(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int *used)
+{
+    return gnn_loop_set_gradient_mode_ex(l, mode, adjoint_max_iter, adjoint_threshold, 0, used);
 }
 
 extern "C" int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *converged, int *form)
@@ -314,6 +328,18 @@ extern "C" int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *co
     if (iterations) *iterations = l->train.adjoint.iterations;
     if (converged) *converged = l->train.adjoint.converged;
     if (form) *form = l->train.adjoint.gather;
+    return GNN_OK;
+}
+
+// z_final of the last backward pass of modes 1 / 2 (the z buffer its last iteration wrote; the step's scratch lives until the next forward)
+extern "C" int gnn_loop_adjoint_z(gnn_loop *l, float *z_host)
+{
+    ARGCHK(l && z_host, "bad arguments");
+    const gnn_train_ctx *cx = l->train_ctx;
+    if (!cx || !cx->fixed_point || !cx->backward_done || !cx->adjoint_z) return gnn_fail(GNN_ERR_STATE, "no backward pass of a fixed-point gradient mode to take z from");
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipStreamSynchronize(l->stream));
+    if (cx->N > 0) HIPCHK(hipMemcpy(z_host, cx->adjoint_z, sizeof(float) * (size_t)cx->N * l->Ds, hipMemcpyDeviceToHost));
     return GNN_OK;
 }
 

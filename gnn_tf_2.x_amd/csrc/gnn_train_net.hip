@@ -249,6 +249,44 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(int64_t n, int F, int cw_s
     }
 }
 
+// ---- BatchNormalization on its MOVING statistics (the fixed-point gradient with GNN_ADJOINT_FROZEN_BN) -------------------------------------
+// A per-row affine map, the one the inference Loop iterates: no statistics kernel, no chunk merge, and a Jacobian that is a per-column scale.
+// k_bn_frozen_prepare, once per step: frozen = [inv_j = 1 / sqrtf(var_mov_j + eps) | s_j = gamma_j inv_j]; raw: the MLP's [gamma | beta | mean | var].
+__global__ void k_bn_frozen_prepare(int F, float eps, const float *raw, const float *gamma, float *frozen)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= F) return;
+    const float inv = 1.0f / sqrtf(raw[3 * F + j] + eps);
+    frozen[j] = inv;
+    frozen[F + j] = gamma[j] * inv;
+}
+
+// the recorded body: xhat = (h - mean_mov) inv, y = gamma xhat + beta (bn_normalize, as k_bn_apply on batch statistics)
+__global__ void __launch_bounds__(256) k_bn_apply_frozen(int64_t n, int F, const float *__restrict__ h, const float *__restrict__ mean, const float *__restrict__ inv,
+                                                         const float *__restrict__ gamma, const float *__restrict__ beta, float *xhat, float *y)
+{
+    const int64_t total = n * F, step = (int64_t)gridDim.x * blockDim.x;
+    const bool small = total < ((int64_t)1 << 31);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int j = small ? (int)((unsigned)i % (unsigned)F) : (int)(i % F);
+        bn_normalize(h[i], mean[j], inv[j], gamma[j], beta[j], &xhat[i], &y[i]);
+    }
+}
+
+// the way back: d <- d s_j, then, fused, the derivative of the layer's activation: d <- d act'(a) (act < 0: none) - in the place of
+// k_bn_bwd_apply behind k_colreduce2 (weight pass), or alone in the place of k_act_bwd (an adjoint iteration)
+__global__ void __launch_bounds__(256) k_bn_bwd_frozen(int64_t n, int F, float *d, const float *__restrict__ scale, const float *__restrict__ a, int act)
+{
+    const int64_t total = n * F, step = (int64_t)gridDim.x * blockDim.x;
+    const bool small = total < ((int64_t)1 << 31);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int j = small ? (int)((unsigned)i % (unsigned)F) : (int)(i % F);
+        float v = d[i] * scale[j];
+        if (act >= 0) v = v * act_grad(a[i], act);
+        d[i] = v;
+    }
+}
+
 // Weight and bias gradient of one Dense layer over one row chunk: part[chunk * pstride + i * n_out + j] = sum_r H'[r, i] DZ[r, j]
 // with H' = [H | 1] (row i = n_in is the bias gradient: dW and db are adjacent in the gradient vector).  32 x 32 outputs per
 // block, 2 x 2 per thread (one 8-byte LDS read of each operand per four products), 64 rows staged per step, the next step's
@@ -595,6 +633,18 @@ int net_setup(hipStream_t st, Buf &buf, Net &net, const gnn_mlp *m, const float 
     return GNN_OK;
 }
 
+int net_freeze_bn(hipStream_t st, Buf &buf, Net &net)
+{
+    const gnn_mlp *m = net.m;
+    if (!m->has_bn) return GNN_OK;
+    const int F = m->dims.back();
+    int rc;
+    if ((rc = buf.get(&net.frozen, (size_t)2 * F))) return rc;
+    hipLaunchKernelGGL(k_bn_frozen_prepare, cdiv(F, 64), 64, 0, st, F, m->eps, m->bn_raw, net.gamma, net.frozen);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
 // training-mode forward of one Sequential on its net.rows rows (x: [rows, dims[0]]); *y_out: [rows, dims.back()].  keep0 != NULL: the Dropout
 // in front of the first Dense layer has been applied by the producer of x (k_train_input), its mask is keep0.  rng: the streams of the
 // masks that are not injected (masks == NULL).
@@ -693,7 +743,17 @@ int net_forward(hipStream_t st, Buf &buf, Net &net, float *x, uint8_t *keep0, co
         }
         h = c.a[l];
     }
-    if (m->has_bn) {
+    if (m->has_bn && net.frozen) {                 // on the moving statistics: no call is counted, no statistics are left
+        const int F = m->dims.back();
+        float *y = mode.y_dst;
+        if (comm || mode.cacheless || mode.replay_call >= 0) return gnn_fail(GNN_ERR_STATE, "internal: a frozen BatchNormalization is one recorded body on one GPU");
+        if ((rc = buf.get(&c.xhat, (size_t)n * F)) || (!y && (rc = buf.get(&y, (size_t)n * F)))) return rc;
+        if (n > 0) {
+            hipLaunchKernelGGL(k_bn_apply_frozen, elementwise_grid(n * F), 256, 0, st, n, F, h, m->bn_raw + 2 * F, net.frozen, net.gamma, net.beta, c.xhat, y);
+            HIPCHK(hipGetLastError());
+        }
+        h = y;
+    } else if (m->has_bn) {
         const int F = m->dims.back();
         float *y = mode.y_dst, *stats_out = nullptr;
         const bool want_xhat = !mode.cacheless || comm;
@@ -771,7 +831,8 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
     }
     const int64_t rpb = rows_per_block(n);
     const int parts = (int)cdiv(n, rpb);
-    if (!wgrad && m->has_bn) return gnn_fail(GNN_ERR_STATE, "internal: an input-gradient-only backward pass through BatchNormalization");
+    const bool frozen = m->has_bn && net.frozen != nullptr;
+    if (!wgrad && m->has_bn && !frozen) return gnn_fail(GNN_ERR_STATE, "internal: an input-gradient-only backward pass through BatchNormalization");
     if (wgrad && net.part_rows != n) {
         if ((rc = buf.get(&net.part, (size_t)parts * net.g_total))) return rc;
         net.part_rows = n;
@@ -780,7 +841,16 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
     const int act_last = m->acts[L - 1];
     // the derivative of the last activation rides on the BatchNormalization pass when nothing sits between them
     bool last_act_done = false;
-    if (m->has_bn) {
+    if (frozen) {
+        // d gamma / d beta from the chunk partials as below (weight pass only); d h = d s_j has no mean or variance terms
+        const int F = m->dims.back(), cs = column_shift(F);
+        const bool fuse = net.rate[L] == 0.0f && act_last != GNN_ACT_SOFTMAX;
+        if (comm) return gnn_fail(GNN_ERR_STATE, "internal: a frozen BatchNormalization is single-GPU");
+        if (wgrad) hipLaunchKernelGGL(k_colreduce2, dim3(cdiv(F, 1 << cs), parts), 256, 0, st, n, F, cs, d, c.xhat, net.part + net.g_off[2 * L], net.part + net.g_off[2 * L + 1], ps, rpb);
+        hipLaunchKernelGGL(k_bn_bwd_frozen, elementwise_grid(n * F), 256, 0, st, n, F, d, net.frozen + F, c.a[L - 1], fuse ? act_last : -1);
+        HIPCHK(hipGetLastError());
+        last_act_done = fuse;
+    } else if (m->has_bn) {
         const int F = m->dims.back(), cs = column_shift(F);
         float *p_dyx = net.part + net.g_off[2 * L], *p_dy = net.part + net.g_off[2 * L + 1];
         const bool fuse = net.rate[L] == 0.0f && act_last != GNN_ACT_SOFTMAX;

@@ -247,12 +247,26 @@ int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, const float *
  * a step is bound by its launch count) run an adjoint iteration as ONE launch: a block owns 16 rows, forms their z from the previous launch's u with
  * the gate of the previous iteration, and runs the whole chain through W^T with the weights staged in LDS (same sums, float32 fmaf).  mode 2 is mode 1
  * without that form (the per-kernel chain everywhere): for A/B runs and tests.
+ * gnn_loop_set_gradient_mode_ex with GNN_ADJOINT_FROZEN_BN in flags (opt-in; flags 0 IS gnn_loop_set_gradient_mode): a net_state that ends in
+ * BatchNormalization is accepted in modes 1 and 2, on its MOVING statistics - the per-row affine map the inference Loop iterates:
+ *   Forward        unchanged (the inference Loop folds the moving statistics into scale and shift already).
+ *   Recorded body  behind the Dense chain: inv_j = 1 / sqrtf(var_mov_j + eps), xhat = (h - mean_mov_j) inv_j, y = gamma_j xhat + beta_j; no batch
+ *                  statistics are taken, xhat is kept for the weight pass alone.
+ *   Adjoint        z is scaled per column by s_j = gamma_j inv_j (one vector of Ds floats per step) in front of act'(a_last): d h = d s_j.  There
+ *                  are no mean or variance terms.
+ *   net_state gradients   d gamma_j = sum_r d[r, j] xhat[r, j], d beta_j = sum_r d[r, j] (fixed-order chunk partials), d h = d s_j, then the
+ *                  Dense chain as without BatchNormalization.  gamma and beta train like any other array.
+ *   Moving statistics of net_state   NOT touched: not by the armed step, gnn_loop_optimizer_step or gnn_loop_update_moving_statistics, and
+ *                  bn_batch_state is left unwritten (there are no batch statistics of net_state).  net_output's are updated as in mode 0.
+ * Dropout in net_state, world > 1 and d_nodes / d_arc_labels stay refused.
  * adjoint_max_iter = 0 / adjoint_threshold < 0: the loop's own max_iter / threshold.  *used (may be NULL) = the mode now set.
  * gnn_loop_adjoint_info: iterations and converged (0 / 1) of the last backward pass of mode 1, and the form of its gather (0: any Ds, every
  * 16th column per lane; 1: 16-byte pieces, Ds % 4 == 0 and Ds <= 64; 2: the same from the aligned rows the three-layer chain leaves; 3: inside the
  * one-launch iteration of narrow nets);
  * any pointer may be NULL. */
 int gnn_loop_set_gradient_mode(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int *used);
+enum { GNN_ADJOINT_FROZEN_BN = 1 };
+int gnn_loop_set_gradient_mode_ex(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int flags, int *used);
 int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *converged, int *form);
 /* What an adjoint iteration of mode 1 launches for a net_state of this description (arguments as gnn_train_forms; the state width is
  * the net's last width) on n_rows rows - host code, no device, the decision the step itself takes.  out receives 4 + n_layers ints: out[0] = 1
@@ -262,6 +276,12 @@ int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *converged, in
  * out[3 + n_layers] = why the one-launch iteration of narrow nets is NOT taken (0: it is; 3 more than three layers, 4 a layer wider than 64, 5 a concat
  * wider than 96, 6 4,096 rows or more, or none, 7 a softmax in net_state). */
 int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int64_t n_rows, int *out);
+/* The same for a loop set with `flags` (gnn_loop_set_gradient_mode_ex): with GNN_ADJOINT_FROZEN_BN a net with has_bn != 0 is eligible (out[1] = 0)
+ * and the forms are those of its Dense chain - the frozen BatchNormalization pass takes the place of the last activation's derivative pass and is
+ * inside the one-launch iteration of narrow nets.  flags 0: gnn_adjoint_form. */
+int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out);
+/* z_final [n_rows, Ds] of the last backward pass of mode 1 / 2, to host memory (test entry point; GNN_ERR_STATE without such a pass). */
+int gnn_loop_adjoint_z(gnn_loop *l, float *z_host);
 /* Bytes handed out from the step's scratch by the last training forward / backward of this loop (test entry point). */
 int gnn_loop_train_arena_bytes(const gnn_loop *l, int64_t *bytes);
 /* Optimizer step on the device (reference GNN_BaseClass.py:243-247, optimizer.apply_gradients on the trainable variables of
