@@ -44,6 +44,7 @@ class GNNnodeBased(BaseClass):
         self.adjoint_max_iteration = None
         self.adjoint_threshold = None
         self.adjoint_batch_normalization = None     # set_gradient_mode(..., batch_normalization='frozen')
+        self.adjoint_label_gradients = False        # set_gradient_mode(..., label_gradients=True)
         self.label_projection = 'off'       # set_label_projection
         self.train_recompute = False        # set_train_recompute
         self.wide_state = 'off'             # set_wide_state
@@ -81,7 +82,7 @@ class GNNnodeBased(BaseClass):
         self.wide_state = {v: k for k, v in _engine.WIDE_STATE_MODES.items()}[code]
 
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None, *,
-                          batch_normalization: Optional[str] = None) -> None:
+                          batch_normalization: Optional[str] = None, label_gradients: bool = False) -> None:
         """How train() differentiates the state loop.  'unrolled' (default): back-propagation through every executed body.
         'fixed_point': the gradient at the converged state (Almeida-Pineda; Scarselli et al. 2009, section III) - the inference Loop
         finds the state, ONE body is recorded there, the adjoint iteration z <- g + J^T z runs until no node's z moves by more than
@@ -92,9 +93,16 @@ class GNNnodeBased(BaseClass):
         default - and runs that layer on its MOVING statistics, as in fine-tuning: this is the map the inference Loop iterates, a per-row
         affine map.  gamma and beta train like any other array; the moving statistics of net_state are NOT updated by train() in this mode
         (net_output's are).  Dropout in net_state stays refused.
+        ``label_gradients=True`` (opt-in; False by default): the fixed-point backward pass also returns the gradient with respect to the node
+        labels (edge-based: and the arc labels) this model saw - the direct part through net_output plus (d body / d labels)^T z at the fixed
+        point.  It is what the joint steps of an LGNN ('parallel' / 'residual') hand from layer i + 1 to layer i; needs state_vect_dim > 0.
         Kept by copy() (so by LKO) and by save() / load()."""
         if mode not in ('unrolled', 'fixed_point'): raise ValueError("param <mode> not in ['unrolled', 'fixed_point']")
         if batch_normalization not in (None, 'frozen'): raise ValueError("param <batch_normalization> not in [None, 'frozen']")
+        if not isinstance(label_gradients, bool): raise ValueError('param <label_gradients> must be a bool')
+        if mode == 'fixed_point' and label_gradients and self.state_vect_dim == 0:
+            raise NotImplementedError('fixed_point label gradients need state_vect_dim > 0: with 0 the unrolled label gradient is the gradient of '
+                                      'the INITIAL state, which a fixed point does not depend on')
         if mode == 'fixed_point' and any(float(r) != 0.0 for r in self.net_state.dropout_rates()):
             raise NotImplementedError('fixed_point gradients need a net_state without Dropout and BatchNormalization: its training-mode '
                                       'forward must be the inference forward')
@@ -107,11 +115,13 @@ class GNNnodeBased(BaseClass):
         self.adjoint_max_iteration = None if max_iteration is None else int(max_iteration)
         self.adjoint_threshold = None if threshold is None else float(threshold)
         self.adjoint_batch_normalization = batch_normalization
+        self.adjoint_label_gradients = label_gradients
 
     def _gradient_config(self) -> dict:
         config = {'mode': self.gradient_mode, 'max_iteration': self.adjoint_max_iteration, 'threshold': self.adjoint_threshold}
         # (written only when set: the dicts and files of models without it are what they were)
         if self.adjoint_batch_normalization is not None: config['batch_normalization'] = self.adjoint_batch_normalization
+        if self.adjoint_label_gradients: config['label_gradients'] = True
         return config
 
     def _frozen_state_bn(self) -> bool:
@@ -129,7 +139,8 @@ class GNNnodeBased(BaseClass):
                              addressed_problem=self.addressed_problem, extra_metrics=self.extra_metrics,
                              extra_metrics_arguments=self.mt_args, state_vect_dim=self.state_vect_dim,
                              path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
-        new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, batch_normalization=self.adjoint_batch_normalization)
+        new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, batch_normalization=self.adjoint_batch_normalization,
+                              label_gradients=self.adjoint_label_gradients)
         new.set_label_projection(self.label_projection)
         new.set_train_recompute(self.train_recompute)
         new.set_wide_state(self.wide_state)
@@ -182,7 +193,7 @@ class GNNnodeBased(BaseClass):
         model = cls(net_state=nets[0], net_output=nets[1], optimizer=optz, loss_function=loss, extra_metrics=extra_metrics,
                     extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
         model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'),
-                                batch_normalization=gradient.get('batch_normalization'))
+                                batch_normalization=gradient.get('batch_normalization'), label_gradients=bool(gradient.get('label_gradients', False)))
         model.set_label_projection(projection)
         model.set_train_recompute(recompute)
         model.set_wide_state(wide_state)
@@ -230,10 +241,11 @@ class GNNnodeBased(BaseClass):
         if getattr(loop, '_impl_set', None) != self.impl:      # (gnn_loop_set_impl checks the fused path, which re-packs the weight images when the weights
             loop.set_impl(self.impl)                          #  have changed - 0.17 ms after every optimizer step; the next inference Loop packs them anyway)
             loop._impl_set = self.impl
-        gradient = (self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, self.adjoint_batch_normalization)
-        if getattr(loop, '_gradient_set', ('unrolled', None, None, None)) != gradient:
-            # (the flag belongs to the fixed-point modes; an unrolled model that carries the keyword sets the plain mode)
-            loop.set_gradient_mode(*gradient[:3], batch_normalization=gradient[3] if gradient[0] != 'unrolled' else None)
+        gradient = (self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, self.adjoint_batch_normalization, self.adjoint_label_gradients)
+        if getattr(loop, '_gradient_set', ('unrolled', None, None, None, False)) != gradient:
+            # (the flags belong to the fixed-point modes; an unrolled model that carries the keywords sets the plain mode)
+            fixed = gradient[0] != 'unrolled'
+            loop.set_gradient_mode(*gradient[:3], batch_normalization=gradient[3] if fixed else None, label_gradients=gradient[4] if fixed else False)
             loop._gradient_set = gradient
         if getattr(loop, '_projection_set', 'off') != self.label_projection:
             loop.set_label_projection(self.label_projection)

@@ -31,6 +31,7 @@ class LGNN(BaseClass):
         self.GNNS_TYPE = kinds.pop()
         self.namespace = [f'{namespace} - GNN{i}' for i in range(self.LAYERS)]
         self.training_mode = None
+        self.device_chain = True        # joint steps of an all-fixed-point stack: label gradients handed from layer to layer on the device
         for gnn, name in zip(self.gnns, self.namespace):
             gnn.namespace = [name]
             gnn.path_writer = f'{self.path_writer}{name}/'
@@ -53,12 +54,14 @@ class LGNN(BaseClass):
         return all(gnn.train_recompute for gnn in self.gnns)
 
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None, *,
-                          batch_normalization: Optional[str] = None) -> None:
-        """GNNnodeBased.set_gradient_mode for every layer (``batch_normalization``: forwarded to them).  'serial' training runs the layers'
+                          batch_normalization: Optional[str] = None, label_gradients: bool = False) -> None:
+        """GNNnodeBased.set_gradient_mode for every layer (``batch_normalization`` / ``label_gradients``: forwarded to them).  'serial' training runs the layers'
         own steps and works in both modes; the joint
-        steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' does not return:
-        they raise NotImplementedError while any layer is in that mode."""
-        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold, batch_normalization=batch_normalization)
+        steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' returns only with
+        ``label_gradients=True``: they raise NotImplementedError while any layer is in that mode without it.  A stack may mix unrolled and
+        fixed-point layers (set the layers' modes one by one).  When every layer is fixed-point the backward passes hand the label gradients
+        on inside the device (attribute ``device_chain``, default True; False: through host arrays, the same bits)."""
+        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold, batch_normalization=batch_normalization, label_gradients=label_gradients)
 
     def copy(self, *, path_writer: str = '', namespace: str = '', copy_weights: bool = True) -> 'LGNN':
         optimizer = self.optimizer
@@ -241,14 +244,18 @@ class LGNN(BaseClass):
         of every layer (``gnn_loop_train_forward``), loss = mean of the per-layer losses ('parallel') or loss of the mean
         output ('residual'), then the backward passes from the last layer to the first (``gnn_loop_train_backward``); layer
         i also receives the gradient that reaches it through the labels of layer i + 1 (update_graph, LGNN.py:227-260).
+        Layers in gradient mode 'fixed_point' need ``label_gradients`` (set_gradient_mode); their net_state gradients are not divided by k
+        under ``mean``, and the result then carries ``adjoint_iterations`` / ``adjoint_converged`` per layer (None for an unrolled layer).
         ``state0`` / ``masks_*``: optional per-layer lists (tests inject them)."""
         from GNN import losses, _engine
         edge_based = self.GNNS_TYPE == GNNedgeBased
         if self.training_mode not in ('parallel', 'residual'):
             raise ValueError("training_step is the joint step of training_mode 'parallel' / 'residual'")
-        if any(gnn.gradient_mode != 'unrolled' for gnn in self.gnns):
+        fixed = [gnn.gradient_mode != 'unrolled' for gnn in self.gnns]
+        if any(f and not gnn.adjoint_label_gradients for f, gnn in zip(fixed, self.gnns)):
             raise NotImplementedError(f"training_mode '{self.training_mode}' needs the unrolled gradient: a layer in gradient mode 'fixed_point' "
-                                      f"returns no gradient for its labels (use training_mode 'serial', or set_gradient_mode('unrolled'))")
+                                      f"returns no gradient for its labels (use training_mode 'serial', set_gradient_mode('unrolled'), or "
+                                      f"set_gradient_mode('fixed_point', label_gradients=True))")
         if isinstance(g, GraphObject): g = GraphTensor.fromGraphObject(g)
         if self.optimizer is None or not hasattr(self.optimizer, 'apply_gradients'):
             raise TypeError('train() needs an optimizer with apply_gradients, e.g. GNN.optimizers.Adam()')
@@ -321,8 +328,19 @@ class LGNN(BaseClass):
         ng = np.asarray(g.NodeGraph, dtype=np.float32) if graph_based else None
         results = [None] * L
         d_state_extra = d_out_extra = None
+        # every layer fixed-point with label gradients: layer i reads what layer i + 1 kept on the device (gnn_loop_train_backward_chained)
+        device_chain = bool(getattr(self, 'device_chain', True)) and all(fixed)
         for idx in reversed(range(L)):
             d_nodes_out = ng @ d_outs[idx] if graph_based else d_outs[idx]
+            if device_chain:
+                above = idx < L - 1
+                # kept: what layer idx - 1 will read - d_nodes for its state and for node- / graph-based outputs, d_arc_labels for edge-based outputs
+                keep = 0
+                if idx > 0 and (self.get_state or (self.get_output and not edge_based)): keep |= _engine.KEEP_D_NODES
+                if idx > 0 and self.get_output and edge_based: keep |= _engine.KEEP_D_ARC_LABELS
+                results[idx] = loops[idx].train_backward_chained(d_nodes_out, loops[idx + 1] if above else None, above and self.get_state,
+                                                                 above and self.get_output, keep_label_gradients=keep)
+                continue
             if d_out_extra is not None: d_nodes_out = d_nodes_out + d_out_extra
             chain = idx > 0
             res = results[idx] = loops[idx].train_backward(d_nodes_out, d_state_extra,
@@ -336,13 +354,18 @@ class LGNN(BaseClass):
                     c += prev.Ds
                 if self.get_output:     # the previous output sits on the arc labels of an edge-based layer, else on the node labels
                     d_out_extra = res['d_arcs'][mask, ALb:ALb + prev.T] if edge_based else res['d_nodes'][mask, c:c + prev.T]
+        adjoint = {}
+        if any(fixed):      # per layer; None for an unrolled layer of a mixed stack
+            infos = [loop.adjoint_info() if f else None for loop, f in zip(loops, fixed)]
+            adjoint = dict(adjoint_iterations=[i and i['iterations'] for i in infos], adjoint_converged=[i and i['converged'] for i in infos])
         # ---- update: net_state gradients / k when mean (GNN_BaseClass.py:241); one optimizer over all layers (:244-247) ----
         # Device-side update (gnn_loop_optimizer_step per layer: gradients, weights and optimizer slots stay in HBM) when nothing of
         # it lives on the host: an optimizer that knows the engine's update rules and regularizers the device knows (above)
         if on_device:
             kind_o, hyper = self.optimizer.device_step_args()           # one optimizer step over all layers (reference :244-247)
             clipvalue, clipnorm, global_clipnorm = self.optimizer.device_clip_args()
-            scales = [(1.0 / k) if (mean and k) else 1.0 for k in K]
+            # (a fixed-point layer's net_state gradients are one pass at the converged state, no sum over k bodies: nothing to average)
+            scales = [(1.0 / k) if (mean and k and not f) else 1.0 for k, f in zip(K, fixed)]
             for loop in loops: loop.set_clipping(clipvalue, clipnorm, 0.0)     # (the global norm spans the layers: it is taken here)
             grad_scale = None
             if global_clipnorm or regularizers.any_regularizer(self.get_dense_layers()):
@@ -361,7 +384,7 @@ class LGNN(BaseClass):
                 gnn.net_state.mark_device_newer()
                 gnn.net_output.mark_device_newer()
             self.optimizer.device_step_done()
-            return dict(loss=loss, k=K, grads_state=[r['grads_state'] for r in results], grads_output=[r['grads_output'] for r in results], outs=outs)
+            return dict(loss=loss, k=K, grads_state=[r['grads_state'] for r in results], grads_output=[r['grads_output'] for r in results], outs=outs, **adjoint)
         for gnn, r in zip(self.gnns, results):     # regularizer terms of the taped loss (reference GNN_BaseClass.py:223-235)
             for net, key in ((gnn.net_state, 'grads_state'), (gnn.net_output, 'grads_output')):
                 pen, rg = regularizers.penalty_and_gradients(net.dense_layers)
@@ -369,7 +392,7 @@ class LGNN(BaseClass):
                 for li, (gk, gb) in enumerate(rg):
                     if gk is not None: r[key][2 * li] = r[key][2 * li] + gk
                     if gb is not None: r[key][2 * li + 1] = r[key][2 * li + 1] + gb
-        gs = [[a / k for a in r['grads_state']] if (mean and k) else r['grads_state'] for r, k in zip(results, K)]
+        gs = [[a / k for a in r['grads_state']] if (mean and k and not f) else r['grads_state'] for r, k, f in zip(results, K, fixed)]
         go = [r['grads_output'] for r in results]
         ws, wo = self.trainable_variables()
         dW = [a for layer in gs + go for a in layer]
@@ -382,6 +405,7 @@ class LGNN(BaseClass):
             net.set_trainable(new[pos:pos + n])
             pos += n
         for gnn, r, loop in zip(self.gnns, results, loops):
-            gnn.net_state.update_moving_statistics(r['bn_batch_state'])
+            # (a frozen BatchNormalization took no batch statistics: its moving statistics stay)
+            if not gnn._frozen_state_bn(): gnn.net_state.update_moving_statistics(r['bn_batch_state'])
             if loop.n_masked: gnn.net_output.update_moving_statistics(r['bn_batch_output'])
-        return dict(loss=loss, k=K, grads_state=[r['grads_state'] for r in results], grads_output=go, outs=outs)
+        return dict(loss=loss, k=K, grads_state=[r['grads_state'] for r in results], grads_output=go, outs=outs, **adjoint)

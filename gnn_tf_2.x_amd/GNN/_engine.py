@@ -24,7 +24,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_persistent', 'gnn_train_persistent_form', 'gnn_loop_train_info',
            'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
-           'gnn_loop_set_gradient_mode_ex', 'gnn_adjoint_form_ex', 'gnn_loop_adjoint_z',
+           'gnn_loop_set_gradient_mode_ex', 'gnn_adjoint_form_ex', 'gnn_loop_adjoint_z', 'gnn_loop_train_backward_chained',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_gather_program_compact', 'gnn_graph_gather_program_format', 'gnn_graph_set_program_entries', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -185,10 +185,16 @@ ADJOINT_REFUSALS = {0: None, 1: 'batch_normalization', 2: 'dropout'}
 ADJOINT_FROZEN_BN = 1           # GNN_ADJOINT_FROZEN_BN of include/gnn_hip.h (gnn_loop_set_gradient_mode_ex, gnn_adjoint_form_ex)
 
 
-def adjoint_flags(batch_normalization) -> int:
-    """The flags of gnn_loop_set_gradient_mode_ex for the keyword ``batch_normalization`` of the Python layers: None or 'frozen'."""
+ADJOINT_LABEL_GRADIENTS = 2     # GNN_ADJOINT_LABEL_GRADIENTS
+KEEP_D_NODES, KEEP_D_ARC_LABELS = 1, 2      # GNN_KEEP_D_NODES, GNN_KEEP_D_ARC_LABELS (gnn_loop_train_backward_chained)
+
+
+def adjoint_flags(batch_normalization, label_gradients: bool = False) -> int:
+    """The flags of gnn_loop_set_gradient_mode_ex for the keywords ``batch_normalization`` (None or 'frozen') and ``label_gradients`` (a bool)
+    of the Python layers."""
     if batch_normalization not in (None, 'frozen'): raise ValueError("param <batch_normalization> not in [None, 'frozen']")
-    return ADJOINT_FROZEN_BN if batch_normalization == 'frozen' else 0
+    if not isinstance(label_gradients, (bool, np.bool_)): raise ValueError('param <label_gradients> must be a bool')
+    return (ADJOINT_FROZEN_BN if batch_normalization == 'frozen' else 0) | (ADJOINT_LABEL_GRADIENTS if label_gradients else 0)
 NARROW_REFUSALS = {0: None, 3: 'layers', 4: 'width', 5: 'concat', 6: 'rows', 7: 'softmax'}      # why the one-launch iteration of narrow nets is not taken
 
 
@@ -807,9 +813,9 @@ class Loop:
         self._train_nets = (net_state, net_output, int(k.value))
         return float(k.value), out
 
-    def train_backward(self, d_out_nodes, d_state_extra=None, want_d_nodes: bool = False, want_d_arcs: bool = False):
-        """gnn_loop_train_backward: dict(grads_state, grads_output (raw sums over the iterations), bn_batch_state,
-        bn_batch_output, d_nodes [N, NL] or None)."""
+    def _backward_buffers(self, d_out_nodes):
+        """What both backward calls share: (d_out [n_masked, T], flat gradient buffers of both nets, batch-statistics buffers, `finish`), where
+        finish(d_nodes, d_arcs) splits the filled buffers into the result dict."""
         net_state, net_output, kk = self._train_nets
         if getattr(self, '_gradient_mode', 0) != 0: kk = 0       # (fixed-point modes: no batch statistics of net_state, as in train_step)
         shp_s, shp_o = self._grad_shapes(net_state), self._grad_shapes(net_output)
@@ -819,14 +825,6 @@ class Loop:
         bno = np.zeros((2, int(net_output.dims[-1])), np.float32)
         d_out = _f32(d_out_nodes)
         if d_out.shape != (self.n_masked, self.T): raise ValueError(f'd_out_nodes shape {d_out.shape} != {(self.n_masked, self.T)}')
-        dse = None
-        if d_state_extra is not None:
-            dse = _f32(d_state_extra)
-            if dse.shape != (self.n_rows, self.Ds): raise ValueError(f'd_state_extra shape {dse.shape} != {(self.n_rows, self.Ds)}')
-        dims = self.graph.dims()
-        dn = np.zeros((self.n_rows, dims['NL']), np.float32) if want_d_nodes else None
-        da = np.zeros((dims['n_arcs'], dims['AL']), np.float32) if want_d_arcs else None
-        _check(lib().gnn_loop_train_backward(self._h, _fp(d_out), _fp(dse), _fp(gs), _fp(go), _fp(bns), _fp(bno), _fp(dn), _fp(da)))
 
         def split(flat, shp):
             out, off = [], 0
@@ -836,7 +834,37 @@ class Loop:
                 off += cnt
             return out
 
-        return dict(grads_state=split(gs, shp_s), grads_output=split(go, shp_o), bn_batch_state=bns[:kk], bn_batch_output=bno, d_nodes=dn, d_arcs=da)
+        def finish(dn, da):
+            return dict(grads_state=split(gs, shp_s), grads_output=split(go, shp_o), bn_batch_state=bns[:kk], bn_batch_output=bno, d_nodes=dn, d_arcs=da)
+
+        return d_out, gs, go, bns, bno, finish
+
+    def train_backward(self, d_out_nodes, d_state_extra=None, want_d_nodes: bool = False, want_d_arcs: bool = False):
+        """gnn_loop_train_backward: dict(grads_state, grads_output (raw sums over the iterations), bn_batch_state,
+        bn_batch_output, d_nodes [N, NL] or None)."""
+        d_out, gs, go, bns, bno, finish = self._backward_buffers(d_out_nodes)
+        dse = None
+        if d_state_extra is not None:
+            dse = _f32(d_state_extra)
+            if dse.shape != (self.n_rows, self.Ds): raise ValueError(f'd_state_extra shape {dse.shape} != {(self.n_rows, self.Ds)}')
+        dims = self.graph.dims()
+        dn = np.zeros((self.n_rows, dims['NL']), np.float32) if want_d_nodes else None
+        da = np.zeros((dims['n_arcs'], dims['AL']), np.float32) if want_d_arcs else None
+        _check(lib().gnn_loop_train_backward(self._h, _fp(d_out), _fp(dse), _fp(gs), _fp(go), _fp(bns), _fp(bno), _fp(dn), _fp(da)))
+        return finish(dn, da)
+
+    def train_backward_chained(self, d_out_nodes, next_loop=None, get_state: bool = False, get_output: bool = False, keep_label_gradients=False):
+        """gnn_loop_train_backward_chained: train_backward() for a stack whose label gradients stay on the device.  keep_label_gradients: what is
+        computed and stays in this loop's training scratch until its next train_forward() - KEEP_D_NODES, KEEP_D_ARC_LABELS (edge-based loops),
+        their sum, or True for both; name what the layer below will read.  next_loop: the loop of the layer above, whose last backward pass kept
+        them - its columns with this loop's state (get_state) take the place of d_state_extra, its masked rows with this loop's outputs
+        (get_output) are added to d_out_nodes.  Bit-identical to chaining two train_backward() calls through host arrays.  Returns the dict of
+        train_backward() with d_nodes = d_arcs = None."""
+        keep = (KEEP_D_NODES | KEEP_D_ARC_LABELS) if keep_label_gradients is True else int(keep_label_gradients)
+        d_out, gs, go, bns, bno, finish = self._backward_buffers(d_out_nodes)
+        _check(lib().gnn_loop_train_backward_chained(self._h, _fp(d_out), next_loop._h if next_loop is not None else None, C.c_int(bool(get_state)),
+                                                     C.c_int(bool(get_output)), _fp(gs), _fp(go), _fp(bns), _fp(bno), C.c_int(keep)))
+        return finish(None, None)
 
     def train_forms(self, net: int = 0) -> dict:
         """gnn_loop_train_forms: what the last train_forward() / train_step() decided for net_state (0) or net_output (1), as train_forms()."""
@@ -912,17 +940,19 @@ class Loop:
         _check(lib().gnn_loop_train_recompute_info(self._h, _ip(out)))
         return dict(state_only=bool(out[0]), replayed=int(out[1]), cacheless_chain=int(out[2]))
 
-    def set_gradient_mode(self, mode, max_iteration=None, threshold=None, *, batch_normalization=None) -> int:
+    def set_gradient_mode(self, mode, max_iteration=None, threshold=None, *, batch_normalization=None, label_gradients: bool = False) -> int:
         """gnn_loop_set_gradient_mode: 'unrolled' / 0 (default: back-propagation through the executed bodies) or 'fixed_point' / 1 (the
         gradient at the converged state: inference Loop, one recorded body, adjoint iteration z <- g + J^T z, one weight-gradient pass).
         max_iteration / threshold of the adjoint iteration: None = the loop's own.  In fixed-point mode grads_state is NOT a sum over bodies
         (never divide it by k), train_step() reports adjoint_iterations / adjoint_converged, and net_state must have neither Dropout nor
         BatchNormalization (NotImplementedError).  'fixed_point_chain' / 2: fixed point without the one-launch iteration of narrow nets (A/B runs, tests).
         batch_normalization='frozen' (gnn_loop_set_gradient_mode_ex with GNN_ADJOINT_FROZEN_BN): a net_state that ends in BatchNormalization is
-        accepted, on its moving statistics, which the step leaves untouched; gamma and beta train.  None: gnn_loop_set_gradient_mode."""
+        accepted, on its moving statistics, which the step leaves untouched; gamma and beta train.  None: gnn_loop_set_gradient_mode.
+        label_gradients=True (GNN_ADJOINT_LABEL_GRADIENTS): train_backward(want_d_nodes / want_d_arcs) and train_backward_chained(keep_label_gradients=...) work
+        in the fixed-point modes - the direct part plus the label columns of the recorded body's d concat for z_final; refused with state_vect_dim 0."""
         code = {'unrolled': 0, 'fixed_point': 1, 'fixed_point_chain': 2, 0: 0, 1: 1, 2: 2}.get(mode)
         if code is None: raise ValueError("gradient mode must be 'unrolled' or 'fixed_point'")
-        flags = adjoint_flags(batch_normalization)
+        flags = adjoint_flags(batch_normalization, label_gradients)
         used = C.c_int(0)
         if flags:
             _check(lib().gnn_loop_set_gradient_mode_ex(self._h, C.c_int(code), C.c_int(int(max_iteration) if max_iteration else 0),

@@ -335,7 +335,8 @@ struct gnn_train_settings {
     int k_hint = 0;               // bodies the last training forward of this loop ran (the next one enqueues that many + 1 before it looks at the gates)
     // gradient mode (gnn_loop_set_gradient_mode): 0 the unrolled gradient, 1 the gradient at the fixed point (gnn_train_adjoint.hip); max_iter 0 /
     // thr < 0: the loop's own; iterations, converged, gather: what the last backward pass of mode 1 ran (gnn_loop_adjoint_info)
-    // flags (gnn_loop_set_gradient_mode_ex): GNN_ADJOINT_FROZEN_BN - a net_state that ends in BatchNormalization is accepted, on its moving statistics
+    // flags (gnn_loop_set_gradient_mode_ex): GNN_ADJOINT_FROZEN_BN - a net_state that ends in BatchNormalization is accepted, on its moving statistics;
+    // GNN_ADJOINT_LABEL_GRADIENTS - the backward pass of modes 1 and 2 returns d_nodes / d_arc_labels
     struct { int mode = 0, max_iter = 0; float thr = -1.0f; int iterations = 0, converged = 0, gather = 0, flags = 0; } adjoint;
     // recomputation of the bodies' activations (gnn_loop_set_train_recompute): 0 off, 1 on, 2 on with the caching kernels in the first pass
     int recompute = 0;

@@ -415,6 +415,10 @@ struct GNN_INTERNAL gnn_train_ctx {
     int replayed = 0;             // ... bodies rebuilt by the backward pass
     int cacheless_chain = 0;      // ... the first pass launched the cache-less three-layer chain (else the ordinary kernels on rewound scratch)
     float *adjoint_z = nullptr;   // gradient modes 1 and 2, behind the backward pass: z_final [N, Ds] (gnn_loop_adjoint_z)
+    // label gradients the last backward pass kept on the device (gnn_loop_train_backward_chained with keep_label_gradients): d loss / d node
+    // labels [N, NL] and / or, edge-based, d loss / d arc labels [E, AL] in original arc order (NULL: not asked for); scratch of this step,
+    // alive until the next forward
+    float *kept_d_nodes = nullptr, *kept_d_arcs = nullptr;
     bool fixed_point = false;     // gradient mode 1: `caches` holds ONE recorded body at the converged state `state` (k bodies of the inference Loop led there)
     bool persistent = false;      // the bodies ran in the persistent launch (k_train_small) ...
     int workgroups = 0, barriers = 0;     // ... of that many workgroups, with that many grid barriers per body

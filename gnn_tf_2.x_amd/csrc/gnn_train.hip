@@ -385,6 +385,17 @@ __global__ void k_add_cols(int64_t n, int width, const float *d_inp, int in_s, i
     acc[t] += d_inp[r * in_s + col0 + c];
 }
 
+// out[q, c] += src[rows[q], col0 + c]   (a chained backward pass: the rows of the layer above's label gradient that carry this loop's masked
+// outputs, added onto d loss / d out_nodes; one thread per element of out)
+__global__ void k_add_masked_cols(int64_t m, int width, const int32_t *__restrict__ rows, const float *__restrict__ src, int stride, int col0, float *out)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m * width) return;
+    const int64_t q = t / width;
+    const int c = (int)(t - q * width);
+    out[t] += src[(int64_t)rows[q] * stride + col0 + c];
+}
+
 // d arc labels, ORIGINAL arc order.  (a) label columns of the per-arc readout rows: row m <-> arc position rows[m];
 // (b) ArcNode^T . arc labels: entry q of destination dst carries arc arc_id[q] with weight arc_w[q].  Targets are unique.
 __global__ void k_arc_grad_readout(int64_t m, int AL, const int32_t *rows, const float *d_feats, int we, int col0, float *d_arcs)
@@ -1012,7 +1023,8 @@ extern "C" int gnn_loop_train_forward(gnn_loop *l, const int32_t *src_indptr, co
 // a time on scratch that every iteration reuses; the host then reads the chunk's gates in one wait.  Iteration t finds gate t - 1 of its
 // chunk on the device: behind a closed gate it hands z on unchanged and raises nothing, so the first closed gate gives the count and the
 // last buffer written holds z of that count - nothing is recomputed.
-static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, float *g_state)
+// *u_out = d concat [N, in_s] of the weight-gradient pass: its label columns are (d body / d labels)^T z_final (GNN_ADJOINT_LABEL_GRADIENTS).
+static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, float *g_state, float **u_out)
 {
     gnn_train_arena *arena = cx->buf.arena;
     Buf &buf = cx->buf;
@@ -1093,17 +1105,43 @@ static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, floa
     arena->rewind(mark);
     cx->adjoint_z = adj.iterations == 0 ? g_state : zb[adj.iterations & 1];
     // `work` holds z_final (the last gather wrote it beside its z buffer; without an iteration it is the copy of g)
-    float *u = nullptr;
-    return net_backward(st, buf, ns, cx->caches[0], work, &u, nullptr, nullptr, 0, true);
+    return net_backward(st, buf, ns, cx->caches[0], work, u_out, nullptr, nullptr, 0, true);
 }
+
+// gnn_loop_train_backward_chained: the label gradients stay on the device.  keep_nodes / keep_arcs: compute d_nodes / d_arc_labels and leave them
+// with the context; next: the loop of the layer above, whose kept label gradients carry this loop's extra state gradient (get_state) and extra
+// output gradient (get_output)
+struct Chain { gnn_loop *next; bool get_state, get_output, keep_nodes, keep_arcs; };
 
 // d_out_dev: d loss / d out_nodes already on the device (gnn_loop_train_step), else d_out_host is uploaded
 static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host, const float *d_state_extra, float *grads_state,
-                          float *grads_output, float *bn_batch_state, float *bn_batch_output, float *d_nodes_host, float *d_arcs_host, bool sync)
+                          float *grads_output, float *bn_batch_state, float *bn_batch_output, float *d_nodes_host, float *d_arcs_host, bool sync,
+                          const Chain *chain = nullptr)
 {
     ARGCHK(l && grads_state && grads_output, "bad arguments");
     gnn_train_ctx *cx = l->train_ctx;
     if (!cx || cx->backward_done) return gnn_fail(GNN_ERR_STATE, "gnn_loop_train_forward has not been called (one backward per forward)");
+    const bool keep_nodes = chain && chain->keep_nodes, keep_arcs = chain && chain->keep_arcs && l->edge_mode, keep = keep_nodes || keep_arcs;
+    const gnn_train_ctx *nx = chain && chain->next && (chain->get_state || chain->get_output) ? chain->next->train_ctx : nullptr;
+    int NLb = 0, ALb = 0;          // the label widths of the base graph: next's labels are [base | this loop's state? | this loop's outputs?]
+    if (chain && chain->next && (chain->get_state || chain->get_output)) {
+        const gnn_loop *nl = chain->next;
+        ARGCHK(l->world == 1 && nl->world == 1, "a chained backward pass is single-GPU");
+        ARGCHK(nl != l && nl->device == l->device, "chained backward: next must be another loop on the same device");
+        if (!nx || !nx->backward_done) return gnn_fail(GNN_ERR_STATE, "chained backward: next has no finished backward pass");
+        ARGCHK(nl->g->n_rows == l->g->n_rows && nl->edge_mode == l->edge_mode, "chained backward: next runs on %lld rows, this loop on %lld (or one is edge-based, the other not)",
+               (long long)nl->g->n_rows, (long long)l->g->n_rows);
+        const bool on_arcs = chain->get_output && l->edge_mode;
+        NLb = nl->g->NL - (chain->get_state ? l->Ds : 0) - (chain->get_output && !on_arcs ? l->T : 0);
+        ALb = nl->g->AL - (on_arcs ? l->T : 0);
+        ARGCHK(NLb >= 0 && ALb >= 0, "chained backward: next's labels (%d node, %d arc columns) do not hold this loop's state / outputs", nl->g->NL, nl->g->AL);
+        // (the sizes of the masks: the rows themselves are the caller's - gnn_graph_update_labels put this loop's outputs on ITS masked rows)
+        ARGCHK(!on_arcs || (nl->g->E == l->g->E && nl->n_edge_masked == l->n_edge_masked), "chained backward: next has another number of arcs or of masked arcs");
+        ARGCHK(!chain->get_output || on_arcs || nl->g->n_masked == l->g->n_masked, "chained backward: next has another number of masked rows");
+        if ((chain->get_state || (chain->get_output && !on_arcs)) && !nx->kept_d_nodes)
+            return gnn_fail(GNN_ERR_STATE, "chained backward: next's last backward pass kept no d_nodes (keep_label_gradients)");
+        if (on_arcs && !nx->kept_d_arcs) return gnn_fail(GNN_ERR_STATE, "chained backward: next's last backward pass kept no d_arc_labels (keep_label_gradients)");
+    }
     // Sharded backward (round 3; after a sharded gnn_loop_train_forward that was given the by-source adjacency of the owned rows): per
     // body the gradient of the aggregated-state columns is all-gathered like the state in the forward pass and every rank adds up, for
     // its own rows, what its out-arcs carry back; BatchNormalization's sums are those of all ranks; at the end the ranks' shares of the
@@ -1114,8 +1152,13 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
         ARGCHK(cx->d_sip, "backward on shards: gnn_loop_train_forward needs the by-source adjacency of the owned rows (src_indptr / src_dst / src_w)");
         ARGCHK(!d_state_extra && !d_nodes_host && !d_arcs_host && !l->edge_mode, "backward on shards: no extra state gradient, label or arc-label gradients, node- or graph-based only");
     }
-    if (cx->fixed_point && (d_nodes_host || d_arcs_host))
-        return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient returns no d_nodes / d_arc_labels (the joint LGNN modes need the unrolled gradient)");
+    if (cx->fixed_point && (d_nodes_host || d_arcs_host || keep)) {
+        if (!(l->train.adjoint.flags & GNN_ADJOINT_LABEL_GRADIENTS))
+            return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient returns no d_nodes / d_arc_labels (the joint LGNN modes need the unrolled gradient)");
+        if (!l->D)
+            return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient returns no d_nodes / d_arc_labels with state_vect_dim == 0: the unrolled d_nodes is the "
+                                                 "gradient of the INITIAL state there, which a fixed point does not depend on");
+    }
     gnn_graph *g = l->g;
     const int64_t N = g->n_rows, M = l->edge_mode ? l->n_edge_masked : g->n_masked;
     // (mode 1: cx->k bodies of the inference Loop led to the state; the backward pass below walks none of them)
@@ -1130,11 +1173,21 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
     float *d_out = d_out_dev, *d_feats = nullptr, *d_state = nullptr, *tmp = nullptr, *d_nodes = nullptr, *via = nullptr;
     if ((!d_out && (rc = buf.get(&d_out, (size_t)M * T))) || (rc = buf.get(&d_state, (size_t)N * Ds))) return rc;
     if (!d_out_dev && M) HIPCHK(hipMemcpyAsync(d_out, d_out_host, sizeof(float) * (size_t)M * T, hipMemcpyHostToDevice, st));
+    // chained: the extra output gradient from the label gradient the layer above kept (one float32 addition per element, as the host makes it)
+    if (nx && chain->get_output && M) {
+        if (l->edge_mode) hipLaunchKernelGGL(k_add_masked_cols, cdiv(M * T, 256), 256, 0, st, M, T, l->edge_rows, nx->kept_d_arcs, chain->next->g->AL, ALb, d_out);
+        else hipLaunchKernelGGL(k_add_masked_cols, cdiv(M * T, 256), 256, 0, st, M, T, g->sh->masked_rows, nx->kept_d_nodes, chain->next->g->NL,
+                                NLb + (chain->get_state ? Ds : 0), d_out);
+        HIPCHK(hipGetLastError());
+    }
     if ((rc = net_backward(st, buf, no_, cx->co, d_out, &d_feats, nullptr, comm, cx->M_global))) return rc;
-    if (d_state_extra) { if (N) HIPCHK(hipMemcpyAsync(d_state, d_state_extra, sizeof(float) * (size_t)N * Ds, hipMemcpyHostToDevice, st)); }
+    const bool chained_state = nx && chain->get_state;         // ... and the extra state gradient, in the place of an uploaded d_state_extra
+    const bool state_extra = d_state_extra || chained_state;
+    if (chained_state) { if (N && (rc = gnn_launch_copy_cols(st, N, Ds, nx->kept_d_nodes + NLb, chain->next->g->NL, d_state, Ds, nullptr, 1))) return rc; }
+    else if (d_state_extra) { if (N) HIPCHK(hipMemcpyAsync(d_state, d_state_extra, sizeof(float) * (size_t)N * Ds, hipMemcpyHostToDevice, st)); }
     else HIPCHK(hipMemsetAsync(d_state, 0, sizeof(float) * std::max<size_t>(1, (size_t)N * Ds), st));
-    const bool want_nodes = d_nodes_host != nullptr;
-    const bool want_arcs = d_arcs_host != nullptr && g->AL > 0;
+    const bool want_nodes = d_nodes_host != nullptr || keep_nodes;
+    const bool want_arcs = (d_arcs_host != nullptr || keep_arcs) && g->AL > 0;
     const int AL = g->AL, c_agga = c_aggn + NLc;
     float *d_arcs = nullptr, *d_aa = nullptr;
     if (want_arcs) {
@@ -1154,7 +1207,7 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
             HIPCHK(hipGetLastError());
         }
     } else if (M) {
-        if (d_state_extra) {        // extra + scattered rows: scatter into a zero buffer, then add
+        if (state_extra) {          // extra + scattered rows: scatter into a zero buffer, then add
             if ((rc = buf.get(&tmp, (size_t)N * Ds))) return rc;
             HIPCHK(hipMemsetAsync(tmp, 0, sizeof(float) * (size_t)N * Ds, st));
             hipLaunchKernelGGL(k_scatter_rows, cdiv(M * Ds, 256), 256, 0, st, M, g->sh->masked_rows, d_feats, wf, Ds, tmp);
@@ -1169,7 +1222,25 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
             HIPCHK(hipGetLastError());
         }
     }
-    if (cx->fixed_point && (rc = adjoint_backward(l, cx, st, d_state))) return rc;
+    // what one body's d concat gives the labels: the aggregated-arc columns (ArcNode^T follows at the end), the own node columns and the
+    // aggregated-node columns over the adjacency by source (GNN.py:228, :263).  Mode 0: every body; modes 1 and 2: the recorded body, once
+    auto label_terms = [&](const float *d_inp) -> int {
+        if (want_arcs && N) {
+            hipLaunchKernelGGL(k_add_cols, cdiv(N * AL, 256), 256, 0, st, N, AL, d_inp, in_s, c_agga, d_aa);
+            HIPCHK(hipGetLastError());
+        }
+        if (want_nodes && l->D && N) {
+            int rc2;
+            if ((rc2 = gnn_launch_spmm(st, N, cx->d_sip, cx->d_sdst, cx->d_sw, d_inp + c_aggn, NL, in_s, via, NL, nullptr, 1))) return rc2;
+            hipLaunchKernelGGL(k_nodes_grad, cdiv(N * NL, 256), 256, 0, st, N, NL, d_inp, in_s, c_nodes, via, d_nodes);
+            HIPCHK(hipGetLastError());
+        }
+        return GNN_OK;
+    };
+    if (cx->fixed_point) {
+        float *u = nullptr;         // d concat of the weight-gradient pass with z_final: (d body / d labels)^T z_final in its label columns
+        if ((rc = adjoint_backward(l, cx, st, d_state, &u)) || (rc = label_terms(u))) return rc;
+    }
     // Recomputing step: body `it` is rebuilt from states[it] on scratch that every body reuses, immediately before its backward pass - the same
     // kernels on the same inputs in the same fixed order, so the rebuilt cache holds the first pass's bits.  All that outlives a body's
     // rewind is allocated here, ahead of the mark: the two d_prev buffers used in turn, net_state's chunk partials (Net::part is remembered
@@ -1215,15 +1286,7 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
             if ((rc = net_backward(st, buf, ns, cx->caches[it], d_state, &d_inp, &job, nullptr, 0))) return rc;
         }
         d_state = d_prev;
-        if (want_arcs && N) {
-            hipLaunchKernelGGL(k_add_cols, cdiv(N * AL, 256), 256, 0, st, N, AL, d_inp, in_s, c_agga, d_aa);
-            HIPCHK(hipGetLastError());
-        }
-        if (want_nodes && l->D && N) {    // labels enter each body directly and through aggregated_nodes (GNN.py:228, :263)
-            if ((rc = gnn_launch_spmm(st, N, cx->d_sip, cx->d_sdst, cx->d_sw, d_inp + c_aggn, NL, in_s, via, NL, nullptr, 1))) return rc;
-            hipLaunchKernelGGL(k_nodes_grad, cdiv(N * NL, 256), 256, 0, st, N, NL, d_inp, in_s, c_nodes, via, d_nodes);
-            HIPCHK(hipGetLastError());
-        }
+        if ((rc = label_terms(d_inp))) return rc;
     }
     if (sharded) {          // the ranks' shares of the weight gradients -> their sum in rank order, on every rank (and in place: gnn_loop_optimizer_step reads it)
         for (const LoopNet &n : loop_nets(l, cx)) {
@@ -1245,10 +1308,12 @@ static int train_backward(gnn_loop *l, float *d_out_dev, const float *d_out_host
         if (M) hipLaunchKernelGGL(k_arc_grad_readout, cdiv(M * AL, 256), 256, 0, st, M, AL, l->edge_rows, d_feats, wf, 2 * (Ds + NLc), d_arcs);
         hipLaunchKernelGGL(k_arc_grad_agg, cdiv(g->E * AL, 256), 256, 0, st, g->E, AL, l->edge_dst, g->sh->arc_id, g->sh->arc_w, d_aa, d_arcs);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(d_arcs_host, d_arcs, sizeof(float) * (size_t)g->E * AL, hipMemcpyDeviceToHost, st));
+        if (d_arcs_host) HIPCHK(hipMemcpyAsync(d_arcs_host, d_arcs, sizeof(float) * (size_t)g->E * AL, hipMemcpyDeviceToHost, st));
     }
-    if (want_nodes && N)        // D == 0: state_0 = nodes (GNN.py:265), so the gradient of the initial state IS the label gradient
+    if (d_nodes_host && N)      // D == 0: state_0 = nodes (GNN.py:265), so the gradient of the initial state IS the label gradient
         HIPCHK(hipMemcpyAsync(d_nodes_host, l->D ? d_nodes : d_state, sizeof(float) * (size_t)N * NL, hipMemcpyDeviceToHost, st));
+    if (keep_nodes) cx->kept_d_nodes = l->D ? d_nodes : d_state;
+    if (keep_arcs && want_arcs) cx->kept_d_arcs = d_arcs;
     if (sync) HIPCHK(hipStreamSynchronize(st));
     cx->backward_done = true;
     return GNN_OK;
@@ -1260,6 +1325,16 @@ extern "C" int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, co
 {
     // the context stays (its gradients feed gnn_loop_optimizer_step) until the next forward; a second backward is refused
     return train_backward(l, nullptr, d_out_nodes, d_state_extra, grads_state, grads_output, bn_batch_state, bn_batch_output, d_nodes_host, d_arcs_host, true);
+}
+
+extern "C" int gnn_loop_train_backward_chained(gnn_loop *l, const float *d_out_nodes, gnn_loop *next, int get_state, int get_output, float *grads_state,
+                                               float *grads_output, float *bn_batch_state, float *bn_batch_output, int keep_label_gradients)
+{
+    ARGCHK(l, "loop is NULL");
+    ARGCHK(l->world == 1, "a chained backward pass is single-GPU (this loop is rank %d of %d)", l->rank, l->world);
+    ARGCHK(keep_label_gradients >= 0 && keep_label_gradients <= (GNN_KEEP_D_NODES | GNN_KEEP_D_ARC_LABELS), "keep_label_gradients: GNN_KEEP_D_NODES, GNN_KEEP_D_ARC_LABELS, both or 0");
+    const Chain chain{next, get_state != 0, get_output != 0, (keep_label_gradients & GNN_KEEP_D_NODES) != 0, (keep_label_gradients & GNN_KEEP_D_ARC_LABELS) != 0};
+    return train_backward(l, nullptr, d_out_nodes, nullptr, grads_state, grads_output, bn_batch_state, bn_batch_output, nullptr, nullptr, true, &chain);
 }
 
 // what the last training forward decided for one of the loop's nets (the context outlives the backward pass: until the next forward)

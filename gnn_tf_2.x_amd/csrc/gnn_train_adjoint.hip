@@ -267,7 +267,7 @@ int launch_adjoint_gather(hipStream_t st, const StateGradJob &job, const float *
 
 extern "C" int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out)
 {
-    ARGCHK((flags & ~GNN_ADJOINT_FROZEN_BN) == 0, "flags: GNN_ADJOINT_FROZEN_BN or 0");
+    ARGCHK((flags & ~(GNN_ADJOINT_FROZEN_BN | GNN_ADJOINT_LABEL_GRADIENTS)) == 0, "flags: GNN_ADJOINT_FROZEN_BN, GNN_ADJOINT_LABEL_GRADIENTS, both or 0");
     ARGCHK(n_layers >= 1 && n_layers <= 16 && dims && acts && rates && n_rows >= 0 && out, "bad arguments");
     gnn_mlp m;
     m.n_layers = n_layers;
@@ -303,7 +303,7 @@ extern "C" int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, 
 extern "C" int gnn_loop_set_gradient_mode_ex(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int flags, int *used)
 {
     ARGCHK(l, "loop is NULL");
-    ARGCHK((flags & ~GNN_ADJOINT_FROZEN_BN) == 0, "flags: GNN_ADJOINT_FROZEN_BN or 0");
+    ARGCHK((flags & ~(GNN_ADJOINT_FROZEN_BN | GNN_ADJOINT_LABEL_GRADIENTS)) == 0, "flags: GNN_ADJOINT_FROZEN_BN, GNN_ADJOINT_LABEL_GRADIENTS, both or 0");
     ARGCHK(mode >= 0 && mode <= 2, "gradient mode: 0 unrolled, 1 fixed point, 2 fixed point without the one-launch iteration of narrow nets");
     ARGCHK(adjoint_max_iter >= 0 && !std::isnan(adjoint_threshold), "adjoint_max_iter must be >= 0 (0: the loop's max_iter), adjoint_threshold a number (< 0: the loop's threshold)");
     if (mode && l->world > 1) return gnn_fail(GNN_ERR_UNSUPPORTED, "the fixed-point gradient is single-GPU (this loop is rank %d of %d)", l->rank, l->world);

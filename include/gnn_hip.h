@@ -220,6 +220,22 @@ int gnn_loop_train_forward(gnn_loop *l, const int32_t *src_indptr, const int32_t
 int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, const float *d_state_extra, float *grads_state,
                             float *grads_output, float *bn_batch_state, float *bn_batch_output, float *d_nodes,
                             float *d_arc_labels);
+/* gnn_loop_train_backward for a stack of loops whose label gradients stay on the device (LGNN's joint steps; every gradient mode).
+ *   keep_label_gradients   GNN_KEEP_D_NODES: d_nodes [N, NL], GNN_KEEP_D_ARC_LABELS (edge-based loops; ignored by others): d_arc_labels [n_arcs, AL] -
+ *                    what is named is computed and left in the loop's training scratch, valid until this loop's next training forward; there is
+ *                    no host copy.  A caller names what the layer below will read: d_nodes for get_state and for the outputs of a node- or
+ *                    graph-based layer, d_arc_labels for the outputs of an edge-based one; 0 computes neither.
+ *   next (or NULL)   the loop of the layer above, whose last backward pass kept its label gradients; its labels are [base labels | this loop's
+ *                    state? | this loop's scattered outputs?] (gnn_graph_update_labels).  With NLb / ALb the base widths, in front of anything else:
+ *                    get_state  != 0: d_state = next.d_nodes[:, NLb : NLb + Ds], in the place of an uploaded d_state_extra;
+ *                    get_output != 0: d_out[q] += next.d_nodes[masked row q, c : c + T], c = NLb + (get_state ? Ds : 0); edge-based loops:
+ *                                     d_out[q] += next.d_arc_labels[masked arc q, ALb : ALb + T].
+ *                    One float32 addition per element, as a host that chains the two calls makes: every result equals the host-chained one bit
+ *                    for bit.  A mismatch of device, row count, the NUMBER of masked rows / arcs or label widths between l and next is
+ *                    GNN_ERR_ARG (which rows are masked is the caller's: next's labels were filled from this loop by gnn_graph_update_labels). */
+enum { GNN_KEEP_D_NODES = 1, GNN_KEEP_D_ARC_LABELS = 2 };
+int gnn_loop_train_backward_chained(gnn_loop *l, const float *d_out_nodes, gnn_loop *next, int get_state, int get_output, float *grads_state,
+                                    float *grads_output, float *bn_batch_state, float *bn_batch_output, int keep_label_gradients);
 /* Gradient mode of a loop's training step.  mode 0 (default): back-propagation through the unrolled loop, as described above.
  * mode 1 ("fixed point"): the gradient at the converged state (Almeida-Pineda; Scarselli et al. 2009, section III).  With Ds the state width:
  *   Forward        the INFERENCE Loop runs with the loop's own settings (arithmetic, persistent or per-body form, certified gate) and gives
@@ -241,7 +257,8 @@ int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, const float *
  *                  a caller that averages (`mean`) must NOT divide them by k, and a step armed with mean != 0 applies them with scale 1.
  *   Everything behind the gradients (regularizers, clipping, optimizer kinds, net_output's moving statistics) is untouched.
  * Refused with GNN_ERR_UNSUPPORTED by the training forward / step / backward of a loop in mode 1: a net_state with BatchNormalization or any
- * Dropout rate != 0 (its training-mode forward is then not the inference forward), world > 1, and requests for d_nodes / d_arc_labels.
+ * Dropout rate != 0 (its training-mode forward is then not the inference forward), world > 1, and requests for d_nodes / d_arc_labels
+ * (without GNN_ADJOINT_LABEL_GRADIENTS, below; with state_vect_dim == 0 always).
  * No float atomics: two identical steps return identical bits.
  * Narrow nets (net_state of 1 - 3 Dense layers of at most 64 outputs, no softmax, a concat of at most 96 columns, fewer than 4,096 rows - the regime where
  * a step is bound by its launch count) run an adjoint iteration as ONE launch: a block owns 16 rows, forms their z from the previous launch's u with
@@ -259,13 +276,21 @@ int gnn_loop_train_backward(gnn_loop *l, const float *d_out_nodes, const float *
  *   Moving statistics of net_state   NOT touched: not by the armed step, gnn_loop_optimizer_step or gnn_loop_update_moving_statistics, and
  *                  bn_batch_state is left unwritten (there are no batch statistics of net_state).  net_output's are updated as in mode 0.
  * Dropout in net_state, world > 1 and d_nodes / d_arc_labels stay refused.
+ * GNN_ADJOINT_LABEL_GRADIENTS in flags (opt-in; combines with GNN_ADJOINT_FROZEN_BN): gnn_loop_train_backward of modes 1 and 2 accepts d_nodes and,
+ * for edge-based loops after gnn_graph_set_arc_order, d_arc_labels.  With p = F(p, l) the fixed point and l the labels,
+ *   d loss / d l = (the direct part through net_output / the edge readout) + (d F / d l)^T z_final,
+ * and (d F / d l)^T z_final is the label columns of the recorded body's d concat for the incoming gradient z_final - the pass that gives net_state's
+ * weight gradients - scattered as mode 0 scatters ONE body's label columns: own node columns directly, aggregated-node columns over the adjacency
+ * by source, aggregated-arc columns through ArcNode^T.  No sum over bodies.  Without the flag nothing changes.  Refused in modes 1 and 2 whatever
+ * the flags: Dropout in net_state, world > 1, and d_nodes / d_arc_labels of a loop with state_vect_dim == 0 (mode 0 returns the gradient of the
+ * INITIAL state there, which a fixed point does not depend on).
  * adjoint_max_iter = 0 / adjoint_threshold < 0: the loop's own max_iter / threshold.  *used (may be NULL) = the mode now set.
  * gnn_loop_adjoint_info: iterations and converged (0 / 1) of the last backward pass of mode 1, and the form of its gather (0: any Ds, every
  * 16th column per lane; 1: 16-byte pieces, Ds % 4 == 0 and Ds <= 64; 2: the same from the aligned rows the three-layer chain leaves; 3: inside the
  * one-launch iteration of narrow nets);
  * any pointer may be NULL. */
 int gnn_loop_set_gradient_mode(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int *used);
-enum { GNN_ADJOINT_FROZEN_BN = 1 };
+enum { GNN_ADJOINT_FROZEN_BN = 1, GNN_ADJOINT_LABEL_GRADIENTS = 2 };
 int gnn_loop_set_gradient_mode_ex(gnn_loop *l, int mode, int adjoint_max_iter, float adjoint_threshold, int flags, int *used);
 int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *converged, int *form);
 /* What an adjoint iteration of mode 1 launches for a net_state of this description (arguments as gnn_train_forms; the state width is
@@ -278,7 +303,7 @@ int gnn_loop_adjoint_info(const gnn_loop *l, int *iterations, int *converged, in
 int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int64_t n_rows, int *out);
 /* The same for a loop set with `flags` (gnn_loop_set_gradient_mode_ex): with GNN_ADJOINT_FROZEN_BN a net with has_bn != 0 is eligible (out[1] = 0)
  * and the forms are those of its Dense chain - the frozen BatchNormalization pass takes the place of the last activation's derivative pass and is
- * inside the one-launch iteration of narrow nets.  flags 0: gnn_adjoint_form. */
+ * inside the one-launch iteration of narrow nets.  GNN_ADJOINT_LABEL_GRADIENTS is accepted and changes no form.  flags 0: gnn_adjoint_form. */
 int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out);
 /* z_final [n_rows, Ds] of the last backward pass of mode 1 / 2, to host memory (test entry point; GNN_ERR_STATE without such a pass). */
 int gnn_loop_adjoint_z(gnn_loop *l, float *z_host);
