@@ -117,6 +117,27 @@ class GNNnodeBased(BaseClass):
         self.adjoint_batch_normalization = batch_normalization
         self.adjoint_label_gradients = label_gradients
 
+    def contraction_estimate(self, g: Union[GraphObject, GraphTensor], iterations: int = 32, v0=None, seed: int = 0) -> dict:
+        """How far net_state's map is from a contraction on graph ``g`` at the state the Loop finds - the condition under which
+        'fixed_point' gradients (and the Loop itself, near its fixed point) converge.  Power iteration on J^T, J = d body / d state at that
+        state with BatchNormalization on its moving statistics: ``growth[t]`` = |J^T v_t| over the unit vectors the iteration runs through,
+        started from ``v0`` [nodes, state_vect_dim] or (None) normal draws keyed on ``seed``.  Returns dict(growth, done, k, last, rho,
+        contractive): ``rho``, the geometric mean of the later half of growth, estimates the spectral radius of J, ``contractive`` is
+        rho < 1, ``k`` the Loop's iteration count, ``done`` < iterations says the vector became 0 (or not finite) there.  Works in either
+        gradient mode and changes nothing of the model.  Needs state_vect_dim > 0 and a net_state without Dropout (NotImplementedError);
+        ``iterations`` from 1 to 1024 (ValueError).  An LGNN layer is estimated on the relabelled graph (update_graph)."""
+        iterations = int(iterations)
+        if not 1 <= iterations <= 1024: raise ValueError('param <iterations> must lie in [1, 1024]')
+        if self.state_vect_dim == 0:
+            raise NotImplementedError('contraction_estimate needs state_vect_dim > 0: with 0 the Loop iterates on the node labels themselves')
+        if any(float(r) != 0.0 for r in self.net_state.dropout_rates()):
+            raise NotImplementedError('contraction_estimate needs a net_state without Dropout: the map the inference Loop iterates')
+        if isinstance(g, GraphObject): g = GraphTensor.fromGraphObject(g)
+        loop = self._device_loop(g.device_graph(self.device))
+        self._prepare_loop(g, loop)
+        loop.set_state0(None, self.seed)
+        return loop.contraction_estimate(self.net_state.device_mlp(self.device), iterations, v0, seed, dropout_state=self.net_state.dropout_rates())
+
     def _gradient_config(self) -> dict:
         config = {'mode': self.gradient_mode, 'max_iteration': self.adjoint_max_iteration, 'threshold': self.adjoint_threshold}
         # (written only when set: the dicts and files of models without it are what they were)

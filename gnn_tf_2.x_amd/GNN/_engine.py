@@ -25,6 +25,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_loop_set_gradient_mode_ex', 'gnn_adjoint_form_ex', 'gnn_loop_adjoint_z', 'gnn_loop_train_backward_chained',
+           'gnn_loop_contraction_estimate', 'gnn_loop_contraction_vector',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_gather_program_compact', 'gnn_graph_gather_program_format', 'gnn_graph_set_program_entries', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -218,6 +219,16 @@ def adjoint_form(dims, activations, n_rows, rates=None, batch_normalization=Fals
         _check(lib().gnn_adjoint_form(C.c_int(L), _ip(d), _ip(a), _fp(r), C.c_int(bool(batch_normalization)), C.c_int64(int(n_rows)), _ip(out)))
     return dict(eligible=bool(out[0]), reason=ADJOINT_REFUSALS[int(out[1])], gather=GATHER_NAMES[int(out[2])],
                 backward=[FORM_NAMES[int(v)] for v in out[3:3 + L]], narrow_refusal=NARROW_REFUSALS[int(out[3 + L])])
+
+
+def contraction_summary(growth, done: int, k: float) -> dict:
+    """The result dict of Loop.contraction_estimate from what the C call returns (host arithmetic, float64)."""
+    g = np.asarray(growth, np.float32)[:done].copy()
+    tail = g[done // 2:done].astype(np.float64)
+    if done == 0 or np.any(g == 0): rho = 0.0
+    else:
+        with np.errstate(all='ignore'): rho = float(np.exp(np.mean(np.log(tail))))
+    return dict(growth=g, done=int(done), k=float(k), last=float(g[-1]) if done else 0.0, rho=rho, contractive=bool(rho < 1.0))
 
 
 def split_f16(values, exponent=None):
@@ -974,6 +985,30 @@ class Loop:
         z = np.zeros((self.n_rows, self.Ds), np.float32)
         _check(lib().gnn_loop_adjoint_z(self._h, _fp(z)))
         return z
+
+    def contraction_estimate(self, net_state: 'Mlp', iterations: int = 32, v0=None, seed: int = 0, src_csr=None, dropout_state=None, bn_state=None) -> dict:
+        """gnn_loop_contraction_estimate: power iteration on J^T at the state the inference Loop finds, J = d body / d state of net_state there
+        (BatchNormalization on its moving statistics).  growth[t] = |J^T v_t| for the unit vectors v_t the iteration runs through, from v0 [n_rows, Ds]
+        or (None) normal draws keyed on ``seed``.  Returns dict(growth (the first ``done`` entries), done (< iterations: the vector became 0 or not
+        finite there), k (bodies of the inference Loop), last (growth[done - 1], 0.0 without one), rho = exp(mean(log(growth[done // 2 : done])))
+        - the estimate of the spectral radius; 0.0 when a growth entry is 0 -, contractive = rho < 1).  Works in every gradient mode and leaves it;
+        ends the life of a pending train_forward()."""
+        iterations = int(iterations)
+        sip, sdst, sw = (np.ascontiguousarray(src_csr[0], np.int32), np.ascontiguousarray(src_csr[1], np.int32), _f32(src_csr[2])) if src_csr is not None else (None, None, None)
+        ds_ = _f32(dropout_state if dropout_state is not None else np.zeros(net_state.n + 1))
+        bs = _f32(bn_state) if bn_state is not None else None
+        if v0 is not None: v0 = _f32(v0, (self.n_rows, self.Ds))
+        growth = np.zeros(max(iterations, 1), np.float32)
+        done, k = C.c_int(0), C.c_float(0.0)
+        _check(lib().gnn_loop_contraction_estimate(self._h, _ip(sip), _ip(sdst), _fp(sw), _fp(ds_), _fp(bs), C.c_int(iterations), _fp(v0), C.c_uint64(seed),
+                                                   _fp(growth), C.byref(done), C.byref(k)))
+        return contraction_summary(growth, int(done.value), float(k.value))
+
+    def contraction_vector(self) -> np.ndarray:
+        """gnn_loop_contraction_vector (test entry point): the last vector w_done [n_rows, Ds] of the last contraction_estimate()."""
+        w = np.zeros((self.n_rows, self.Ds), np.float32)
+        _check(lib().gnn_loop_contraction_vector(self._h, _fp(w)))
+        return w
 
     def train_arena_bytes(self) -> int:
         """gnn_loop_train_arena_bytes (test entry point): bytes of device scratch the last training forward / backward of this loop used."""

@@ -340,6 +340,9 @@ struct gnn_train_settings {
     struct { int mode = 0, max_iter = 0; float thr = -1.0f; int iterations = 0, converged = 0, gather = 0, flags = 0; } adjoint;
     // recomputation of the bodies' activations (gnn_loop_set_train_recompute): 0 off, 1 on, 2 on with the caching kernels in the first pass
     int recompute = 0;
+    // the last contraction estimate of this loop (gnn_loop_contraction_estimate, gnn_train_adjoint.hip): its last vector w_done [rows, Ds] in the
+    // training scratch, alive until the loop's next training forward or estimate resets that scratch (NULL: none)
+    struct { const float *w = nullptr; int64_t rows = 0; } power;
 };
 #define GNN_INTERNAL __attribute__((visibility("hidden")))      // the library's own: kept out of its dynamic symbol table
 struct GNN_INTERNAL gnn_train_ctx;                // gnn_train.h

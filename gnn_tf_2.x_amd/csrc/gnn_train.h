@@ -226,6 +226,11 @@ struct StateGradJob {
     const int *gate_prev = nullptr;
     int *gate = nullptr;
     int *form_out = nullptr;      // receives the ADJ_GATHER_* form the gather took
+    // power iteration of the contraction estimate (pw_inv != NULL; gnn_train_adjoint.hip) instead: z_next[r] = that sum * *pw_inv, also written to
+    // `work`, and ONE partial squared norm of z_next per block of the gather in pw_part; *pw_inv == 0 (the iteration has stopped): z_next stays,
+    // `work` and the partials are zero.  g, z_prev and the gates are not read
+    const float *pw_inv = nullptr;
+    float *pw_part = nullptr;
 };
 
 // floats of a net's trainable arrays = of its gradient vector: dW1, db1, ..., dgamma, dbeta
@@ -361,6 +366,15 @@ inline int adjoint_refusal(const gnn_mlp *m, const float *rates, int flags = 0)
 // the gather of one adjoint iteration (job.g != NULL) from u = d inp [n, in_s], or (aligned) from the dsg rows [n, 2 Ds] k_bwd3_split left;
 // returns the ADJ_GATHER_* form it took through *form (may be NULL)
 int launch_adjoint_gather(hipStream_t st, const StateGradJob &job, const float *u, bool aligned, int *form);
+// The power iteration w_t = (J^T w_{t-1}) / |w_{t-1}| of the contraction estimate (include/gnn_hip.h: gnn_loop_contraction_estimate).  Its gather
+// (job.pw_inv != NULL) has the three shapes of the adjoint's, without g, z_prev and the gate: per element the same fmaf chain, then (own + acc) * *pw_inv,
+// and one partial sum of squares per block of 16 rows.  power_blocks: the partials a vector of n rows leaves.
+inline unsigned power_blocks(int64_t n) { return cdiv(n * 16, 256); }
+int launch_power_gather(hipStream_t st, const StateGradJob &job, const float *u, bool aligned, int *form);
+// w_0: v [n, Ds] filled with normal draws of the counter RNG keyed on seed (fill != 0), copied to `work`, with its partials
+int launch_power_start(hipStream_t st, int64_t n, int Ds, int fill, uint64_t seed, float *v, float *work, float *part);
+// one block: norm = sqrt(part[0] + part[1] + ... in double), *norm_out = norm, *inv = 1 / norm - or 0 when norm is 0 or not finite
+int launch_power_finalize(hipStream_t st, unsigned blocks, const float *part, float *norm_out, float *inv);
 
 // One launch per adjoint iteration for narrow nets (k_adjoint_narrow): a block owns ADJ_NARROW_ROWS rows, forms z_L of them by the gather from the
 // PREVIOUS launch's u (with the gate of iteration L - 1), then runs the whole chain d z -> . W^T (.) act'(a) -> ... down to the own-state and

@@ -864,6 +864,7 @@ static int train_forward_once(gnn_loop *l, const int32_t *src_indptr, const int3
         l->graph_ready_seen = true;
     }
     gnn_train_ctx_free(l);
+    l->train.power = {};              // (the vector of a contraction estimate lived in the scratch that is handed out again from here on)
     gnn_train_arena *arena = loop_arena(l);
     arena->reset();
     gnn_train_ctx *cx = l->train_ctx = new gnn_train_ctx();
@@ -1106,6 +1107,102 @@ static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, floa
     cx->adjoint_z = adj.iterations == 0 ? g_state : zb[adj.iterations & 1];
     // `work` holds z_final (the last gather wrote it beside its z buffer; without an iteration it is the copy of g)
     return net_backward(st, buf, ns, cx->caches[0], work, u_out, nullptr, nullptr, 0, true);
+}
+
+// Contraction estimate at the fixed point (include/gnn_hip.h): power iteration on J^T of the ONE recorded body - the J of adjoint_backward, always
+// with BatchNormalization on its moving statistics.  Forward as gradient mode 1 takes it (the inference Loop to p, one body recorded at p) without
+// net_output; then w_0 (the caller's, or normal draws keyed on seed) with its norm, and per iteration net_backward without weight gradients on the
+// per-kernel chain with the power gather (gnn_train_adjoint.hip: w_t = J^T w_{t-1} / n_{t-1}, one partial squared norm per block) and
+// k_power_finalize (n_t into growth, 1 / n_t for the next gather; 0 stops the iteration on the device).  Scratch is rewound per iteration as the
+// adjoint's; the host waits once, for growth.  The loop's gradient mode is neither read nor written; the context of a pending training forward ends.
+extern "C" int gnn_loop_contraction_estimate(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w, const float *dropout_state,
+                                             const float *bn_state, int iterations, const float *v0, uint64_t seed, float *growth, int *done, float *k_out)
+{
+    ARGCHK(l && dropout_state && growth && done && k_out, "bad arguments");
+    ARGCHK(iterations >= 1 && iterations <= 1024, "iterations must lie in [1, 1024] (got %d)", iterations);
+    if (l->world > 1) return gnn_fail(GNN_ERR_UNSUPPORTED, "the contraction estimate is single-GPU (this loop is rank %d of %d)", l->rank, l->world);
+    if (l->D == 0) return gnn_fail(GNN_ERR_UNSUPPORTED, "the contraction estimate needs state_vect_dim > 0 (with 0 the loop iterates on the node labels themselves)");
+    if (adjoint_refusal(l->st, dropout_state, GNN_ADJOINT_FROZEN_BN))
+        return gnn_fail(GNN_ERR_UNSUPPORTED, "the contraction estimate needs a net_state without Dropout (the map the inference Loop iterates): this one has a Dropout rate != 0");
+    ARGCHK(l->edge_mode == l->edge_expected, "edge-based net_output: call gnn_loop_set_edge_readout first");
+    if (!l->have_state0) return gnn_fail(GNN_ERR_STATE, "state_vect_dim > 0: call gnn_loop_set_state0 first");
+    gnn_graph *g = l->g;
+    const int64_t N = g->n_rows;
+    const int Ds = l->Ds;
+    int rc;
+    HIPCHK(hipSetDevice(l->device));
+    hipStream_t st = l->stream;
+    float k_inference = 0.0f;
+    if ((rc = gnn_loop_run(l, 0, &k_inference))) return rc;
+    if (!l->graph_ready_seen) {
+        if ((rc = gnn_graph_wait_ready(g, st))) return rc;
+        l->graph_ready_seen = true;
+    }
+    gnn_train_ctx_free(l);
+    l->train.power = {};
+    gnn_train_arena *arena = loop_arena(l);
+    arena->reset();
+    // (the context lives for this call alone: it holds no net_output, so nothing behind a training forward may find it)
+    struct Scoped { gnn_loop *l; ~Scoped() { gnn_train_ctx_free(l); } } scoped{l};
+    gnn_train_ctx *cx = l->train_ctx = new gnn_train_ctx();
+    cx->buf.arena = arena;
+    cx->N = N; cx->M = 0;
+    cx->backward_done = true; cx->applied = true;
+    Buf &buf = cx->buf;
+    Forward f{l, cx, st, false, nullptr, N, 0, 0, dropout_state, seed};
+    f.flag_words = (size_t)2 * GNN_FLAG_WORDS;
+    const size_t z_s = net_zero_floats(l->st, 1), z_f = (f.flag_words + 63) & ~(size_t)63, z_total = z_s + z_f + (size_t)N * l->in_s;
+    float *zero_mem = nullptr;
+    if ((rc = buf.get(&zero_mem, z_total))) return rc;
+    HIPCHK(hipMemsetAsync(zero_mem, 0, sizeof(float) * std::max<size_t>(1, z_total), st));
+    if ((rc = net_setup(st, buf, cx->ns, l->st, dropout_state, bn_state, 1, zero_mem, N, true))) return rc;
+    if (l->st->has_bn && (rc = net_freeze_bn(st, buf, cx->ns))) return rc;
+    f.flags = reinterpret_cast<int *>(zero_mem + z_s);
+    cx->tmpl = zero_mem + z_s + z_f;
+    cx->seed = seed;
+    if ((rc = f.by_source(src_indptr, src_dst, src_w)) || (rc = f.concat_template())) return rc;
+    float *p = nullptr;
+    if ((rc = buf.get(&p, (size_t)std::max<int64_t>(N, 1) * Ds))) return rc;
+    if (N) HIPCHK(hipMemcpyAsync(p, gnn_loop_state_after(l, l->kfinal, 0), sizeof(float) * (size_t)N * Ds, hipMemcpyDeviceToDevice, st));
+    cx->states.push_back(p);
+    if ((rc = f.enqueue_body(0))) return rc;
+    cx->fixed_point = true;
+    cx->state = p;
+    cx->k = (int)k_inference;
+
+    const size_t zf = (size_t)std::max<int64_t>(N, 1) * Ds;
+    const unsigned blocks = power_blocks(N);
+    float *w = nullptr, *work = nullptr, *part = nullptr, *norms = nullptr, *inv = nullptr;        // norms [iterations + 1]: n_0, then growth
+    if ((rc = buf.get(&w, zf)) || (rc = buf.get(&work, zf)) || (rc = buf.get(&part, (size_t)std::max(blocks, 1u))) || (rc = buf.get(&norms, (size_t)iterations + 1)) ||
+        (rc = buf.get(&inv, (size_t)1))) return rc;
+    float *hnorms = static_cast<float *>(arena->host.get(std::max<size_t>(sizeof(float) * ((size_t)iterations + 1), 4096)));
+    if (!hnorms) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
+    for (int t = 0; t < iterations; ++t) growth[t] = 0.0f;
+    *done = 0;
+    *k_out = k_inference;
+    if (N == 0) { HIPCHK(hipStreamSynchronize(st)); return GNN_OK; }
+    if (v0) HIPCHK(hipMemcpyAsync(w, v0, sizeof(float) * (size_t)N * Ds, hipMemcpyHostToDevice, st));
+    if ((rc = launch_power_start(st, N, Ds, v0 ? 0 : 1, seed, w, work, part)) || (rc = launch_power_finalize(st, blocks, part, norms, inv))) return rc;
+    const gnn_train_arena::Mark mark = arena->mark();
+    for (int t = 1; t <= iterations; ++t) {
+        arena->rewind(mark);
+        StateGradJob job{N, Ds, l->in_s, Ds + l->NLc, cx->d_sip, cx->d_sdst, cx->d_sw, nullptr};
+        job.z_next = w; job.work = work; job.pw_inv = inv; job.pw_part = part;
+        float *u = nullptr;
+        if ((rc = net_backward(st, buf, cx->ns, cx->caches[0], work, &u, &job, nullptr, 0, false)) ||
+            (rc = launch_power_finalize(st, blocks, part, norms + t, inv))) return rc;
+    }
+    arena->rewind(mark);
+    HIPCHK(hipMemcpyAsync(hnorms, norms, sizeof(float) * ((size_t)iterations + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // done = the first t whose n_t is 0 or not finite (its entry is kept as measured, the later ones are 0), else all of them
+    int t_done = iterations;
+    for (int t = 0; t <= iterations; ++t)
+        if (!(hnorms[t] > 0.0f) || !std::isfinite(hnorms[t])) { t_done = t; break; }
+    for (int t = 1; t <= iterations; ++t) growth[t - 1] = t <= t_done ? hnorms[t] : 0.0f;
+    *done = t_done;
+    l->train.power.w = w; l->train.power.rows = N;
+    return GNN_OK;
 }
 
 // gnn_loop_train_backward_chained: the label gradients stay on the device.  keep_nodes / keep_arcs: compute d_nodes / d_arc_labels and leave them

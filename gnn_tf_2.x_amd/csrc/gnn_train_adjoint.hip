@@ -151,6 +151,177 @@ __global__ void __launch_bounds__(256) k_adjoint_gather(const AdjGather p)
     if (__any(moved) && (threadIdx.x & 63) == 0) gnn_flag_raise(p.gate);
 }
 
+// ---- power iteration on J^T (the contraction estimate, include/gnn_hip.h: gnn_loop_contraction_estimate) ------------------------------------------
+// w_t = (J^T w_{t-1}) * inv with inv = 1 / |w_{t-1}| read from one device float: the gathers above without g, z_prev and the gate.  The squared
+// norm of w_t is formed in the same pass, in a fixed order: per lane over its ascending columns, the 16 lanes of a row by row16_sum, the 16 rows of a
+// block in row order through LDS - ONE float per block; k_power_finalize adds the blocks' floats in block order, in double.  No float atomics.
+struct PowGather {
+    int64_t n;
+    int Ds, in_s, c_aggs;
+    const float *u;               // as AdjGather::u
+    const int32_t *sip, *sdst;
+    const float *sw;
+    const float *inv;
+    float *w_next, *work, *part;
+};
+
+// the block's 16 row sums (the same bits in the 16 lanes of a row) -> part[block], rows in ascending order; every thread of the block calls it
+__device__ __forceinline__ void power_block_sum(float row_sq, float *part)
+{
+    __shared__ float rows[16];
+    if ((threadIdx.x & 15) == 0) rows[threadIdx.x >> 4] = row_sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = rows[0];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) s = s + rows[q];
+        part[blockIdx.x] = s;
+    }
+}
+
+// the shapes of k_adjoint_gather_rows<ALIGNED>
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256) k_power_gather_rows(const PowGather p)
+{
+    const float inv = *p.inv;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = t >> 4;
+    const int cc = 4 * (int)(t & 15), Ds = p.Ds;
+    float sq = 0.0f;
+    if (r < p.n && cc < Ds) {
+        if (inv != 0.0f) {
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            float4 own;
+            const int32_t e1 = p.sip[r + 1];
+            if (ALIGNED) {
+                for (int32_t e = p.sip[r]; e < e1; e += 8) {
+                    float w[8];
+                    float4 x[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int32_t ee = e + q < e1 ? e + q : e;       // clamp: a real entry, result unused
+                        w[q] = p.sw[ee];
+                        x[q] = *reinterpret_cast<const float4 *>(p.u + (int64_t)p.sdst[ee] * 2 * Ds + Ds + cc);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        if (e + q < e1) {
+                            acc[0] = __builtin_fmaf(w[q], x[q].x, acc[0]); acc[1] = __builtin_fmaf(w[q], x[q].y, acc[1]);
+                            acc[2] = __builtin_fmaf(w[q], x[q].z, acc[2]); acc[3] = __builtin_fmaf(w[q], x[q].w, acc[3]);
+                        }
+                }
+                own = *reinterpret_cast<const float4 *>(p.u + r * 2 * Ds + cc);
+            } else {
+                for (int32_t e = p.sip[r]; e < e1; e += 4) {
+                    float w[4], x[4][4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const bool in = e + q < e1;
+                        w[q] = in ? p.sw[e + q] : 0.0f;
+                        const float *src = p.u + (int64_t)(in ? p.sdst[e + q] : 0) * p.in_s + p.c_aggs + cc;
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) x[q][v] = in ? src[v] : 0.0f;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (e + q < e1) {
+#pragma unroll
+                            for (int v = 0; v < 4; ++v) acc[v] = __builtin_fmaf(w[q], x[q][v], acc[v]);
+                        }
+                }
+                const float *o = p.u + r * p.in_s + cc;
+                own = float4{o[0], o[1], o[2], o[3]};
+            }
+            const float4 wn = float4{(own.x + acc[0]) * inv, (own.y + acc[1]) * inv, (own.z + acc[2]) * inv, (own.w + acc[3]) * inv};
+            *reinterpret_cast<float4 *>(p.w_next + r * Ds + cc) = wn;
+            *reinterpret_cast<float4 *>(p.work + r * Ds + cc) = wn;
+            sq = sq + wn.x * wn.x; sq = sq + wn.y * wn.y; sq = sq + wn.z * wn.z; sq = sq + wn.w * wn.w;
+        } else
+            *reinterpret_cast<float4 *>(p.work + r * Ds + cc) = float4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    power_block_sum(row16_sum(sq), p.part);
+}
+
+// the shape of k_adjoint_gather
+__global__ void __launch_bounds__(256) k_power_gather(const PowGather p)
+{
+    const float inv = *p.inv;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = t >> 4;
+    const int j = (int)(t & 15), Ds = p.Ds;
+    float sq = 0.0f;
+    if (r < p.n) {
+        const int32_t e0 = p.sip[r], e1 = p.sip[r + 1];
+        for (int c = j; c < Ds; c += 16) {
+            if (inv == 0.0f) { p.work[r * Ds + c] = 0.0f; continue; }
+            float acc = 0.0f;
+            for (int32_t e = e0; e < e1; e += 4) {
+                float w[4], x[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const bool in = e + q < e1;
+                    w[q] = in ? p.sw[e + q] : 0.0f;
+                    x[q] = in ? p.u[(int64_t)p.sdst[e + q] * p.in_s + p.c_aggs + c] : 0.0f;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) if (e + q < e1) acc = __builtin_fmaf(w[q], x[q], acc);
+            }
+            const float wn = (p.u[r * p.in_s + c] + acc) * inv;
+            p.w_next[r * Ds + c] = wn;
+            p.work[r * Ds + c] = wn;
+            sq = sq + wn * wn;
+        }
+    }
+    power_block_sum(row16_sum(sq), p.part);
+}
+
+// w_0: lane j of a row takes the columns j, j + 16, ...; fill: element i = r Ds + c is a normal draw of the counter RNG (mix64 of gnn_train.h, Box-Muller
+// on the two 24-bit halves of one word), else v holds the caller's vector; copied to `work`, with the block's partial squared norm
+__global__ void __launch_bounds__(256) k_power_start(int64_t n, int Ds, int fill, uint64_t seed, float *v, float *work, float *part)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = t >> 4;
+    const int j = (int)(t & 15);
+    float sq = 0.0f;
+    if (r < n)
+        for (int c = j; c < Ds; c += 16) {
+            const int64_t i = r * Ds + c;
+            float x;
+            if (fill) {
+                const uint64_t h = mix64(mix64(seed) ^ mix64((uint64_t)i));
+                const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777217.0f);
+                const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
+                x = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+                v[i] = x;
+            } else
+                x = v[i];
+            work[i] = x;
+            sq = sq + x * x;
+        }
+    power_block_sum(row16_sum(sq), part);
+}
+
+// One block.  Thread i adds the partials of blocks [i c, (i + 1) c), c = ceil(blocks / 256), in block order in double; thread 0 adds the 256 sums
+// in thread order: the blocks in ascending order, in 256 runs.  norm = sqrt(sum); *inv = 1 / norm for the next gather, 0 when the norm is 0 or
+// not finite - the iteration stops there, and every later gather hands nothing on.
+__global__ void __launch_bounds__(256) k_power_finalize(unsigned blocks, const float *part, float *norm_out, float *inv)
+{
+    __shared__ double sums[256];
+    const unsigned c = (blocks + 255) / 256, b0 = threadIdx.x * c, b1 = b0 + c < blocks ? b0 + c : blocks;
+    double s = 0.0;
+    for (unsigned b = b0; b < b1; ++b) s = s + (double)part[b];
+    sums[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = sums[0];
+        for (int q = 1; q < 256; ++q) tot = tot + sums[q];
+        const float norm = (float)sqrt(tot);
+        *norm_out = norm;
+        const float r = norm > 0.0f && norm <= 3.402823466e+38f ? (float)(1.0 / (double)norm) : 0.0f;
+        *inv = r <= 3.402823466e+38f ? r : 0.0f;                   // (a subnormal norm: its reciprocal is no float)
+    }
+}
+
 // One launch per adjoint iteration for narrow nets (at most three Dense layers of at most 64 outputs behind a concat of at most 96 columns,
 // fewer than 4,096 rows: the step is bound by its launch count there).  Launch L: a block of 256 threads owns ADJ_NARROW_ROWS = 16 rows, 16 lanes
 // per row.  (1) gather != 0: z_L of its rows = g + (u_{L-1}[r, :Ds] + sum over the arcs r -> dst of w u_{L-1}[dst, Ds:]) from the PREVIOUS
@@ -263,6 +434,37 @@ int launch_adjoint_gather(hipStream_t st, const StateGradJob &job, const float *
     return GNN_OK;
 }
 
+int launch_power_gather(hipStream_t st, const StateGradJob &job, const float *u, bool aligned, int *form)
+{
+    const bool rows = adjoint_rows16(job.Ds);
+    if (form) *form = rows ? (aligned ? ADJ_GATHER_ROWS_ALIGNED : ADJ_GATHER_ROWS) : ADJ_GATHER_GENERIC;
+    if (aligned && !rows) return gnn_fail(GNN_ERR_STATE, "internal: aligned state-gradient rows with state width %d", job.Ds);
+    if (!job.pw_inv || !job.pw_part || !job.z_next || !job.work) return gnn_fail(GNN_ERR_STATE, "internal: a power gather without its buffers");
+    if (job.N <= 0) return GNN_OK;
+    const PowGather p{job.N, job.Ds, job.in_s, job.c_aggs, u, job.sip, job.sdst, job.sw, job.pw_inv, job.z_next, job.work, job.pw_part};
+    const unsigned grid = power_blocks(job.N);
+    if (rows && aligned) hipLaunchKernelGGL(k_power_gather_rows<true>, grid, 256, 0, st, p);
+    else if (rows) hipLaunchKernelGGL(k_power_gather_rows<false>, grid, 256, 0, st, p);
+    else hipLaunchKernelGGL(k_power_gather, grid, 256, 0, st, p);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
+int launch_power_start(hipStream_t st, int64_t n, int Ds, int fill, uint64_t seed, float *v, float *work, float *part)
+{
+    if (n <= 0) return GNN_OK;
+    hipLaunchKernelGGL(k_power_start, power_blocks(n), 256, 0, st, n, Ds, fill, seed, v, work, part);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
+int launch_power_finalize(hipStream_t st, unsigned blocks, const float *part, float *norm_out, float *inv)
+{
+    hipLaunchKernelGGL(k_power_finalize, 1, 256, 0, st, blocks, part, norm_out, inv);
+    HIPCHK(hipGetLastError());
+    return GNN_OK;
+}
+
 }   // namespace gnn_train
 
 extern "C" int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out)
@@ -340,6 +542,17 @@ extern "C" int gnn_loop_adjoint_z(gnn_loop *l, float *z_host)
     HIPCHK(hipSetDevice(l->device));
     HIPCHK(hipStreamSynchronize(l->stream));
     if (cx->N > 0) HIPCHK(hipMemcpy(z_host, cx->adjoint_z, sizeof(float) * (size_t)cx->N * l->Ds, hipMemcpyDeviceToHost));
+    return GNN_OK;
+}
+
+// w_done of the last contraction estimate (gnn_train.hip: it lives in the step's scratch until the next training forward or estimate)
+extern "C" int gnn_loop_contraction_vector(gnn_loop *l, float *w_host)
+{
+    ARGCHK(l && w_host, "bad arguments");
+    if (!l->train.power.w) return gnn_fail(GNN_ERR_STATE, "no contraction estimate of this loop to take the vector from (a training forward since ends its life)");
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipStreamSynchronize(l->stream));
+    if (l->train.power.rows > 0) HIPCHK(hipMemcpy(w_host, l->train.power.w, sizeof(float) * (size_t)l->train.power.rows * l->Ds, hipMemcpyDeviceToHost));
     return GNN_OK;
 }
 

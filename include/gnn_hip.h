@@ -307,6 +307,33 @@ int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float
 int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out);
 /* z_final [n_rows, Ds] of the last backward pass of mode 1 / 2, to host memory (test entry point; GNN_ERR_STATE without such a pass). */
 int gnn_loop_adjoint_z(gnn_loop *l, float *z_host);
+/* Contraction estimate at the fixed point: how far net_state's map is from a contraction at the state the Loop finds - the condition under which the
+ * adjoint iteration of modes 1 / 2 (and the inference Loop near its fixed point) converges.  With p the state the inference Loop stops at, F one body of
+ * net_state at p (BatchNormalization on its moving statistics, always) and J = dF/dp over the own-state and aggregated-state columns - the J of the
+ * adjoint iteration above - power iteration on J^T from w_0 [N, Ds], n_0 = |w_0|_2:
+ *   for t = 1 .. iterations:   w_t = (J^T w_{t-1}) * (1 / n_{t-1});   n_t = |w_t|_2;   growth[t - 1] = n_t
+ * so growth[t - 1] = |J^T v_{t-1}| for the unit vector v_{t-1} = w_{t-1} / |w_{t-1}|.  Its late entries approach the spectral radius of J when the
+ * dominant eigenvalue is real; their geometric mean is the Gelfand estimate otherwise.  If some n_t is 0 or not finite the iteration stops there:
+ * *done = t, growth[t - 1] is what was measured, the later entries are 0 (otherwise *done = iterations).
+ *   Forward        as the training forward of mode 1: the inference Loop with the loop's own settings (state0, arithmetic, launch form, certified
+ *                  gate) gives *k and p, ONE body is recorded at p.  net_output does not run.
+ *   Iteration      the input-gradient-only backward pass of the recorded body on the per-kernel chain (as mode 2), then a gather with the adjoint
+ *                  gather's three shapes and its fmaf chain over the arcs in stored order: w_t[r] = (u[r, :Ds] + sum w u[dst, c_aggs : c_aggs + Ds]) * inv,
+ *                  inv = 1 / n_{t-1} read from one device float.  The same pass leaves one partial squared norm per block of 16 rows (per lane over
+ *                  ascending columns, the 16 lanes of a row by a fixed butterfly, the rows in order); one block adds the partials in block order in
+ *                  double, writes n_t and the next inv (0 stops every later gather on the device).  No float atomics: two calls return the same
+ *                  bits.  The host waits once, at the end.
+ *   src_*, dropout_state, bn_state   as gnn_loop_train_forward takes them for net_state; iterations: 1 .. 1024 (else GNN_ERR_ARG);
+ *   v0 [N, Ds]     w_0, or NULL: normal draws of the engine's counter RNG keyed on seed (element i: mix64(mix64(seed) ^ mix64(i)), Box-Muller).
+ * Works in every gradient mode and leaves the mode as it is.  Like any forward it ends the life of a pending training forward's context: a
+ * gnn_loop_train_backward behind it is refused (GNN_ERR_STATE).  The loop's state / outputs are those of the inference Loop it ran.
+ * GNN_ERR_UNSUPPORTED, with the reason in gnn_last_error: a Dropout rate != 0 in net_state, state_vect_dim == 0, world > 1.
+ * A graph without rows: *done = 0, growth all zero. */
+int gnn_loop_contraction_estimate(gnn_loop *l, const int32_t *src_indptr, const int32_t *src_dst, const float *src_w, const float *dropout_state,
+                                  const float *bn_state, int iterations, const float *v0, uint64_t seed, float *growth, int *done, float *k_out);
+/* w_done [n_rows, Ds] of the last gnn_loop_contraction_estimate, to host memory (test entry point, not part of the supported interface; GNN_ERR_STATE
+ * without an estimate, or after a training forward since). */
+int gnn_loop_contraction_vector(gnn_loop *l, float *w_host);
 /* Bytes handed out from the step's scratch by the last training forward / backward of this loop (test entry point). */
 int gnn_loop_train_arena_bytes(const gnn_loop *l, int64_t *bytes);
 /* Optimizer step on the device (reference GNN_BaseClass.py:243-247, optimizer.apply_gradients on the trainable variables of
