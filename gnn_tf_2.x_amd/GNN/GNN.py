@@ -45,6 +45,8 @@ class GNNnodeBased(BaseClass):
         self.adjoint_threshold = None
         self.adjoint_batch_normalization = None     # set_gradient_mode(..., batch_normalization='frozen')
         self.adjoint_label_gradients = False        # set_gradient_mode(..., label_gradients=True)
+        self.adjoint_solver = 'picard'              # set_gradient_mode(..., adjoint_solver='anderson', anderson_window=5)
+        self.anderson_window = 5
         self.label_projection = 'off'       # set_label_projection
         self.train_recompute = False        # set_train_recompute
         self.wide_state = 'off'             # set_wide_state
@@ -82,7 +84,8 @@ class GNNnodeBased(BaseClass):
         self.wide_state = {v: k for k, v in _engine.WIDE_STATE_MODES.items()}[code]
 
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None, *,
-                          batch_normalization: Optional[str] = None, label_gradients: bool = False) -> None:
+                          batch_normalization: Optional[str] = None, label_gradients: bool = False, adjoint_solver: str = 'picard',
+                          anderson_window: int = 5) -> None:
         """How train() differentiates the state loop.  'unrolled' (default): back-propagation through every executed body.
         'fixed_point': the gradient at the converged state (Almeida-Pineda; Scarselli et al. 2009, section III) - the inference Loop
         finds the state, ONE body is recorded there, the adjoint iteration z <- g + J^T z runs until no node's z moves by more than
@@ -96,10 +99,20 @@ class GNNnodeBased(BaseClass):
         ``label_gradients=True`` (opt-in; False by default): the fixed-point backward pass also returns the gradient with respect to the node
         labels (edge-based: and the arc labels) this model saw - the direct part through net_output plus (d body / d labels)^T z at the fixed
         point.  It is what the joint steps of an LGNN ('parallel' / 'residual') hand from layer i + 1 to layer i; needs state_vect_dim > 0.
+        ``adjoint_solver='anderson'`` (opt-in; 'picard' by default): the adjoint system (I - J^T) z = g is solved by Anderson mixing over the last
+        ``anderson_window`` (1 .. 8, default 5) difference pairs of the iteration instead of the plain iteration, whose count grows like
+        1 / (1 - rho) with rho the spectral radius contraction_estimate() reports: the same stopping rule on the residual, a fraction of the
+        iterations where rho is close to 1, the same count where it is small.  The gradients agree with 'picard' to the threshold, not bit for bit,
+        and the step takes 2 window + 2 more scratch buffers of [nodes, state_vect_dim] floats.  It presumes a contraction as the mode itself
+        does: without one the Loop has no fixed point and the gradient means nothing.  Both keywords combine with the two above; in 'unrolled'
+        mode they are stored and have no effect, as ``max_iteration`` / ``threshold``.
         Kept by copy() (so by LKO) and by save() / load()."""
         if mode not in ('unrolled', 'fixed_point'): raise ValueError("param <mode> not in ['unrolled', 'fixed_point']")
         if batch_normalization not in (None, 'frozen'): raise ValueError("param <batch_normalization> not in [None, 'frozen']")
         if not isinstance(label_gradients, bool): raise ValueError('param <label_gradients> must be a bool')
+        if adjoint_solver not in ('picard', 'anderson'): raise ValueError("param <adjoint_solver> not in ['picard', 'anderson']")
+        if isinstance(anderson_window, bool) or not isinstance(anderson_window, (int, np.integer)) or not 1 <= int(anderson_window) <= 8:
+            raise ValueError('param <anderson_window> must be an int in [1, 8]')
         if mode == 'fixed_point' and label_gradients and self.state_vect_dim == 0:
             raise NotImplementedError('fixed_point label gradients need state_vect_dim > 0: with 0 the unrolled label gradient is the gradient of '
                                       'the INITIAL state, which a fixed point does not depend on')
@@ -116,6 +129,8 @@ class GNNnodeBased(BaseClass):
         self.adjoint_threshold = None if threshold is None else float(threshold)
         self.adjoint_batch_normalization = batch_normalization
         self.adjoint_label_gradients = label_gradients
+        self.adjoint_solver = adjoint_solver
+        self.anderson_window = int(anderson_window)
 
     def contraction_estimate(self, g: Union[GraphObject, GraphTensor], iterations: int = 32, v0=None, seed: int = 0) -> dict:
         """How far net_state's map is from a contraction on graph ``g`` at the state the Loop finds - the condition under which
@@ -143,6 +158,7 @@ class GNNnodeBased(BaseClass):
         # (written only when set: the dicts and files of models without it are what they were)
         if self.adjoint_batch_normalization is not None: config['batch_normalization'] = self.adjoint_batch_normalization
         if self.adjoint_label_gradients: config['label_gradients'] = True
+        if self.adjoint_solver != 'picard' or self.anderson_window != 5: config.update(adjoint_solver=self.adjoint_solver, anderson_window=self.anderson_window)
         return config
 
     def _frozen_state_bn(self) -> bool:
@@ -161,7 +177,7 @@ class GNNnodeBased(BaseClass):
                              extra_metrics_arguments=self.mt_args, state_vect_dim=self.state_vect_dim,
                              path_writer=path_writer or self.path_writer + '_copied/', namespace=namespace or 'GNN')
         new.set_gradient_mode(self.gradient_mode, self.adjoint_max_iteration, self.adjoint_threshold, batch_normalization=self.adjoint_batch_normalization,
-                              label_gradients=self.adjoint_label_gradients)
+                              label_gradients=self.adjoint_label_gradients, adjoint_solver=self.adjoint_solver, anderson_window=self.anderson_window)
         new.set_label_projection(self.label_projection)
         new.set_train_recompute(self.train_recompute)
         new.set_wide_state(self.wide_state)
@@ -214,7 +230,8 @@ class GNNnodeBased(BaseClass):
         model = cls(net_state=nets[0], net_output=nets[1], optimizer=optz, loss_function=loss, extra_metrics=extra_metrics,
                     extra_metrics_arguments=extra_metrics_arguments, path_writer=path_writer, namespace=namespace, **config)
         model.set_gradient_mode(gradient['mode'], gradient.get('max_iteration'), gradient.get('threshold'),
-                                batch_normalization=gradient.get('batch_normalization'), label_gradients=bool(gradient.get('label_gradients', False)))
+                                batch_normalization=gradient.get('batch_normalization'), label_gradients=bool(gradient.get('label_gradients', False)),
+                                adjoint_solver=gradient.get('adjoint_solver', 'picard'), anderson_window=int(gradient.get('anderson_window', 5)))
         model.set_label_projection(projection)
         model.set_train_recompute(recompute)
         model.set_wide_state(wide_state)
@@ -268,6 +285,10 @@ class GNNnodeBased(BaseClass):
             fixed = gradient[0] != 'unrolled'
             loop.set_gradient_mode(*gradient[:3], batch_normalization=gradient[3] if fixed else None, label_gradients=gradient[4] if fixed else False)
             loop._gradient_set = gradient
+        solver = (self.adjoint_solver, self.anderson_window) if self.gradient_mode != 'unrolled' else ('picard', 5)
+        if getattr(loop, '_solver_set', ('picard', 5)) != solver:
+            loop.set_adjoint_solver(*solver)
+            loop._solver_set = solver
         if getattr(loop, '_projection_set', 'off') != self.label_projection:
             loop.set_label_projection(self.label_projection)
             loop._projection_set = self.label_projection

@@ -54,14 +54,17 @@ class LGNN(BaseClass):
         return all(gnn.train_recompute for gnn in self.gnns)
 
     def set_gradient_mode(self, mode: str, max_iteration: Optional[int] = None, threshold: Optional[float] = None, *,
-                          batch_normalization: Optional[str] = None, label_gradients: bool = False) -> None:
-        """GNNnodeBased.set_gradient_mode for every layer (``batch_normalization`` / ``label_gradients``: forwarded to them).  'serial' training runs the layers'
+                          batch_normalization: Optional[str] = None, label_gradients: bool = False, adjoint_solver: str = 'picard',
+                          anderson_window: int = 5) -> None:
+        """GNNnodeBased.set_gradient_mode for every layer (``batch_normalization`` / ``label_gradients`` / ``adjoint_solver`` / ``anderson_window``:
+        forwarded to them; the device chain of the joint steps runs with the layers' solver).  'serial' training runs the layers'
         own steps and works in both modes; the joint
         steps of 'parallel' / 'residual' need the gradient with respect to a layer's labels, which 'fixed_point' returns only with
         ``label_gradients=True``: they raise NotImplementedError while any layer is in that mode without it.  A stack may mix unrolled and
         fixed-point layers (set the layers' modes one by one).  When every layer is fixed-point the backward passes hand the label gradients
         on inside the device (attribute ``device_chain``, default True; False: through host arrays, the same bits)."""
-        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold, batch_normalization=batch_normalization, label_gradients=label_gradients)
+        for gnn in self.gnns: gnn.set_gradient_mode(mode, max_iteration, threshold, batch_normalization=batch_normalization, label_gradients=label_gradients,
+                                  adjoint_solver=adjoint_solver, anderson_window=anderson_window)
 
     def copy(self, *, path_writer: str = '', namespace: str = '', copy_weights: bool = True) -> 'LGNN':
         optimizer = self.optimizer

@@ -25,7 +25,7 @@ EXPORTS = ['gnn_last_error', 'gnn_version', 'gnn_device_count', 'gnn_device_sync
            'gnn_loop_set_train_recompute', 'gnn_loop_train_recompute_info',
            'gnn_loop_set_gradient_mode', 'gnn_loop_adjoint_info', 'gnn_adjoint_form', 'gnn_loop_train_arena_bytes',
            'gnn_loop_set_gradient_mode_ex', 'gnn_adjoint_form_ex', 'gnn_loop_adjoint_z', 'gnn_loop_train_backward_chained',
-           'gnn_loop_contraction_estimate', 'gnn_loop_contraction_vector',
+           'gnn_loop_contraction_estimate', 'gnn_loop_contraction_vector', 'gnn_loop_set_adjoint_solver', 'gnn_loop_adjoint_solver_info',
            'gnn_mlp_set_regularizers', 'gnn_loop_set_clipping', 'gnn_loop_grad_sqnorm', 'gnn_loop_optimizer_step_scaled',
            'gnn_counters_get', 'gnn_lgnn_run', 'gnn_loop_run_many', 'gnn_loop_set_impl', 'gnn_loop_gate_info', 'gnn_loop_set_pieces', 'gnn_loop_range_info', 'gnn_split_f16_exponent', 'gnn_split_f16', 'gnn_loop_set_persistent', 'gnn_loop_set_tile_form', 'gnn_loop_body_kernel', 'gnn_loop_set_gather_form', 'gnn_gather_program_build', 'gnn_graph_gather_program_info', 'gnn_gather_program_compact', 'gnn_graph_gather_program_format', 'gnn_graph_set_program_entries', 'gnn_loop_set_tile_schedule', 'gnn_loop_set_label_projection', 'gnn_loop_get_label_projection', 'gnn_label_projection_form', 'gnn_loop_set_wide_state', 'gnn_wide_state_form', 'gnn_loop_body_launch', 'gnn_loop_set_grid_limit', 'gnn_loop_set_wide_loader', 'gnn_tile_schedule_build', 'gnn_graph_tile_schedule_info', 'gnn_loop_drop_cached_aggregates', 'gnn_loop_set_profiling', 'gnn_loop_get_timing', 'gnn_loop_get_exchange_timing', 'gnn_loop_destroy', 'gnn_shard_range',
            'gnn_comm_unique_id', 'gnn_comm_create', 'gnn_comm_allreduce_max', 'gnn_comm_destroy', 'gnn_halo_plan', 'gnn_graph_create_halo',
@@ -181,6 +181,8 @@ def train_persistent_form(dims, activations, n_rows, max_iter, rates=None) -> di
     return dict(persistent=bool(out[0]), workgroups=int(out[1]), rows=int(out[2]), lds=int(out[3]), body_bytes=int(out[4]))
 
 
+SOLVER_NAMES = {0: 'picard', 1: 'anderson'}       # gnn_loop_set_adjoint_solver
+SOLVER_CODES = {'picard': 0, 'anderson': 1, 0: 0, 1: 1}
 GATHER_NAMES = {0: 'generic', 1: 'rows', 2: 'rows_aligned', 3: 'narrow'}       # gather form of gnn_loop_adjoint_info / gnn_adjoint_form
 ADJOINT_REFUSALS = {0: None, 1: 'batch_normalization', 2: 'dropout'}
 ADJOINT_FROZEN_BN = 1           # GNN_ADJOINT_FROZEN_BN of include/gnn_hip.h (gnn_loop_set_gradient_mode_ex, gnn_adjoint_form_ex)
@@ -979,6 +981,23 @@ class Loop:
         it, cv, fm = C.c_int(0), C.c_int(0), C.c_int(0)
         _check(lib().gnn_loop_adjoint_info(self._h, C.byref(it), C.byref(cv), C.byref(fm)))
         return dict(iterations=int(it.value), converged=bool(cv.value), gather=GATHER_NAMES[int(fm.value)])
+
+    def set_adjoint_solver(self, solver='picard', window: int = 5) -> int:
+        """gnn_loop_set_adjoint_solver: how the backward pass of the fixed-point modes solves (I - J^T) z = g.  'picard' / 0 (default): the iteration
+        z <- g + J^T z; 'anderson' / 1: Anderson mixing over the last ``window`` (1 .. 8) difference pairs - the same gate on the residual, far fewer
+        iterations where the spectral radius of J is close to 1, 2 window + 2 more [n_rows, Ds] scratch buffers, other bits than 'picard'."""
+        code = SOLVER_CODES.get(solver)
+        if code is None: raise ValueError("adjoint solver must be 'picard' or 'anderson'")
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= int(window) <= 8: raise ValueError('window must be an int in [1, 8]')
+        used = C.c_int(0)
+        _check(lib().gnn_loop_set_adjoint_solver(self._h, C.c_int(code), C.c_int(int(window)), C.byref(used)))
+        return used.value
+
+    def adjoint_solver_info(self) -> dict:
+        """gnn_loop_adjoint_solver_info: dict(solver, window, restarts) - the solver and window set, the window restarts of the last backward pass."""
+        sv, wd, rs = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(lib().gnn_loop_adjoint_solver_info(self._h, C.byref(sv), C.byref(wd), C.byref(rs)))
+        return dict(solver=SOLVER_NAMES[int(sv.value)], window=int(wd.value), restarts=int(rs.value))
 
     def adjoint_z(self) -> np.ndarray:
         """gnn_loop_adjoint_z (test entry point): z_final [n_rows, Ds] of the last backward pass in a fixed-point mode."""

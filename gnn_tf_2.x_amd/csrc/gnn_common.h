@@ -337,7 +337,8 @@ struct gnn_train_settings {
     // thr < 0: the loop's own; iterations, converged, gather: what the last backward pass of mode 1 ran (gnn_loop_adjoint_info)
     // flags (gnn_loop_set_gradient_mode_ex): GNN_ADJOINT_FROZEN_BN - a net_state that ends in BatchNormalization is accepted, on its moving statistics;
     // GNN_ADJOINT_LABEL_GRADIENTS - the backward pass of modes 1 and 2 returns d_nodes / d_arc_labels
-    struct { int mode = 0, max_iter = 0; float thr = -1.0f; int iterations = 0, converged = 0, gather = 0, flags = 0; } adjoint;
+    // solver (gnn_loop_set_adjoint_solver): 0 Picard, 1 Anderson mixing over `window` difference pairs (gnn_train_anderson.hip); restarts: of the last backward pass
+    struct { int mode = 0, max_iter = 0; float thr = -1.0f; int iterations = 0, converged = 0, gather = 0, flags = 0, solver = 0, window = 5, restarts = 0; } adjoint;
     // recomputation of the bodies' activations (gnn_loop_set_train_recompute): 0 off, 1 on, 2 on with the caching kernels in the first pass
     int recompute = 0;
     // the last contraction estimate of this loop (gnn_loop_contraction_estimate, gnn_train_adjoint.hip): its last vector w_done [rows, Ds] in the

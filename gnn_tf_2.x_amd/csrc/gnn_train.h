@@ -231,6 +231,10 @@ struct StateGradJob {
     // `work` and the partials are zero.  g, z_prev and the gates are not read
     const float *pw_inv = nullptr;
     float *pw_part = nullptr;
+    // Anderson-accelerated adjoint iteration (anderson != NULL, beside g; gnn_train_anderson.hip) instead: the gather forms G = g + that sum, the residual
+    // f = G - z_prev with the gate, the difference rows of the window's slot and the block's partial dots; z_next and `work` are written by the
+    // mix that follows (by the gather itself in iteration 0, and behind a closed gate_prev as above)
+    const struct AndersonJob *anderson = nullptr;
 };
 
 // floats of a net's trainable arrays = of its gradient vector: dW1, db1, ..., dgamma, dbeta
@@ -375,6 +379,28 @@ int launch_power_gather(hipStream_t st, const StateGradJob &job, const float *u,
 int launch_power_start(hipStream_t st, int64_t n, int Ds, int fill, uint64_t seed, float *v, float *work, float *part);
 // one block: norm = sqrt(part[0] + part[1] + ... in double), *norm_out = norm, *inv = 1 / norm - or 0 when norm is 0 or not finite
 int launch_power_finalize(hipStream_t st, unsigned blocks, const float *part, float *norm_out, float *inv);
+
+// gnn_train_anderson.hip: the Anderson-accelerated adjoint solve (include/gnn_hip.h: gnn_loop_set_adjoint_solver).  An iteration t >= 1 is
+// net_backward (wgrad = false) with the Anderson gather, then launch_anderson_solve_mix with the same job.
+constexpr int ANDERSON_MAX_WINDOW = 8, ANDERSON_PARTS = 2 * ANDERSON_MAX_WINDOW;
+// device-resident state of one backward pass (zeroed in front of it): H over the slots, gamma of the last solve with the slots it covers (live; 0
+// behind a restart), hist = difference pairs stored since the last restart, restarts
+struct AndersonState {
+    double H[ANDERSON_MAX_WINDOW][ANDERSON_MAX_WINDOW];
+    float gamma[ANDERSON_MAX_WINDOW];
+    int hist, live, restarts, pad;
+};
+struct AndersonJob {
+    int first, window;            // first: iteration 0 (no history: the gather writes z_next and `work` itself; no solve, no mix)
+    float *G, *f;                 // [N, Ds]: G_{t-1} / f_{t-1} in, G_t / f_t out
+    float *dF, *dG;               // the rings, [window][stride]
+    size_t stride;
+    AndersonState *state;
+    double *part;                 // [ANDERSON_PARTS][anderson_blocks(N)]
+};
+inline unsigned anderson_blocks(int64_t n) { return cdiv(n * 16, 256); }
+int launch_anderson_gather(hipStream_t st, const StateGradJob &job, const float *u, bool aligned, int *form);
+int launch_anderson_solve_mix(hipStream_t st, const StateGradJob &job);
 
 // One launch per adjoint iteration for narrow nets (k_adjoint_narrow): a block owns ADJ_NARROW_ROWS rows, forms z_L of them by the gather from the
 // PREVIOUS launch's u (with the gate of iteration L - 1), then runs the whole chain d z -> . W^T (.) act'(a) -> ... down to the own-state and

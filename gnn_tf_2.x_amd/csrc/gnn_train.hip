@@ -1044,18 +1044,32 @@ static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, floa
     adj.iterations = 0; adj.converged = 1;
     adj.gather = adjoint_rows16(Ds) ? ADJ_GATHER_ROWS : ADJ_GATHER_GENERIC;       // (without an iteration; else what the launches report)
     // narrow nets: one launch per iteration (k_adjoint_narrow), decided once per step; mode 2 keeps to the per-kernel chain
-    const bool narrow = adj.mode == 1 && adjoint_narrow_why(ns.m, N) == 0;
+    // (the Anderson solver keeps to the per-kernel chain as well: its gather carries the window's bookkeeping)
+    const bool anderson = adj.solver == 1;
+    const bool narrow = adj.mode == 1 && !anderson && adjoint_narrow_why(ns.m, N) == 0;
+    adj.restarts = 0;
     if (cx->caches.size() != 1) return gnn_fail(GNN_ERR_STATE, "internal: the fixed-point gradient needs one recorded body, not %zu", cx->caches.size());
     float *zb[2] = {nullptr, nullptr}, *work = nullptr;
     int *gates = nullptr;
     if ((rc = buf.get(&zb[0], zf)) || (rc = buf.get(&zb[1], zf)) || (rc = buf.get(&work, zf)) || (rc = buf.get(&gates, gate_blocks * GNN_FLAG_WORDS))) return rc;
     // (not arena->host: gnn_loop_train_step has this step's loss partials on their way into it)
-    int *hgates = static_cast<int *>(arena->gates.get(sizeof(int) * gate_blocks * GNN_FLAG_WORDS));
+    int *hgates = static_cast<int *>(arena->gates.get(sizeof(int) * (gate_blocks * GNN_FLAG_WORDS + 16)));      // (+ the Anderson solver's restart count)
     if (!hgates) return gnn_fail(GNN_ERR_HIP, "hipHostMalloc failed");
     if (N) HIPCHK(hipMemcpyAsync(work, g_state, sizeof(float) * (size_t)N * Ds, hipMemcpyDeviceToDevice, st));
     if (N > 0 && t_max > 0) adj.converged = 0;
     float *ub[2] = {nullptr, nullptr};             // narrow form: u of launch L, [N, 2 Ds] = [own-state columns | aggregated-state columns] of d concat
     if (narrow && ((rc = buf.get(&ub[0], 2 * zf)) || (rc = buf.get(&ub[1], 2 * zf)))) return rc;
+    // Anderson solver: G and f of the iteration before, the two rings of `window` difference rows (2 window + 2 buffers of [N, Ds]), the blocks'
+    // partial dots and the window's device state
+    AndersonJob aj{};
+    if (anderson) {
+        double *part = nullptr, *state_mem = nullptr;
+        aj.window = adj.window; aj.stride = zf;
+        if ((rc = buf.get(&aj.G, zf)) || (rc = buf.get(&aj.f, zf)) || (rc = buf.get(&aj.dF, zf * aj.window)) || (rc = buf.get(&aj.dG, zf * aj.window)) ||
+            (rc = buf.get(&part, (size_t)ANDERSON_PARTS * std::max(anderson_blocks(N), 1u))) || (rc = buf.get(&state_mem, (sizeof(AndersonState) + 7) / 8))) return rc;
+        aj.part = part; aj.state = reinterpret_cast<AndersonState *>(state_mem);
+        HIPCHK(hipMemsetAsync(aj.state, 0, sizeof(AndersonState), st));
+    }
     const gnn_train_arena::Mark mark = arena->mark();
     for (int t = 0; N > 0 && t < t_max && !adj.converged;) {
         const int t0 = t, t1 = std::min(t_max, t0 + (t0 == 0 ? first_chunk : (int)TRAIN_CHUNK));
@@ -1091,11 +1105,15 @@ static int adjoint_backward(gnn_loop *l, gnn_train_ctx *cx, hipStream_t st, floa
             job.gate_prev = t > t0 ? gates + (size_t)(t - t0 - 1) * GNN_FLAG_WORDS : nullptr;
             job.gate = gates + (size_t)(t - t0) * GNN_FLAG_WORDS;
             job.form_out = &adj.gather;
+            if (anderson) { aj.first = t == 0; job.anderson = &aj; }
             float *u = nullptr;
             if ((rc = net_backward(st, buf, ns, cx->caches[0], work, &u, &job, nullptr, 0, false))) return rc;
+            if (anderson && t > 0 && (rc = launch_anderson_solve_mix(st, job))) return rc;
         }
         HIPCHK(hipMemcpyAsync(hgates, gates, sizeof(int) * (size_t)(t1 - t0) * GNN_FLAG_WORDS, hipMemcpyDeviceToHost, st));
+        if (anderson) HIPCHK(hipMemcpyAsync(hgates + gate_blocks * GNN_FLAG_WORDS, &aj.state->restarts, sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (anderson) adj.restarts = hgates[gate_blocks * GNN_FLAG_WORDS];
         adj.iterations = t1;
         for (int i = 0; i < t1 - t0; ++i) {
             int any = 0;

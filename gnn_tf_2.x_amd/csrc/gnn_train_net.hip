@@ -934,6 +934,9 @@ int net_backward(hipStream_t st, Buf &buf, Net &net, const NetCache &c, float *d
     if (job && job->pw_inv) {                      // an iteration of the contraction estimate: z_next = the state gradient * *pw_inv, with its squared norm
         if (wgrad) return gnn_fail(GNN_ERR_STATE, "internal: a power iteration takes no weight gradients");
         if ((rc = launch_power_gather(st, *job, dsg ? dsg : d, dsg != nullptr, job->form_out))) return rc;
+    } else if (job && job->g && job->anderson) {   // an iteration of the Anderson-accelerated adjoint solve: G = g + the state gradient, residual, slot, gate, partial dots
+        if (wgrad) return gnn_fail(GNN_ERR_STATE, "internal: an adjoint iteration takes no weight gradients");
+        if ((rc = launch_anderson_gather(st, *job, dsg ? dsg : d, dsg != nullptr, job->form_out))) return rc;
     } else if (job && job->g) {                    // an adjoint iteration: z_next = g + the state gradient, with the iteration's gate
         if (wgrad) return gnn_fail(GNN_ERR_STATE, "internal: an adjoint iteration takes no weight gradients");
         if ((rc = launch_adjoint_gather(st, *job, dsg ? dsg : d, dsg != nullptr, job->form_out))) return rc;

@@ -307,6 +307,30 @@ int gnn_adjoint_form(int n_layers, const int *dims, const int *acts, const float
 int gnn_adjoint_form_ex(int n_layers, const int *dims, const int *acts, const float *rates, int has_bn, int flags, int64_t n_rows, int *out);
 /* z_final [n_rows, Ds] of the last backward pass of mode 1 / 2, to host memory (test entry point; GNN_ERR_STATE without such a pass). */
 int gnn_loop_adjoint_z(gnn_loop *l, float *z_host);
+/* Solver of the adjoint system (I - J^T) z = g of modes 1 / 2 (opt-in; solver 0, the default, is the iteration z <- g + J^T z above with every launch,
+ * allocation and bit as without this call).  solver 1: Anderson mixing over a window of m = `window` difference pairs - on a linear map a
+ * GMRES-like method that needs only the operator the plain iteration applies; its count grows far slower than 1 / (1 - rho(J)).  z_0 = g; for t = 0, 1, ...:
+ *   G_t, f_t       G_t = g + J^T z_t with the arithmetic of the plain iteration (the input-gradient-only backward pass on the per-kernel chain, the
+ *                  gather's fmaf chain over the arcs in stored order, g + (own + acc)); f_t = G_t - z_t in float32.
+ *   Gate t         the plain iteration's rule on the residual: a node moves when sqrt(sum f_t[r]^2) > theta_adj sqrt(sum z_t[r]^2) (strict; with
+ *                  z_next = G_t this IS the Picard gate).  Closed: z_final = G_t, iterations = t + 1, converged.
+ *   Window         with hist = difference pairs stored since the last restart (0 at t = 0), an iteration t >= 1 writes slot s = hist mod m:
+ *                  dF_s = f_t - f_{t-1}, dG_s = G_t - G_{t-1} in float32; live = min(hist + 1, m).
+ *   Gram           H_ij = dF_i . dF_j and b_i = dF_i . f_t over the live slots, products and sums in double, in a fixed order: per lane over its
+ *                  ascending columns, the 16 lanes of a row by a fixed butterfly, the 16 rows of a block in row order, the blocks in block order in
+ *                  256 runs.  Row and column s of H are new per iteration, the rest stays in a device-resident double matrix; b is recomputed whole.
+ *   Solve          (H + lambda I) gamma = b with lambda = 2^-40 trace(H) / live, by Cholesky in double in one thread.  A pivot that is not > 0, or any
+ *                  value that is not finite, RESTARTS the window: gamma = 0, hist = 0, and the restart is counted.
+ *   Mix            z_{t+1} = G_t - sum_i gamma_i dG_i, gamma rounded to float, the sum a float fmaf chain over ascending slots.
+ * Three kernels per iteration behind the backward pass (gather with residual, slot, gate and the blocks' partial dots; a one-block solve; the mix);
+ * the one-launch iteration of narrow nets is not used.  Control stays on the device as above: iterations are enqueued five at a time, kernels behind a
+ * closed gate change nothing.  No float atomics: two identical steps return identical bits.  Scratch: 2 m + 2 more [n_rows, Ds] float buffers.
+ * The bits of the gradients differ from solver 0's (both lie within the adjoint threshold of the solution).  The method presumes what the mode
+ * presumes, a contraction: without one the forward Loop has no fixed point and the gradient means nothing, whatever this solver returns.
+ * window outside 1 .. 8 or solver outside 0 / 1: GNN_ERR_ARG; solver 1 with world > 1: GNN_ERR_UNSUPPORTED, as the mode.  *used (may be NULL) = the
+ * solver now set.  gnn_loop_adjoint_solver_info: the solver and window set, and the restarts of the last backward pass; any pointer may be NULL. */
+int gnn_loop_set_adjoint_solver(gnn_loop *l, int solver, int window, int *used);
+int gnn_loop_adjoint_solver_info(const gnn_loop *l, int *solver, int *window, int *restarts);
 /* Contraction estimate at the fixed point: how far net_state's map is from a contraction at the state the Loop finds - the condition under which the
  * adjoint iteration of modes 1 / 2 (and the inference Loop near its fixed point) converges.  With p the state the inference Loop stops at, F one body of
  * net_state at p (BatchNormalization on its moving statistics, always) and J = dF/dp over the own-state and aggregated-state columns - the J of the
