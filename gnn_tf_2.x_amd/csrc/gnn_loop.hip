@@ -580,6 +580,9 @@ extern "C" int gnn_loop_set_slice_exchange(gnn_loop *l, int on)
         if (!rc) rc = dev_alloc(&l->agg_own, (size_t)l->shard_rows * l->Ds);
         if (rc) return rc;
         if ((rc = zero_on_stream(l->sl_agg, sizeof(float) * std::max<size_t>(slice, 1), l->stream))) return rc;      // rows past N_global are never written
+        // rows past n_rows of a short shard are never written either (k_slice_unpack), and the full-tile kernel copies all 32 rows of its last
+        // tile (load_tile_given64): layer 0 cuts them, and the fp16 range guard reads what it cuts - stale values there repeated Loops at random
+        if ((rc = zero_on_stream(l->agg_own, sizeof(float) * std::max<size_t>((size_t)l->shard_rows * l->Ds, 1), l->stream))) return rc;
     }
     l->slice_mode = true;
     l->sl_pipeline = on != 2;          // 2: the whole slice is aggregated, then one grouped all-to-all (round-2 form; kept for comparison)
